@@ -13,11 +13,15 @@ flight while the ranks decode; `overlap_ms` = what finish still waited, `gather_
 Decode at N > 1 is the N-GPU decode of that ONE member by byte ranges (lfx_sharded_decode: block finder + scan per range, one
 all-gather of candidate tuples, the same chain walk on every rank; no bit offset from the encoder).  Scaling is weak by default.
 
-The line also carries (N = 1): `roofline` of the dominant kernel with HBM traffic measured IN THIS RUN (two rocprofv3
---pmc child passes of this script: the L2's memory-side read requests by size, WRITE_SIZE), `whole_path` (2(N+C)/t_step against
-the HBM peak), the second write schedule of SURVEY cfg2 (`schedule_S1`), `other_configs` (cfg3, cfg5), `pcie_inclusive`,
-`stream_api` (the reference's io::copy protocol through the stream ABI, from C), `raw_deflate`, `match_fallbacks`, and `cpu_baseline` — the oracle on one host core over the SAME 256 MiB (its output must
-equal the GPU's byte for byte) plus the "N streams on N cores" figure with the host's core count.
+A plain run sets up, warms up, times --steps bare steps (no HIP events inside them), writes the last step's outputs if
+--dump-outputs is given, and prints the line: the metric, its timing (`ms_per_step`, encode / decode split, median) and
+`match_fallbacks`.  Everything else is measured with --full, which also brackets the timed steps' longest kernel with HIP events.
+With --full the line also carries (N = 1): `phases_ms`, `roofline` of the dominant kernel with HBM traffic measured IN THIS RUN
+(two rocprofv3 --pmc child passes of this script: the L2's memory-side read requests by size, WRITE_SIZE), `whole_path`
+(2(N+C)/t_step against the HBM peak), the second write schedule of SURVEY cfg2 (`schedule_S1`), `other_configs` (cfg3, cfg5),
+`pcie_inclusive`, `stream_api` (the reference's io::copy protocol through the stream ABI, from C), `raw_deflate`, and
+`cpu_baseline` — the oracle on one host core over the SAME 256 MiB (its output must equal the GPU's byte for byte) plus the
+"N streams on N cores" figure with the host's core count; at N > 1 `cfg4`, `overlap_ms` and `gather_alone_ms`.
 """
 import argparse
 import csv
@@ -567,6 +571,32 @@ def sub_cfg5(ctx, torch, synth, _ffi, C, dev, reps=2):
             "round_trip_ok": ok, "hbm_frac_algorithmic": round((n + m) / best / 1e9 / HBM_PEAK_GBPS, 5)}
 
 
+DUMP_SAMPLE = 1 << 22      # sampled bytes per dumped array: two arrays of float32 stay near 32 MB (the limit is 64 MB)
+DUMP_EDGE = 4096           # always dumped whole at both ends: the container header, the final block and the trailer
+
+
+def sample_positions(length, seed):
+    """--dump-outputs: the positions of an array of `length` bytes that are dumped — all of them up to DUMP_SAMPLE + 2 DUMP_EDGE,
+    else the first and last DUMP_EDGE and DUMP_SAMPLE seeded positions in between, ascending.  Equal lengths, equal positions."""
+    import numpy as np
+    if length <= DUMP_SAMPLE + 2 * DUMP_EDGE:
+        return np.arange(length, dtype=np.int64)
+    mid = np.sort(np.random.default_rng(seed).integers(DUMP_EDGE, length - DUMP_EDGE, DUMP_SAMPLE, dtype=np.int64))
+    return np.concatenate([np.arange(DUMP_EDGE, dtype=np.int64), mid, np.arange(length - DUMP_EDGE, length, dtype=np.int64)])
+
+
+def dump_outputs(out_dir, torch, encoded, decoded):
+    """What the timed path hands its caller, from the last timed step: the compressed member (`encoded`) and the bytes decoded
+    from it (`decoded`), uint8 device tensors → out_dir/{encoded,decoded}.npy (float32 byte values at sample_positions) and
+    out_dir/lengths.npy (float64: compressed bytes, decoded bytes)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t, seed in (("encoded", encoded, 1), ("decoded", decoded, 2)):
+        idx = torch.from_numpy(sample_positions(int(t.numel()), seed)).to(t.device)
+        np.save(os.path.join(out_dir, name + ".npy"), t[idx].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "lengths.npy"), np.array([encoded.numel(), decoded.numel()], dtype=np.float64))
+
+
 def strong_share(total_bytes, world):
     """--scaling strong: a rank's share of the job — whole blocks, since a shard boundary has to be a block boundary
     (deflate/encode.rs:12, DEFAULT_BLOCK_SIZE = 1 MiB; 8192-byte writes divide it)."""
@@ -610,15 +640,24 @@ def main():
                     help="weak: every rank holds --bytes (256 MiB per GPU: the driver's scaling curve).  strong: --bytes is the "
                          "whole job, split evenly over the ranks (BASELINE.json's metric read literally: 256 MiB at 1/2/4/8 GPUs; "
                          "at 32 MiB per GPU the per-call fixed costs show)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes")
-    ap.add_argument("--no-s1", action="store_true", help="skip the S1 sub-record")
-    ap.add_argument("--no-subs", action="store_true", help="skip the cfg3 / cfg5 sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the metric: per-phase times and the roofline (HIP events around the "
+                         "timed steps' longest kernel, rocprofv3 --pmc child passes), the S1 schedule, cfg3 / cfg5 / cfg4, the "
+                         "host-memory and stream-API figures, raw DEFLATE, the CPU baseline and its byte-for-byte comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (float32 samples of the compressed "
+                         "member and of the decoded bytes, float64 lengths)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-traffic", action="store_true", help="(--full) skip the rocprofv3 --pmc child passes")
+    ap.add_argument("--no-s1", action="store_true", help="(--full) skip the S1 sub-record")
+    ap.add_argument("--no-subs", action="store_true", help="(--full) skip the cfg3 / cfg5 / cfg4, host-memory, stream-API and raw DEFLATE sub-records")
     ap.add_argument("--child", action="store_true", help="(internal) bare timed loop for a profiler pass")
     ap.add_argument("--schedule", choices=["S8K", "S1"], default="S8K",
                     help="write schedule of the encoder: S8K = 8192-byte writes (the metric's configuration), "
                          "S1 = one write_all (one LZ77 chunk, one block: SURVEY cfg2's second schedule)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np  # noqa: F401
     import torch
@@ -828,13 +867,15 @@ def main():
         run.timed(args.steps, args.warmup, record=False)
         return
 
-    elapsed, enc_t, dec_t, m = run.timed(args.steps, args.warmup)
+    elapsed, enc_t, dec_t, m = run.timed(args.steps, args.warmup, record=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, run.d_out[:m] if not sharded_path else run.d_member[:run.member_len], run.d_dec)
     comp = None
-    if not sharded_path:
+    if args.full and not sharded_path:
         import zlib
         comp = run.d_out[:m].cpu().numpy().tobytes()
         assert int.from_bytes(comp[-8:-4], "little") == zlib.crc32(data.tobytes()), "CRC-32 trailer mismatch"
-    elif rank == 0 and world * n <= (1 << 30):
+    elif args.full and rank == 0 and world * n <= (1 << 30):
         import zlib
         member = run.d_member[:run.member_len].cpu().numpy().tobytes()
         whole = b"".join(synth.text(n, seed=synth.SEED_BASE + 2 + r).tobytes() for r in range(world))
@@ -843,7 +884,7 @@ def main():
     #      1 GiB per rank through the same sharded step (all ranks take part; LFX_BENCH_CFG4_BYTES sizes the self-test)
     cfg4 = None
     n4 = int(os.environ.get("LFX_BENCH_CFG4_BYTES", str(1 << 30)))
-    if sharded_path and (world == 8 or "LFX_BENCH_CFG4_BYTES" in os.environ) and not args.no_subs and n4 != n:
+    if args.full and sharded_path and (world == 8 or "LFX_BENCH_CFG4_BYTES" in os.environ) and not args.no_subs and n4 != n:
         try:
             d_in4 = torch.from_numpy(synth.text(n4, seed=synth.SEED_BASE + 40 + rank)).to(dev)
             r4 = Run(args.schedule, n4, d_in4)
@@ -869,12 +910,14 @@ def main():
     steps_sorted = sorted(run.step_s)
     median_s = steps_sorted[len(steps_sorted) // 2] if steps_sorted else None     # (this rank's encode + decode calls of one step)
     peak_measured = None
-    try:
-        peak_measured = measure_copy_peak(torch, dev, min(n, N_BYTES))
-    except Exception:   # noqa: BLE001
-        pass
+    if args.full:
+        try:
+            peak_measured = measure_copy_peak(torch, dev, min(n, N_BYTES))
+        except Exception:   # noqa: BLE001
+            pass
     value = total_bytes / (elapsed / args.steps) / 1e9
-    # ---- roofline of the dominant kernel phase (HIP events on the context's stream, inside the timed region)
+    # ---- roofline of the dominant kernel phase (HIP events on the context's stream, inside the timed region; --full only:
+    #      a plain run records no phases)
     avg = {k: sum(v) / len(v) for k, v in run.phase_acc.items()}        # (the extra, fully instrumented steps)
     kernel_phases = {k: v for k, v in avg.items() if k.split(":")[1] not in ("upload", "start", "done")}
     dom = max(kernel_phases, key=kernel_phases.get) if kernel_phases else None
@@ -917,7 +960,7 @@ def main():
              "traffic_over_algorithmic": round(step_traffic / (2.0 * algo_bytes), 2) if step_traffic else None}
     # ---- the other write schedule of SURVEY cfg2 in the same run (fewer steps: it is a sub-record, not the metric)
     s1 = None
-    if world == 1 and not sharded_path and not args.no_s1:
+    if args.full and world == 1 and not sharded_path and not args.no_s1:
         other = "S1" if args.schedule == "S8K" else "S8K"
         r2 = Run(other)
         e2, en2, de2, m2 = r2.timed(max(1, min(3, args.steps)), 1, record=False)
@@ -928,7 +971,7 @@ def main():
         del r2
     # ---- the other single-GPU configurations of BASELINE.json, as sub-records of the same line
     subs = None
-    if world == 1 and not sharded_path and not args.no_subs and n == N_BYTES:
+    if args.full and world == 1 and not sharded_path and not args.no_subs and n == N_BYTES:
         subs = {}
         for name, fn in (("cfg3_batch_decode", sub_cfg3), ("cfg5_lowent_encode", sub_cfg5)):
             try:
@@ -937,7 +980,7 @@ def main():
                 subs[name] = {"error": "%s: %s" % (type(e).__name__, e)}
             torch.cuda.empty_cache()
     pcie = stream_api = raw_deflate = None
-    if world == 1 and not sharded_path and not args.no_subs:
+    if args.full and world == 1 and not sharded_path and not args.no_subs:
         for name, fn in (("pcie", lambda: sub_pcie(ctx, _ffi, data, run.write)),
                          ("stream_api", lambda: sub_stream_api(ctx, _ffi, data, comp if args.schedule == "S8K" else None)),
                          ("raw_deflate", lambda: sub_raw_deflate(ctx, torch, _ffi, C, d_in, n, run.write))):
@@ -952,7 +995,7 @@ def main():
             else:
                 raw_deflate = rec
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and not sharded_path:
+    if args.full and not args.no_cpu_baseline and world == 1 and not sharded_path:
         import multiprocessing as mp
         import lfo_oracle as oracle
         write = run.write
@@ -1010,23 +1053,26 @@ def main():
                    "offset from the encoder" % world},
         "encode_GBps": round(total_bytes * args.steps / enc_t / 1e9, 4),
         "decode_GBps": round(total_bytes * args.steps / dec_t / 1e9, 4),
-        "phases_ms": {k: round(v, 4) for k, v in sorted(avg.items())},
-        "phases_ms_how": "HIP events behind every phase in extra steps behind the timed loop (an event record between two kernels costs "
-                         "~6 us of idle GPU: the timed steps carry only the two around the longest kernel's phase — " +
-                         str(getattr(run, "bracket_phase", None)) + ", picked from one instrumented step in front of them — whose figure "
-                         "here is theirs); the encode's match and parse phases are split by kernel (timing level 6): lz77_cand = "
-                         "lz77_match7_kernel, lz77_resolve = compaction + resolver, lz77_walk = parse_walk_kernel, lz77_chain = parse_fixseg + "
-                         "parse_fix + parse_emit_hist",
-        "roofline": roof, "whole_path": whole, "schedule_S1" if args.schedule == "S8K" else "schedule_S8K": s1,
-        "other_configs": subs,
-        "pcie_inclusive": pcie,
-        "stream_api": stream_api,
-        "raw_deflate": raw_deflate,
         "match_fallbacks": ctx.match_fallbacks(),
-        "cfg4": cfg4,
-        "cpu_baseline": cpu,
     }
-    if sharded_path:
+    if args.full:
+        line.update({
+            "phases_ms": {k: round(v, 4) for k, v in sorted(avg.items())},
+            "phases_ms_how": "HIP events behind every phase in extra steps behind the timed loop (an event record between two kernels costs "
+                             "~6 us of idle GPU: the timed steps carry only the two around the longest kernel's phase — " +
+                             str(getattr(run, "bracket_phase", None)) + ", picked from one instrumented step in front of them — whose figure "
+                             "here is theirs); the encode's match and parse phases are split by kernel (timing level 6): lz77_cand = "
+                             "lz77_match7_kernel, lz77_resolve = compaction + resolver, lz77_walk = parse_walk_kernel, lz77_chain = parse_fixseg + "
+                             "parse_fix + parse_emit_hist",
+            "roofline": roof, "whole_path": whole, "schedule_S1" if args.schedule == "S8K" else "schedule_S8K": s1,
+            "other_configs": subs,
+            "pcie_inclusive": pcie,
+            "stream_api": stream_api,
+            "raw_deflate": raw_deflate,
+            "cfg4": cfg4,
+            "cpu_baseline": cpu,
+        })
+    if args.full and sharded_path:
         # what lfx_sharded_encode_finish still had to wait for after the decode (max over ranks, mean over steps): the part of
         # the concatenation that did NOT hide behind the decode, plus placing the shards on rank 0
         fin = getattr(run, "finish_max_s", None)

@@ -55,3 +55,21 @@ def test_strong_scaling_share_is_whole_blocks():
         for world in (1, 2, 3, 4, 7, 8):
             n = bench.strong_share(total, world)
             assert n % (1 << 20) == 0 and n >= 1 << 20 and n * world <= max(total, world << 20)
+
+
+def test_dump_sample_positions_are_fixed_and_bounded():
+    """--dump-outputs: the same positions for the same length in every run, the container's ends always in, at most 64 MB
+    for the two float32 arrays of a 256 MiB step."""
+    import bench
+    import numpy as np
+    assert np.array_equal(bench.sample_positions(1000, 1), np.arange(1000))
+    N = 256 << 20
+    for n in (N, 130_000_000, bench.DUMP_SAMPLE + 2 * bench.DUMP_EDGE + 1):
+        p = bench.sample_positions(n, 1)
+        assert np.array_equal(p, bench.sample_positions(n, 1))
+        assert len(p) == bench.DUMP_SAMPLE + 2 * bench.DUMP_EDGE and p[0] == 0 and p[-1] == n - 1
+        assert (np.diff(p) >= 0).all() and 0 <= p.min() and p.max() < n
+        assert np.array_equal(p[:bench.DUMP_EDGE], np.arange(bench.DUMP_EDGE))
+        assert np.array_equal(p[-bench.DUMP_EDGE:], np.arange(n - bench.DUMP_EDGE, n))
+    assert not np.array_equal(bench.sample_positions(N, 1), bench.sample_positions(N, 2))
+    assert 2 * 4 * len(bench.sample_positions(N, 1)) <= 64 << 20

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out; mkdir -p $O
 cd $R
-timeout 600 python bench.py > $O/r2_bench_default.json 2> $O/r2_bench_default.err; echo "bench rc=$?"; tail -c 600 $O/r2_bench_default.json
+timeout 600 python bench.py --full > $O/r2_bench_default.json 2> $O/r2_bench_default.err; echo "bench rc=$?"; tail -c 600 $O/r2_bench_default.json
 cd /tmp
 rm -rf $O/kt_r2
 timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_r2 -- python $R/bench.py --child --steps 5 --warmup 2 > $O/kt_r2.log 2>&1

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out; mkdir -p $O
 cd $R
 timeout 1800 python -m pytest tests -q -m gpu > $O/r3_suite.log 2>&1; tail -4 $O/r3_suite.log
-timeout 900 python bench.py > $O/r3_bench_default.json 2> $O/r3_bench_default.err; echo "bench rc=$?"; cut -c1-400 $O/r3_bench_default.json
+timeout 900 python bench.py --full > $O/r3_bench_default.json 2> $O/r3_bench_default.err; echo "bench rc=$?"; cut -c1-400 $O/r3_bench_default.json
 cd /tmp
 rm -rf $O/kt_r3
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_r3 -- python $R/bench.py --child --steps 5 --warmup 2 > $O/kt_r3.log 2>&1

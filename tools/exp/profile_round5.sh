@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out; mkdir -p $O
 cd $R
 timeout 1800 python -m pytest tests -q -m gpu > $O/r5_suite.log 2>&1; tail -4 $O/r5_suite.log | grep -v amdgpu > $O/r05_gpu_suite_tail.txt; cat $O/r05_gpu_suite_tail.txt
-timeout 1200 python bench.py > $O/r05_bench_default.json 2> $O/r05_bench_default.err; echo "bench rc=$?"; cut -c1-400 $O/r05_bench_default.json
+timeout 1200 python bench.py --full > $O/r05_bench_default.json 2> $O/r05_bench_default.err; echo "bench rc=$?"; cut -c1-400 $O/r05_bench_default.json
 cd /tmp
 rm -rf /tmp/kt_r5
 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/kt_r5 -- python $R/bench.py --child --steps 5 --warmup 2 > /tmp/kt_r5.log 2>&1
@@ -31,9 +31,9 @@ timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/kt_c3 -- python $R/tools/ex
 python $R/tools/prof_summary.py /tmp/kt_c3 "rocprofv3 --kernel-trace --stats -- python tools/exp/cfg3_run.py (4096 x 64 KiB zlib streams: one batch encode of 2048, four batch decodes of 4096)" 2>/dev/null | grep -v "at::native\|elementwise" > $O/r05_cfg3_kernel_stats.csv; head -5 $O/r05_cfg3_kernel_stats.csv | cut -c1-150
 cd $R
 timeout 300 python tools/bench_small.py 8192 65536 262144 1048576 4194304 16777216 33554432 67108864 100663296 134217728 > $O/r05_small_sizes.json 2>/dev/null; cut -c1-300 $O/r05_small_sizes.json
-timeout 300 python bench.py --schedule S1 --no-traffic --no-cpu-baseline --no-s1 --no-subs --steps 5 --warmup 2 2>/dev/null | tail -1 > $O/r05_bench_s1.json; cut -c1-200 $O/r05_bench_s1.json
+timeout 300 python bench.py --full --schedule S1 --no-traffic --no-cpu-baseline --no-s1 --no-subs --steps 5 --warmup 2 2>/dev/null | tail -1 > $O/r05_bench_s1.json; cut -c1-200 $O/r05_bench_s1.json
 LFX_FUZZ=500 timeout 900 python -m pytest tests/test_gpu_fuzz.py -q -m gpu 2>&1 | tail -2 | grep -v amdgpu > $O/r05_fuzz.txt; cat $O/r05_fuzz.txt
 timeout 400 python tools/exp/m5_stress.py 1000 2>&1 | tail -1 >> $O/r05_fuzz.txt; tail -1 $O/r05_fuzz.txt
-LFX_BENCH_FORCE_SHARDED=1 timeout 300 python bench.py --steps 10 --warmup 3 --no-subs --no-cpu-baseline --no-s1 --no-traffic 2>/dev/null | tail -1 > $O/r05_bench_force_sharded_world1.txt; cut -c1-160 $O/r05_bench_force_sharded_world1.txt
-LFX_BENCH_ONE_GPU=1 LFX_BENCH_CFG4_BYTES=134217728 timeout 900 python bench.py --gpus 3 --steps 3 --warmup 1 --bytes 67108864 --no-cpu-baseline --no-s1 --no-traffic 2>/dev/null | grep "^{" | tail -1 > $O/r05_bench_one_gpu_3ranks.txt; cut -c1-160 $O/r05_bench_one_gpu_3ranks.txt
-LFX_BENCH_ONE_GPU=1 timeout 900 python bench.py --gpus 3 --steps 3 --warmup 1 --scaling strong --no-subs --no-cpu-baseline --no-s1 --no-traffic 2>/dev/null | grep "^{" | tail -1 > $O/r05_bench_one_gpu_3ranks_strong.txt; cut -c1-160 $O/r05_bench_one_gpu_3ranks_strong.txt
+LFX_BENCH_FORCE_SHARDED=1 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-subs --no-cpu-baseline --no-s1 --no-traffic 2>/dev/null | tail -1 > $O/r05_bench_force_sharded_world1.txt; cut -c1-160 $O/r05_bench_force_sharded_world1.txt
+LFX_BENCH_ONE_GPU=1 LFX_BENCH_CFG4_BYTES=134217728 timeout 900 python bench.py --full --gpus 3 --steps 3 --warmup 1 --bytes 67108864 --no-cpu-baseline --no-s1 --no-traffic 2>/dev/null | grep "^{" | tail -1 > $O/r05_bench_one_gpu_3ranks.txt; cut -c1-160 $O/r05_bench_one_gpu_3ranks.txt
+LFX_BENCH_ONE_GPU=1 timeout 900 python bench.py --full --gpus 3 --steps 3 --warmup 1 --scaling strong --no-subs --no-cpu-baseline --no-s1 --no-traffic 2>/dev/null | grep "^{" | tail -1 > $O/r05_bench_one_gpu_3ranks_strong.txt; cut -c1-160 $O/r05_bench_one_gpu_3ranks_strong.txt

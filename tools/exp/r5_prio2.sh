@@ -5,7 +5,7 @@ echo "prio off: $(LFX_SO=$PWD/libflate_amd/liblfx_a.so timeout 300 python tools/
 echo "prio on:  $(timeout 300 python tools/exp/enc_timing.py 268435456 8192 5 2>&1 | grep -E 'rep 4|rror' | sed 's/.*| dec //' | cut -c1-200)"
 LFX_DEBUG=1 timeout 300 python tools/exp/enc_timing.py 268435456 8192 1 2>&1 | grep -E "K2 block" | head -3
 for so in liblfx_a.so liblfx.so; do
-  LFX_SO=$PWD/libflate_amd/$so timeout 300 python bench.py --no-cpu-baseline --no-traffic --no-s1 2>/dev/null | tail -1 | python -c "
+  LFX_SO=$PWD/libflate_amd/$so timeout 300 python bench.py --full --no-cpu-baseline --no-traffic --no-s1 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d.get('cfg3_batch_decode',{})
 print('$so', 'value', d['value'], 'cfg3', {k: s.get(k) for k in ('value','decode_GBps','encode_GBps','decode_ms','encode_ms')}, 'cfg5', {k: d.get('cfg5_lowent_encode',{}).get(k) for k in ('encode_GBps','decode_ms')})"

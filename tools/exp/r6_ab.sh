@@ -4,8 +4,8 @@
 out=$1; shift
 mkdir -p "$out"
 for rep in 1 2; do
-  python bench.py --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 > "$out/base_$rep.log" 2>&1
-  env "$@" python bench.py --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 > "$out/alt_$rep.log" 2>&1
+  python bench.py --full --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 > "$out/base_$rep.log" 2>&1
+  env "$@" python bench.py --full --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 > "$out/alt_$rep.log" 2>&1
 done
 python - "$out" <<'PY'
 import json, sys, glob

@@ -4,9 +4,9 @@
 out=$1; shift
 mkdir -p "$out"
 for rep in 1 2; do
-  python bench.py --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 > "$out/product_$rep.log" 2>&1
+  python bench.py --full --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 > "$out/product_$rep.log" 2>&1
   for so in "$@"; do
-    LFX_SO=$GRAFT_REPO_ROOT/$so python bench.py --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 > "$out/$(basename $so .so)_$rep.log" 2>&1
+    LFX_SO=$PWD/$so python bench.py --full --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 > "$out/$(basename $so .so)_$rep.log" 2>&1
   done
 done
 python - "$out" <<'PY'

@@ -7,7 +7,7 @@ mkdir -p $out
 timeout 1200 python -m pytest tests -m gpu -x -q -k "$kexpr" > $out/pytest.log 2>&1; tail -3 $out/pytest.log; grep -c "corrupted\|Aborted" $out/pytest.log
 for rep in 1 2; do
   for v in "" "$sw"; do
-    env $v python bench.py --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 2>/dev/null | python -c "
+    env $v python bench.py --full --steps 10 --warmup 3 --no-subs --no-traffic --no-cpu-baseline --no-s1 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); p=d['phases_ms']; print('[$v]', d['value'], d['encode_GBps'], d['decode_GBps'], 'parse', p['enc:lz77_parse'], 'match', p['enc:lz77_match'])"
   done
