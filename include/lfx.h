@@ -135,6 +135,26 @@ int lfx_decode_batch_device(lfx_ctx *c, int format, uint32_t count, const void *
                             const uint64_t *in_off, const uint64_t *in_len, void *d_out,
                             const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
                             int32_t *status);
+/* gzip::MultiDecoder (gzip.rs:1052-1167) over a whole buffer, with the members decoded as ONE batch: the members are found
+ * on the device (candidate offsets, header parse, a walk of their blocks that produces no output), chained on the host
+ * from byte 0, and the chained members go through the batch decoder; whatever that pass does not settle (a damaged
+ * member, a start that is no candidate, a member longer than the walk, output that does not fit, the end of the input)
+ * is decoded by the sequential member loop of lfx_decode_device from that member on.  Status, *out_len, *consumed,
+ * lfx_ctx_last_error and d_out[0 .. *out_len) are exactly those of
+ * lfx_decode_device(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, d_out, cap, ...).
+ * members: the members whose trailer was verified, in input order; *n_members = their count (also when that exceeds
+ * max_members: only the first max_members entries are written).  members may be NULL. */
+typedef struct lfx_member {
+    uint64_t in_off, in_len;   /* the member's bytes in the input: header .. 8-byte trailer */
+    uint64_t out_off, out_len; /* its output in d_out */
+} lfx_member;                  /* 32 bytes */
+int lfx_decode_members_device(lfx_ctx *c, const void *d_in, uint64_t n, void *d_out, uint64_t cap,
+                              uint64_t *out_len, uint64_t *consumed,
+                              lfx_member *members, uint32_t max_members, uint32_t *n_members);
+/* same, host buffers (staged like lfx_decode_host) */
+int lfx_decode_members_host(lfx_ctx *c, const void *in, uint64_t n, void *out, uint64_t cap,
+                            uint64_t *out_len, uint64_t *consumed,
+                            lfx_member *members, uint32_t max_members, uint32_t *n_members);
 
 /* ---- sharded encode: independent block ranges per rank, one gzip/zlib/deflate member
  * (SURVEY §8e).  prepare() runs match finding → Huffman build and the checksums and reports the

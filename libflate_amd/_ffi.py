@@ -31,7 +31,7 @@ EXPORTS = [
     "lfx_lz77_free", "lfx_ctx_last_timing", "lfx_ctx_enable_timing", "lfx_version",
     "lfx_comm_rccl", "lfx_comm_rccl_free", "lfx_sharded_encode_begin", "lfx_sharded_encode_finish", "lfx_sharded_byte_range",
     "lfx_sharded_decode", "lfx_sharded_layout", "lfx_sharded_gather_tuples", "lfx_sharded_fold", "lfx_sharded_free",
-    "lfx_host_alloc", "lfx_host_free", "lfx_ctx_match_fallbacks",
+    "lfx_host_alloc", "lfx_host_free", "lfx_ctx_match_fallbacks", "lfx_decode_members_device", "lfx_decode_members_host",
 ]
 
 
@@ -56,6 +56,11 @@ class BlkTuple(C.Structure):
                 ("n_codes", C.c_uint32), ("nlanes", C.c_uint32), ("btype", C.c_uint8), ("bfinal", C.c_uint8),
                 ("status", C.c_uint8), ("_pad", C.c_uint8), ("rank", C.c_uint16), ("_pad2", C.c_uint16),
                 ("slot", C.c_uint32), ("_pad3", C.c_uint32)]
+
+
+class Member(C.Structure):
+    """lfx_member: one verified member of a multi-member gzip input (32 bytes)"""
+    _fields_ = [("in_off", C.c_uint64), ("in_len", C.c_uint64), ("out_off", C.c_uint64), ("out_len", C.c_uint64)]
 
 
 class ShardInfo(C.Structure):
@@ -155,6 +160,10 @@ def lib():
     L.lfx_decode_device.argtypes = [vp, i32, u32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.lfx_decode_host.argtypes = [vp, i32, u32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.lfx_decode_batch_device.argtypes = [vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lfx_decode_members_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,
+                                            C.POINTER(u32)]
+    L.lfx_decode_members_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,
+                                          C.POINTER(u32)]
     L.lfx_encode_batch_device.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lfx_encode_shard_prepare.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, u64, i32,
                                            i32, C.POINTER(ShardInfo)]

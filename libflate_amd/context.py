@@ -107,6 +107,37 @@ class Context:
             raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
         return rc, out_len.value, consumed.value, self.last_error() if rc else ""
 
+    def decode_members_device(self, d_in, n, d_out, cap, max_members=None):
+        """gzip::MultiDecoder over device bytes, the members decoded as one batch (lfx_decode_members_device)
+        → (status, out_len, consumed, members, message); members = [(in_off, in_len, out_off, out_len)] of the verified
+        members, at most max_members of them (None: room for every member n bytes can hold)"""
+        return self._members(_ffi.lib().lfx_decode_members_device, d_in, n, d_out, cap, max_members)
+
+    def _members(self, fn, src, n, dst, cap, max_members):
+        if max_members is None:
+            max_members = n // 20 + 1           # (a gzip member takes at least 20 bytes)
+        table = (_ffi.Member * max(int(max_members), 1))()
+        out_len, consumed, count = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        rc = fn(self._h, src, n, dst, cap, C.byref(out_len), C.byref(consumed), table, int(max_members), C.byref(count))
+        if rc in (_ffi.E_DEVICE, _ffi.E_OOM, _ffi.E_ARG):
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        members = [(m.in_off, m.in_len, m.out_off, m.out_len) for m in table[:min(count.value, int(max_members))]]
+        return rc, out_len.value, consumed.value, members, self.last_error() if rc else ""
+
+    def decode_members_host(self, data, cap=None, max_members=None):
+        """the same on host bytes (lfx_decode_members_host) → (status, output_so_far, consumed, members, message); like
+        decode_host, a cap left to None grows while the output does not fit"""
+        data = bytes(data)
+        grow = cap is None
+        cap = cap if cap is not None else max(1 << 16, len(data) * 16)
+        while True:
+            out = C.create_string_buffer(cap)
+            rc, ol, used, members, msg = self._members(_ffi.lib().lfx_decode_members_host, data, len(data), out, cap, max_members)
+            if grow and rc == _ffi.E_NOSPACE and cap < len(data) * 1040 + (1 << 20):
+                cap *= 8
+                continue
+            return rc, out.raw[:ol], used, members, msg
+
     def encode_host(self, fmt, data, opts=None, schedule=None):
         data = bytes(data)
         bound = _ffi.lib().lfx_encode_bound(len(data), C.byref(opts) if opts is not None else None,

@@ -860,17 +860,21 @@ struct DecodeOutcome {
     int status = LFX_OK;
     uint64_t out_len = 0, delivered_len = 0, consumed = 0;
     bool header_failed = false;  // the FIRST member's container header was rejected
+    bool more = false;           // one_member: the member was verified and the loop stopped in front of the next one (at consumed)
     std::string msg;
 };
 
+// The member loop from input byte `base` on, its output from d_out[out_at] on (the members in front of `base` were decoded
+// into d_out[0, out_at) and verified by the caller; base == 0 is the first member).  one_member: return behind the first
+// member whose trailer was verified (oc.more), without looking at what follows.  members: the verified members are appended.
 int decode_stream(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_t n, uint8_t *d_out,
-                  uint64_t cap, DecodeOutcome &oc) {
+                  uint64_t cap, DecodeOutcome &oc, uint64_t base = 0, uint64_t out_at = 0, bool one_member = false,
+                  std::vector<lfx_member> *members = nullptr) {
     (void)hipSetDevice(c->device);
     hipStream_t st = c->stream;
-    c->n_ev = 0;
-    c->phase("start");
-    uint64_t base = 0, out_at = 0;
-    bool first = true;
+    bool first = base == 0;
+    oc.consumed = base;
+    oc.out_len = oc.delivered_len = out_at;
     int rc;
     if ((rc = c->d_res.reserve(256))) return rc;
     if ((rc = c->d_small.reserve(70000))) return rc;
@@ -952,13 +956,14 @@ int decode_stream(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint6
                 }
             }
         }
+        if (members) members->push_back(lfx_member{base, oc.consumed - base, out_at, mr.out_len});
         out_at = oc.out_len;
+        if (one_member) { oc.more = true; break; }
         if (!(format == LFX_GZIP && (flags & LFX_DEC_MULTI))) break;
         base = oc.consumed;
         first = false;
     }
     oc.out_len = oc.delivered_len = out_at;
-    c->phase("done");
     return LFX_OK;
 }
 
@@ -970,9 +975,13 @@ extern "C" int lfx_decode_device(lfx_ctx *cc, int format, uint32_t flags, const 
     Ctx *c = reinterpret_cast<Ctx *>(cc);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     if (format < 0 || format > 2) return LFX_E_ARG;
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
     DecodeOutcome oc;
     int rc = decode_stream(c, format, flags, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, oc);
     if (rc) return rc;
+    if (oc.status == LFX_OK) c->phase("done");
     if (oc.out_len > cap) oc.out_len = cap;  // defensive: never report more than the buffer holds
     if (out_len) *out_len = oc.out_len;
     if (consumed) *consumed = oc.consumed;
@@ -1495,18 +1504,12 @@ static int batch_fast(Ctx *c, const uint8_t *d_in, uint64_t n_in, uint8_t *d_out
 }
 }  // namespace lfx
 
-extern "C" int lfx_decode_batch_device(lfx_ctx *cc, int format, uint32_t count, const void *d_in,
-                                       const uint64_t *in_off, const uint64_t *in_len, void *d_out,
-                                       const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
-                                       int32_t *status) try {
-    if (!cc) return LFX_E_DEVICE;
-    Ctx *c = reinterpret_cast<Ctx *>(cc);
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    (void)hipSetDevice(c->device);
+namespace {
+// the body of lfx_decode_batch_device: res[i] = stream i's verdict (trailer included), used[i] = its bytes consumed
+int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uint64_t *in_off, const uint64_t *in_len,
+                 void *d_out, const uint64_t *out_off, const uint64_t *out_cap, std::vector<InflateResult> &res,
+                 std::vector<uint64_t> *used = nullptr) {
     hipStream_t st = c->stream;
-    c->n_ev = 0;
-    c->phase("start");
-    if (!count) return LFX_OK;
     std::vector<DecStream> streams(count);
     for (uint32_t i = 0; i < count; i++) streams[i] = DecStream{in_off[i], in_len[i], out_off[i], out_cap[i]};
     int rc;
@@ -1572,10 +1575,32 @@ extern "C" int lfx_decode_batch_device(lfx_ctx *cc, int format, uint32_t count, 
                                           sizeof(InflateResult) / 8, d_crc, d_adler));   // out_off / out_len fields
     LAUNCH_TRY(launch_verify_trailers(st, format, count, (const uint8_t *)d_in, d_streams, d_hdrs,
                                       (InflateResult *)c->d_dec_state.p, d_crc, d_adler, d_consumed));
-    std::vector<InflateResult> res(count);
+    res.resize(count);
     HIP_TRY(hipMemcpyAsync(res.data(), c->d_dec_state.p, sizeof(InflateResult) * count, hipMemcpyDeviceToHost, st));
+    if (used) {
+        used->resize(count);
+        HIP_TRY(hipMemcpyAsync(used->data(), d_consumed, 8ull * count, hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
     c->phase("verify");
+    return LFX_OK;
+}
+}  // namespace
+
+extern "C" int lfx_decode_batch_device(lfx_ctx *cc, int format, uint32_t count, const void *d_in,
+                                       const uint64_t *in_off, const uint64_t *in_len, void *d_out,
+                                       const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
+                                       int32_t *status) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    if (!count) return LFX_OK;
+    std::vector<InflateResult> res;
+    int rc = decode_batch(c, format, count, d_in, in_off, in_len, d_out, out_off, out_cap, res);
+    if (rc) return rc;
     int worst = LFX_OK;
     for (uint32_t i = 0; i < count; i++) {
         if (out_len) out_len[i] = res[i].out_len;
@@ -1584,6 +1609,268 @@ extern "C" int lfx_decode_batch_device(lfx_ctx *cc, int format, uint32_t count, 
         if (s != LFX_OK && worst == LFX_OK) { worst = s; c->set_error(format_error(res[i].err, res[i].a0, res[i].a1)); }
     }
     return LFX_OK;  // per-stream results are in status[]
+} LFX_ABI_CATCH
+
+// ------------------------------------------------------------------------------------------------
+// gzip::MultiDecoder as one batch (lfx_decode_members_device).  Five steps: the candidate finder
+// (lfx_members.hip), a header parse and a block walk of every candidate that produce no output, the chain from byte 0 on the
+// host, ONE batch decode of the chained members, and the sequential member loop (decode_stream) for the rest of the input
+// from the first member the batch did not settle.  Every error, every partial output and the clean end come from that loop,
+// so the result is lfx_decode_device(LFX_GZIP, LFX_DEC_MULTI)'s by construction; the batch only settles members that loop
+// would have decoded without a fault.
+namespace {
+constexpr uint32_t MEMBER_DENSE = 64;          // a tile with more candidates than this (one per 256 bytes) is not listed: a chain
+                                               // start inside it goes through the sequential loop (a stored member full of magic)
+constexpr uint32_t MEMBER_GROUP = 4096;        // candidates parsed and walked together, members decoded by one batch call
+constexpr uint32_t MEMBER_WALK_ROUNDS = 4;     // blocks a walk follows (batch_fast's MAX_ROUNDS) ...
+constexpr uint64_t MEMBER_WALK_BYTES = 4ull << 20;   // ... and input bytes it covers; a member beyond either is "long"
+constexpr uint64_t MEMBER_HDR_BYTES = 64ull << 10;   // header bytes a candidate's parse may read (a longer header: sequential)
+
+// the nested decodes record phases of their own: the members path names only its five (and "start")
+struct PhaseMute {
+    Ctx *c;
+    int saved;
+    explicit PhaseMute(Ctx *c_) : c(c_), saved(c_->timing_on) { c->timing_on = 0; }
+    ~PhaseMute() { c->timing_on = saved; }
+};
+
+struct MemberWalk {
+    uint64_t end_byte = 0;   // byte behind the member's last DEFLATE byte (its trailer starts here)
+    uint64_t n_out = 0;
+    uint8_t state = 0;       // 0 not walked, 1 walked to its BFINAL block, 2 not a member the walk could follow
+};
+
+// cand = the candidate offsets of d_in[0, n) in input order, without those of tiles denser than MEMBER_DENSE
+int member_candidates(Ctx *c, const uint8_t *d_in, uint64_t n, std::vector<uint64_t> &cand) {
+    hipStream_t st = c->stream;
+    cand.clear();
+    const uint64_t ntiles = member_tiles(n);
+    if (!ntiles) return LFX_OK;
+    int rc;
+    if ((rc = c->d_dec_tmp.reserve(4 * ntiles))) return rc;
+    LAUNCH_TRY(launch_member_count(st, d_in, n, (uint32_t *)c->d_dec_tmp.p));
+    std::vector<uint32_t> cnt(ntiles);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), c->d_dec_tmp.p, 4 * ntiles, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<uint64_t> pos(ntiles);
+    uint64_t total = 0;
+    for (uint64_t t = 0; t < ntiles; t++) {
+        if (cnt[t] > MEMBER_DENSE || cnt[t] == 0) { pos[t] = MEMBER_SKIP; continue; }
+        pos[t] = total;
+        total += cnt[t];
+    }
+    if (!total) return LFX_OK;
+    if ((rc = c->d_dec_tmp.reserve(8 * ntiles + 8 * total))) return rc;
+    uint64_t *d_pos = (uint64_t *)c->d_dec_tmp.p, *d_cand = d_pos + ntiles;
+    HIP_TRY(hipMemcpyAsync(d_pos, pos.data(), 8 * ntiles, hipMemcpyHostToDevice, st));
+    LAUNCH_TRY(launch_member_emit(st, d_in, n, d_pos, d_cand, total));
+    cand.resize(total);
+    HIP_TRY(hipMemcpyAsync(cand.data(), d_cand, 8 * total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LFX_OK;
+}
+
+// header parse and block walk of candidates [k0, k1): walk[k] for each
+int member_walk(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<uint64_t> &cand, size_t k0, size_t k1,
+                std::vector<MemberWalk> &walk) {
+    hipStream_t st = c->stream;
+    const uint32_t cnt = (uint32_t)(k1 - k0);
+    if (!cnt) return LFX_OK;
+    int rc;
+    std::vector<DecStream> ds(cnt);
+    for (uint32_t i = 0; i < cnt; i++) ds[i] = DecStream{cand[k0 + i], std::min(n - cand[k0 + i], MEMBER_HDR_BYTES), 0, 0};
+    const size_t sz_ds = sizeof(DecStream) * cnt, sz_dh = sizeof(DecHeader) * cnt;
+    if ((rc = c->d_dec_blocks.reserve(sz_ds + sz_dh))) return rc;
+    DecStream *d_ds = (DecStream *)c->d_dec_blocks.p;
+    DecHeader *d_dh = (DecHeader *)((uint8_t *)c->d_dec_blocks.p + sz_ds);
+    HIP_TRY(hipMemcpyAsync(d_ds, ds.data(), sz_ds, hipMemcpyHostToDevice, st));
+    LAUNCH_TRY(launch_container(st, LFX_GZIP, cnt, d_in, d_ds, d_dh));
+    std::vector<DecHeader> dh(cnt);
+    HIP_TRY(hipMemcpyAsync(dh.data(), d_dh, sz_dh, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // the walk: one block per live candidate and round, the scan kernel of the batch path (no output)
+    struct Live { size_t k; uint64_t bit, end_bit, produced; };
+    std::vector<Live> live;
+    for (uint32_t i = 0; i < cnt; i++) {
+        const size_t k = k0 + i;
+        walk[k].state = 2;
+        if (dh[i].status != 0) continue;
+        const uint64_t data = cand[k] + dh[i].deflate_off;
+        // the range a block may end in: up to the next candidate (a member's trailer lies in front of the next member's
+        // header), at most MEMBER_WALK_BYTES
+        uint64_t lim = std::min<uint64_t>(n, cand[k] + MEMBER_WALK_BYTES);
+        const auto nx = std::upper_bound(cand.begin(), cand.end(), data);
+        if (nx != cand.end() && *nx < lim) lim = *nx;
+        if (lim <= data) continue;
+        live.push_back(Live{k, data * 8, lim * 8, 0});
+    }
+    for (uint32_t round = 0; round < MEMBER_WALK_ROUNDS && !live.empty(); round++) {
+        const uint32_t nj = (uint32_t)live.size();
+        std::vector<BlkJob> bj(nj);
+        uint64_t range_bits = 0;
+        for (uint32_t q = 0; q < nj; q++) {
+            bj[q] = BlkJob{live[q].bit, live[q].end_bit};
+            range_bits += live[q].end_bit - live[q].bit;
+        }
+        if ((rc = c->d_dec_streams.reserve(sizeof(BlkJob) * nj))) return rc;
+        if ((rc = c->d_dec_state.reserve(sizeof(BlkInfo) * nj))) return rc;
+        if ((rc = c->d_dec_cand.reserve(sizeof(BlkLanes) * (size_t)nj))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_dec_streams.p, bj.data(), sizeof(BlkJob) * nj, hipMemcpyHostToDevice, st));
+        const bool small = !c->diag.no_small_scan && range_bits / nj < (512ull << 10);
+        LAUNCH_TRY(launch_blk_scan(st, d_in, n, (const BlkJob *)c->d_dec_streams.p, nj, (BlkInfo *)c->d_dec_state.p,
+                                   (BlkLanes *)c->d_dec_cand.p, nullptr, small));
+        std::vector<BlkInfo> bi(nj);
+        HIP_TRY(hipMemcpyAsync(bi.data(), c->d_dec_state.p, sizeof(BlkInfo) * nj, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<Live> next;
+        for (uint32_t q = 0; q < nj; q++) {
+            Live l = live[q];
+            const BlkInfo &r = bi[q];
+            if (r.status != BLK_OK || r.end_bit <= l.bit || r.end_bit > l.end_bit) continue;    // state stays 2
+            l.produced += r.n_out;
+            if (r.bfinal) {
+                MemberWalk &w = walk[l.k];
+                w.end_byte = (r.end_bit + 7) / 8;
+                w.n_out = l.produced;
+                w.state = 1;
+            } else { l.bit = r.end_bit; next.push_back(l); }
+        }
+        live.swap(next);
+    }
+    return LFX_OK;   // (still live after the last round: a long member, state 2)
+}
+
+struct ChainEntry {
+    lfx_member m;
+    bool batch;   // decoded by the batch (else: already decoded and verified by the sequential loop)
+};
+
+int decode_members(Ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, DecodeOutcome &oc,
+                   std::vector<lfx_member> &members) {
+    int rc;
+    // ---- 1. candidates
+    std::vector<uint64_t> cand;
+    if ((rc = member_candidates(c, d_in, n, cand))) return rc;
+    c->phase("candidates");
+    // ---- 2.-4. header parse and walk (a group of candidates at a time, from the one the chain has reached), the chain
+    std::vector<MemberWalk> walk(cand.size());
+    std::vector<ChainEntry> chain;
+    uint64_t base = 0, out_at = 0;
+    size_t walked_to = 0;   // candidates in front of this one were walked or passed over
+    while (base < n) {
+        const size_t k = (size_t)(std::lower_bound(cand.begin(), cand.end(), base) - cand.begin());
+        const bool is_cand = k < cand.size() && cand[k] == base;
+        if (is_cand && k >= walked_to) {
+            const size_t k1 = std::min<size_t>(cand.size(), k + MEMBER_GROUP);
+            if ((rc = member_walk(c, d_in, n, cand, k, k1, walk))) return rc;
+            walked_to = k1;
+            if (c->n_ev + 6 < 17) c->phase("walk");
+        }
+        if (is_cand && walk[k].state == 1) {
+            const MemberWalk &w = walk[k];
+            if (n - w.end_byte < 8 || w.n_out > cap - out_at) break;   // a cut trailer, output that does not fit: the tail says so
+            chain.push_back(ChainEntry{lfx_member{base, w.end_byte + 8 - base, out_at, w.n_out}, true});
+            base = w.end_byte + 8;
+            out_at += w.n_out;
+            continue;
+        }
+        // no candidate here (a dense tile, reserved FLG bits, not a header at all), or one the walk could not follow (a long
+        // member, a damaged one): ONE member through the sequential loop; anything but a verified member ends the chain
+        DecodeOutcome one;
+        std::vector<lfx_member> got;
+        {
+            PhaseMute mute(c);
+            if ((rc = decode_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, d_out, cap, one, base, out_at, true, &got))) return rc;
+        }
+        if (!one.more || got.size() != 1) break;
+        chain.push_back(ChainEntry{got[0], false});
+        base = one.consumed;
+        out_at = one.out_len;
+    }
+    c->phase("chain");
+    // ---- 5. the chained members through the batch decoder, MEMBER_GROUP at a time; the first one it does not verify
+    // (or that comes out other than walked) is where the tail starts
+    uint64_t tail_base = base, tail_out = out_at;
+    size_t keep = chain.size();
+    for (size_t e0 = 0; e0 < chain.size() && keep == chain.size();) {
+        std::vector<size_t> idx;
+        size_t e1 = e0;
+        for (; e1 < chain.size() && idx.size() < MEMBER_GROUP; e1++)
+            if (chain[e1].batch) idx.push_back(e1);
+        e0 = e1;
+        if (idx.empty()) continue;
+        const uint32_t nb = (uint32_t)idx.size();
+        std::vector<uint64_t> in_off(nb), in_len(nb), out_off(nb), out_cap(nb), used;
+        for (uint32_t q = 0; q < nb; q++) {
+            const lfx_member &m = chain[idx[q]].m;
+            in_off[q] = m.in_off; in_len[q] = m.in_len; out_off[q] = m.out_off; out_cap[q] = m.out_len;
+        }
+        std::vector<InflateResult> res;
+        {
+            PhaseMute mute(c);
+            if ((rc = decode_batch(c, LFX_GZIP, nb, d_in, in_off.data(), in_len.data(), d_out, out_off.data(), out_cap.data(), res,
+                                   &used)))
+                return rc;
+        }
+        for (uint32_t q = 0; q < nb; q++)
+            if (res[q].status != 0 || used[q] != in_len[q] || res[q].out_len != out_cap[q]) {
+                keep = idx[q];
+                tail_base = in_off[q];
+                tail_out = out_off[q];
+                break;
+            }
+    }
+    c->phase("batch");
+    // ---- 6. the sequential member loop from there on: the exact verdict, partial output and clean end
+    members.clear();
+    for (size_t e = 0; e < keep; e++) members.push_back(chain[e].m);
+    {
+        PhaseMute mute(c);
+        if ((rc = decode_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, d_out, cap, oc, tail_base, tail_out, false, &members))) return rc;
+    }
+    c->phase("tail");
+    return LFX_OK;
+}
+}  // namespace
+
+extern "C" int lfx_decode_members_device(lfx_ctx *cc, const void *d_in, uint64_t n, void *d_out, uint64_t cap,
+                                         uint64_t *out_len, uint64_t *consumed, lfx_member *members, uint32_t max_members,
+                                         uint32_t *n_members) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    DecodeOutcome oc;
+    std::vector<lfx_member> got;
+    int rc = decode_members(c, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, oc, got);
+    if (rc) return rc;
+    if (oc.out_len > cap) oc.out_len = cap;  // (as lfx_decode_device)
+    if (out_len) *out_len = oc.out_len;
+    if (consumed) *consumed = oc.consumed;
+    if (n_members) *n_members = (uint32_t)std::min<size_t>(got.size(), 0xFFFFFFFFu);
+    if (members) memcpy(members, got.data(), sizeof(lfx_member) * std::min<size_t>(got.size(), max_members));
+    if (oc.status != LFX_OK) c->set_error(oc.msg);
+    return oc.status;
+} LFX_ABI_CATCH
+
+extern "C" int lfx_decode_members_host(lfx_ctx *cc, const void *in, uint64_t n, void *out, uint64_t cap, uint64_t *out_len,
+                                       uint64_t *consumed, lfx_member *members, uint32_t max_members, uint32_t *n_members) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
+    if ((rc = c->d_io_out.reserve(std::max<uint64_t>(cap, 4)))) return rc;
+    if (int hr = host_to_device(c, c->d_io_in.p, in, n, c->stream)) { c->set_error("host to device copy failed"); return hr; }
+    uint64_t ol = 0;
+    rc = lfx_decode_members_device(cc, c->d_io_in.p, n, c->d_io_out.p, cap, &ol, consumed, members, max_members, n_members);
+    if (rc == LFX_E_DEVICE || rc == LFX_E_OOM || rc == LFX_E_ARG) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (ol) { if (int hr = device_to_host(c, out, c->d_io_out.p, ol, c->stream)) { c->set_error("device to host copy failed"); return hr; } }
+    if (out_len) *out_len = ol;
+    return rc;
 } LFX_ABI_CATCH
 
 // ------------------------------------------------------------------------------------------------

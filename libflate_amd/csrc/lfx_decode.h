@@ -207,6 +207,14 @@ int launch_find_stage2(hipStream_t st, const uint8_t *in, uint64_t nbytes, const
                        uint32_t *final_count, uint64_t *final_list, uint32_t final_cap, uint32_t n_cu,
                        uint64_t *dbg = nullptr /* device, zero: seven counters (LFX_DEBUG) */,
                        int exp = 0 /* timing experiments: a cut-down kernel that finds nothing (LFX_FIND2_EXP) */);
+// multi-member decode (lfx_members.hip): gzip member candidates (1f 8b 08, reserved FLG bits clear) per tile of MEMBER_TILE
+// input bytes — counted, then written in input order to the positions the host gives each tile (MEMBER_SKIP: none)
+constexpr uint64_t MEMBER_TILE = 16384;
+constexpr uint64_t MEMBER_SKIP = ~0ull;
+inline uint64_t member_tiles(uint64_t n) { return (n + MEMBER_TILE - 1) / MEMBER_TILE; }
+int launch_member_count(hipStream_t st, const uint8_t *in, uint64_t n, uint32_t *tile_count /* member_tiles(n) */);
+int launch_member_emit(hipStream_t st, const uint8_t *in, uint64_t n, const uint64_t *tile_pos /* member_tiles(n) */,
+                       uint64_t *out, uint64_t cap);
 int launch_verify_trailers(hipStream_t st, int format, uint32_t count, const uint8_t *in,
                            const DecStream *streams, const DecHeader *hdrs, InflateResult *results,
                            const uint32_t *crc, const uint32_t *adler, uint64_t *consumed);

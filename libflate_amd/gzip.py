@@ -4,6 +4,7 @@ import struct
 from . import _ffi
 from . import deflate as _deflate
 from ._stream import StreamError, _DecoderBase, _EncoderBase  # noqa: F401
+from .context import default_context
 
 
 class ExtraSubField:  # gzip.rs:507-541
@@ -122,3 +123,14 @@ class MultiDecoder(_DecoderBase):
     @classmethod
     def new(cls, inner, context=None):
         return cls(inner, context)
+
+
+def decode_members(data, context=None):
+    """What MultiDecoder reads from `data` (concatenated members: BGZF, `cat a.gz b.gz`), the members decoded on the GPU as
+    one batch (lfx_decode_members_host) → (bytes, [(in_off, in_len, out_off, out_len)] per member).  Raises StreamError
+    where MultiDecoder's read_to_end would fail."""
+    ctx = context if context is not None else default_context()
+    rc, out, _used, members, msg = ctx.decode_members_host(data)
+    if rc != _ffi.OK:
+        raise StreamError(rc, msg)
+    return out, members
