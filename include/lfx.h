@@ -156,6 +156,68 @@ int lfx_decode_members_host(lfx_ctx *c, const void *in, uint64_t n, void *out, u
                             uint64_t *out_len, uint64_t *consumed,
                             lfx_member *members, uint32_t max_members, uint32_t *n_members);
 
+/* ---- seek index: random-access reads of a DEFLATE / zlib / gzip stream ---------------------------------
+ * One decode builds the index: a list of access points (a bit of the input where decoding can start, the output byte it
+ * produces first, the 32 KiB of output in front of it).  A read of output bytes [off, off + len) decodes only from the access
+ * point in front of off.  An index belongs to the context it was made on (like lfx_encoder / lfx_decoder); its windows live
+ * in that context's device memory.
+ * Candidates for access points: every block start, and the proved lane starts of the decode's block scan inside dynamic
+ * and fixed blocks that produce more than `spacing` bytes — of those, the first in each spacing / 16 bytes of output (stored
+ * blocks: block starts only).  Every member starts with a
+ * point at its first block header (win_len 0); inside a member the next point is the last candidate whose out_off is at
+ * most the previous point's out_off + spacing, or the first candidate after that when there is none.  max_gap = the
+ * largest distance from a point to the next point or to its member's end.  A member decoded by the serial kernel (streams
+ * under 4 KiB, anomalies) keeps only its start point.
+ * Integrity: the checksums (CRC-32 / Adler-32) are verified when the index is built, NOT when it is read.  A read checks
+ * each point's in_crc against the input bytes it holds, and a segment decoded up to the next point must end exactly at
+ * that point's in_bit and out_off (a member's last segment: at its BFINAL block's EndOfBlock); anything else is
+ * LFX_E_INVALID_DATA for that read, and the message names the point.
+ * Serialised form (little-endian): a 64-byte header — "LFXINDEX", u32 version = 1, u32 format, u32 flags, u32 n_points,
+ * u64 in_len (the decode's consumed), u64 out_len, u64 spacing, u64 max_gap, u32 n_members, u32 0 — then n_points
+ * 40-byte lfx_index_point records, then the windows concatenated in point order (win_len bytes each), then a u32 CRC-32
+ * of every byte in front of it.  Export is deterministic. */
+typedef struct lfx_index lfx_index;
+typedef struct lfx_index_point {
+    uint64_t in_bit;   /* first bit decoded from this point, relative to input byte 0: a block header, or a symbol boundary
+                          inside the block whose header is at hdr_bit */
+    uint64_t hdr_bit;  /* header bit of the block holding in_bit (== in_bit at a block start) */
+    uint64_t out_off;  /* output byte that in_bit produces first, relative to the decode's whole output */
+    uint32_t member;   /* gzip member index (0 without LFX_DEC_MULTI) */
+    uint32_t win_len;  /* history kept: min(32768, out_off - out_off of the member's first point) */
+    uint32_t in_crc;   /* CRC-32 of input bytes [in_bit/8, in_bit/8 + 64), clipped to the input */
+    uint8_t btype;     /* of the block at hdr_bit; 0 (stored) only at a block start */
+    uint8_t _pad[3];
+} lfx_index_point;     /* 40 bytes */
+typedef struct lfx_index_info {
+    uint64_t in_len, out_len, spacing, max_gap, export_bytes;
+    uint32_t format, flags, n_points, n_members;
+} lfx_index_info;      /* 56 bytes */
+/* lfx_decode_device plus an index.  Status, *out_len, *consumed, lfx_ctx_last_error and d_out[0 .. *out_len) are EXACTLY
+ * those of lfx_decode_device(c, format, flags, ...) (LFX_DEC_MULTI: of lfx_decode_members_device).  On LFX_OK, *idx is a new
+ * index; on any other status, *idx = NULL.  spacing < 4096 -> LFX_E_ARG. */
+int lfx_decode_index_device(lfx_ctx *c, int format, uint32_t flags, const void *d_in, uint64_t n, void *d_out,
+                            uint64_t cap, uint64_t *out_len, uint64_t *consumed, uint64_t spacing, lfx_index **idx);
+/* `count` reads (off, len, out_off, out_len_r, status: HOST arrays).  d_in holds input bytes [in_base, in_base + n).
+ * Read i writes output bytes [off[i], off[i] + len[i]) clipped to out_len at d_out + out_off[i], and writes nothing else.
+ * out_len_r[i] = bytes written, status[i] = LFX_* per read: LFX_E_ARG if off[i] > out_len or the input the read needs
+ * (lfx_index_span) is not inside [in_base, in_base + n); a read with len 0, or one that starts at out_len, is LFX_OK and
+ * writes nothing.  The return value is LFX_OK when every read is OK, otherwise the first failing read's status. */
+int lfx_index_read_device(lfx_ctx *c, const lfx_index *idx, const void *d_in, uint64_t in_base, uint64_t n,
+                          uint32_t count, const uint64_t *off, const uint64_t *len, void *d_out,
+                          const uint64_t *out_off, uint64_t *out_len_r, int32_t *status);
+/* host only: the input bytes [*in_lo, *in_hi) that a read of [off, off + len) needs held in d_in — from the header of the block
+ * that holds the first access point it decodes from (that header is parsed again) */
+int lfx_index_span(const lfx_index *idx, uint64_t off, uint64_t len, uint64_t *in_lo, uint64_t *in_hi);
+int lfx_index_get_info(const lfx_index *idx, lfx_index_info *info);
+int lfx_index_get_point(const lfx_index *idx, uint32_t i, lfx_index_point *p);
+/* the serialised index into buf[0, cap); *len = its size (also when cap is too small: LFX_E_NOSPACE; buf may be NULL) */
+int lfx_index_export(lfx_ctx *c, const lfx_index *idx, void *buf, uint64_t cap, uint64_t *len);
+/* a serialised index (lfx_index_check first) → a new index on c; NULL with *status on failure */
+lfx_index *lfx_index_import(lfx_ctx *c, const void *buf, uint64_t len, int *status);
+/* host only: validates a serialised index (LFX_E_INVALID_DATA when it breaks the format); info may be NULL */
+int lfx_index_check(const void *buf, uint64_t len, lfx_index_info *info);
+void lfx_index_free(lfx_index *idx);
+
 /* ---- sharded encode: independent block ranges per rank, one gzip/zlib/deflate member
  * (SURVEY §8e).  prepare() runs match finding → Huffman build and the checksums and reports the
  * shard's bit length; after the ranks exchanged lfx_shard_info (RCCL all-gather), emit() packs the

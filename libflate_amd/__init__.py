@@ -7,5 +7,6 @@ CPU fallback.
 from . import _ffi  # noqa: F401
 from .context import Context, default_context  # noqa: F401
 from . import deflate, gzip, lz77, non_blocking, zlib  # noqa: F401
+from .index import Index  # noqa: F401
 
-__all__ = ["Context", "default_context", "deflate", "zlib", "gzip", "lz77", "non_blocking"]
+__all__ = ["Context", "default_context", "Index", "deflate", "zlib", "gzip", "lz77", "non_blocking"]

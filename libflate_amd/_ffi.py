@@ -32,6 +32,8 @@ EXPORTS = [
     "lfx_comm_rccl", "lfx_comm_rccl_free", "lfx_sharded_encode_begin", "lfx_sharded_encode_finish", "lfx_sharded_byte_range",
     "lfx_sharded_decode", "lfx_sharded_layout", "lfx_sharded_gather_tuples", "lfx_sharded_fold", "lfx_sharded_free",
     "lfx_host_alloc", "lfx_host_free", "lfx_ctx_match_fallbacks", "lfx_decode_members_device", "lfx_decode_members_host",
+    "lfx_decode_index_device", "lfx_index_read_device", "lfx_index_span", "lfx_index_get_info", "lfx_index_get_point",
+    "lfx_index_export", "lfx_index_import", "lfx_index_check", "lfx_index_free",
 ]
 
 
@@ -61,6 +63,19 @@ class BlkTuple(C.Structure):
 class Member(C.Structure):
     """lfx_member: one verified member of a multi-member gzip input (32 bytes)"""
     _fields_ = [("in_off", C.c_uint64), ("in_len", C.c_uint64), ("out_off", C.c_uint64), ("out_len", C.c_uint64)]
+
+
+class IndexPoint(C.Structure):
+    """lfx_index_point: one access point of a seek index (40 bytes)"""
+    _fields_ = [("in_bit", C.c_uint64), ("hdr_bit", C.c_uint64), ("out_off", C.c_uint64), ("member", C.c_uint32),
+                ("win_len", C.c_uint32), ("in_crc", C.c_uint32), ("btype", C.c_uint8), ("_pad", C.c_uint8 * 3)]
+
+
+class IndexInfo(C.Structure):
+    """lfx_index_info: what a seek index covers (56 bytes)"""
+    _fields_ = [("in_len", C.c_uint64), ("out_len", C.c_uint64), ("spacing", C.c_uint64), ("max_gap", C.c_uint64),
+                ("export_bytes", C.c_uint64), ("format", C.c_uint32), ("flags", C.c_uint32), ("n_points", C.c_uint32),
+                ("n_members", C.c_uint32)]
 
 
 class ShardInfo(C.Structure):
@@ -164,6 +179,17 @@ def lib():
                                             C.POINTER(u32)]
     L.lfx_decode_members_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,
                                           C.POINTER(u32)]
+    L.lfx_decode_index_device.argtypes = [vp, i32, u32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), u64, C.POINTER(vp)]
+    L.lfx_index_read_device.argtypes = [vp, vp, vp, u64, u64, u32, vp, vp, vp, vp, vp, vp]
+    L.lfx_index_span.argtypes = [vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.lfx_index_get_info.argtypes = [vp, C.POINTER(IndexInfo)]
+    L.lfx_index_get_point.argtypes = [vp, u32, C.POINTER(IndexPoint)]
+    L.lfx_index_export.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
+    L.lfx_index_import.argtypes = [vp, vp, u64, C.POINTER(i32)]
+    L.lfx_index_import.restype = vp
+    L.lfx_index_check.argtypes = [vp, u64, C.POINTER(IndexInfo)]
+    L.lfx_index_free.argtypes = [vp]
+    L.lfx_index_free.restype = None
     L.lfx_encode_batch_device.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lfx_encode_shard_prepare.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, u64, i32,
                                            i32, C.POINTER(ShardInfo)]

@@ -113,6 +113,27 @@ class Context:
         members, at most max_members of them (None: room for every member n bytes can hold)"""
         return self._members(_ffi.lib().lfx_decode_members_device, d_in, n, d_out, cap, max_members)
 
+    def decode_index_device(self, fmt, d_in, n, d_out, cap, spacing=1 << 20, flags=0):
+        """lfx_decode_device plus a seek index (lfx_decode_index_device) → (status, out_len, consumed, index_handle, message);
+        index_handle is a native lfx_index* (None unless status is 0) — libflate_amd.index.Index wraps it"""
+        out_len, consumed, h = C.c_uint64(0), C.c_uint64(0), C.c_void_p(None)
+        rc = _ffi.lib().lfx_decode_index_device(self._h, fmt, flags, d_in, n, d_out, cap, C.byref(out_len), C.byref(consumed),
+                                                spacing, C.byref(h))
+        if rc in (_ffi.E_DEVICE, _ffi.E_OOM, _ffi.E_ARG):
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return rc, out_len.value, consumed.value, h.value, self.last_error() if rc else ""
+
+    def index_read_device(self, index_handle, d_in, in_base, n, offs, lens, d_out, out_offs):
+        """count reads through a seek index (lfx_index_read_device) → (status, out_lens, statuses, message)"""
+        k = len(offs)
+        a = lambda v: (C.c_uint64 * max(k, 1))(*v)
+        o, ln, oo = a(offs), a(lens), a(out_offs)
+        out_len, st = (C.c_uint64 * max(k, 1))(), (C.c_int32 * max(k, 1))()
+        rc = _ffi.lib().lfx_index_read_device(self._h, index_handle, d_in, in_base, n, k, o, ln, d_out, oo, out_len, st)
+        if rc in (_ffi.E_DEVICE, _ffi.E_OOM) or (rc == _ffi.E_ARG and not any(st[i] == _ffi.E_ARG for i in range(k))):
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return rc, list(out_len[:k]), list(st[:k]), self.last_error() if rc else ""
+
     def _members(self, fn, src, n, dst, cap, max_members):
         if max_members is None:
             max_members = n // 20 + 1           # (a gzip member takes at least 20 bytes)

@@ -17,6 +17,7 @@
 #include "lfx_ctx.h"
 #include "lfx_container.h"
 #include "lfx_decode.h"
+#include "lfx_index.h"
 #include <thread>
 #include <chrono>
 
@@ -803,6 +804,10 @@ int inflate_member(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t off0, uint8
                     fl = 0;
                 }
                 if (fl == 0) {   // no back-reference reached before its block's first byte
+                    // (an index build: the chain's block starts and its large blocks' lanes, before a later step reuses the slots)
+                    if (c->idx && (rc = idx_record_chain(c, emit.data(), ne, (const BlkLanes *)c->d_dec_blocks.p, c->idx->bit_base,
+                                                         c->idx->out_base, true)))
+                        return rc;
                     mr.status = LFX_OK;
                     mr.out_len = total;
                     mr.blk_out_start = total;
@@ -903,6 +908,11 @@ int decode_stream(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint6
                 return LFX_OK;
             }
             off0 = dh.deflate_off;
+        }
+        if (c->idx) {   // (an index build: the member's first block is an access point)
+            c->idx->bit_base = base * 8;
+            c->idx->out_base = out_at;
+            c->idx->cand.push_back(IdxCand{(base + off0) * 8, (base + off0) * 8, out_at, IDX_BTYPE_READ});
         }
         MemberResult mr;
         mr.ck_mode = format == LFX_GZIP ? 1 : format == LFX_ZLIB ? 2 : 0;
@@ -1473,6 +1483,11 @@ static int batch_fast(Ctx *c, const uint8_t *d_in, uint64_t n_in, uint8_t *d_out
             HIP_TRY(hipMemcpyAsync(jf.data(), d_jf, 4ull * ne, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
+        if (c->idx && ne) {   // (an index build: the blocks this round proved)
+            std::vector<BlkEmit> ok;
+            for (uint32_t q = 0; q < ne; q++) if (!jf[q]) ok.push_back(emit[q]);
+            if ((rc = idx_record_chain(c, ok.data(), (uint32_t)ok.size(), (const BlkLanes *)c->d_dec_cand.p, 0, 0, false))) return rc;
+        }
         std::vector<Live> next;
         for (uint32_t q = 0; q < ne; q++) {
             if (jf[q]) continue;                                 // reads in front of the block: serial kernel
@@ -1532,6 +1547,10 @@ int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uin
     c->phase("headers");
     std::vector<InflateJob> jobs(count);
     for (uint32_t i = 0; i < count; i++) {
+        if (c->idx && (format == LFX_DEFLATE || hdrs[i].status == 0)) {   // (an index build: a member's first block)
+            const uint64_t b = (in_off[i] + (format == LFX_DEFLATE ? 0 : hdrs[i].deflate_off)) * 8;
+            c->idx->cand.push_back(IdxCand{b, b, out_off[i], IDX_BTYPE_READ});
+        }
         InflateJob j{};
         j.in_off = in_off[i];
         j.in_len = in_len[i];
@@ -1871,6 +1890,53 @@ extern "C" int lfx_decode_members_host(lfx_ctx *cc, const void *in, uint64_t n, 
     if (ol) { if (int hr = device_to_host(c, out, c->d_io_out.p, ol, c->stream)) { c->set_error("device to host copy failed"); return hr; } }
     if (out_len) *out_len = ol;
     return rc;
+} LFX_ABI_CATCH
+
+// ------------------------------------------------------------------------------------------------
+// seek index: the decode of lfx_decode_device (LFX_DEC_MULTI: of lfx_decode_members_device), unchanged, with
+// Ctx::idx set — its chains record their block starts and the lanes of their large blocks — then the index from those
+// candidates (lfx_index.hip)
+namespace {
+struct IdxScope {      // Ctx::idx for the length of the decode, whatever way it is left
+    Ctx *c;
+    IdxScope(Ctx *c_, IdxCollect *col) : c(c_) { c->idx = col; }
+    ~IdxScope() { c->idx = nullptr; }
+};
+}  // namespace
+
+extern "C" int lfx_decode_index_device(lfx_ctx *cc, int format, uint32_t flags, const void *d_in, uint64_t n, void *d_out,
+                                       uint64_t cap, uint64_t *out_len, uint64_t *consumed, uint64_t spacing, lfx_index **idx) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    if (idx) *idx = nullptr;
+    if (format < 0 || format > 2 || spacing < 4096 || !idx) return LFX_E_ARG;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    const bool multi = format == LFX_GZIP && (flags & LFX_DEC_MULTI);
+    IdxCollect col;
+    col.spacing = spacing;
+    DecodeOutcome oc;
+    std::vector<lfx_member> members;
+    int rc;
+    {
+        IdxScope scope(c, &col);
+        PhaseMute mute(c);
+        if (multi) rc = decode_members(c, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, oc, members);
+        else rc = decode_stream(c, format, flags, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, oc, 0, 0, false, &members);
+    }
+    if (rc) return rc;
+    c->phase("decode");
+    if (oc.out_len > cap) oc.out_len = cap;  // (as lfx_decode_device)
+    if (out_len) *out_len = oc.out_len;
+    if (consumed) *consumed = oc.consumed;
+    if (oc.status != LFX_OK) { c->set_error(oc.msg); return oc.status; }
+    if ((rc = idx_finish(c, col, format, multi ? LFX_DEC_MULTI : 0u, (const uint8_t *)d_in, oc.consumed, (const uint8_t *)d_out,
+                         oc.out_len, members, idx)))
+        return rc;
+    c->phase("done");
+    return LFX_OK;
 } LFX_ABI_CATCH
 
 // ------------------------------------------------------------------------------------------------

@@ -65,6 +65,7 @@ struct InflateResult {
 
 // ---- lane-parallel single-stream path (lfx_inflate_fast.hip)
 enum : uint32_t { BLK_OK = 0, BLK_BAD = 1, BLK_NO_EOB = 2 };
+constexpr uint32_t BLK_PIECE_KNOWN = 2;   // BlkJob::piece: a piece that starts at a known symbol boundary
 struct BlkJob {
     uint64_t start_bit;  // block header bit
     uint64_t end_bit;    // range end guess: the next candidate's start (or the end of the input)
@@ -74,6 +75,8 @@ struct BlkJob {
     // only if the boundary equals the exit of the piece before it.  A piece without EndOfBlock is "open":
     // status BLK_NO_EOB, but lanes / counts / end_bit (exit of its last lane) are valid.
     // Piece 0 starts behind the header like any job (warm_bit = 0).
+    // piece == BLK_PIECE_KNOWN: lo_bit is a KNOWN symbol boundary of the block (a seek index's access point, or where the
+    // piece in front of it ended): the job scans from exactly there, without a warm-up.
     uint64_t lo_bit, warm_bit;
     uint32_t piece, _pad;
     // the storing scan (round 6, launch_blk_scan_store): this job's lanes write their code words to temp + temp_off +

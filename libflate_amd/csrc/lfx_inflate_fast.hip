@@ -964,7 +964,7 @@ __global__ __launch_bounds__(NT, STORE ? 4 : 8) void blk_scan_kernel(const uint8
         for (uint32_t i = tid; i < sizeof(FastTabs) / 4; i += NT) dst[i] = srcw[i];
     }
     const bool piece = job.piece != 0;
-    if (piece && job.warm_bit) {
+    if (piece && job.warm_bit && job.piece != BLK_PIECE_KNOWN) {
         // warm-up: the first symbol boundary at or behind lo_bit (one lane; ~500 symbols)
         if (tid == 0) {
             uint32_t wn = 0, wcc = 0, wco = 0;
@@ -978,7 +978,10 @@ __global__ __launch_bounds__(NT, STORE ? 4 : 8) void blk_scan_kernel(const uint8
         bi.data_bit = hdr64[0];
         if (hdr[2]) { bi.status = BLK_BAD; if (tid == 0) infos[blockIdx.x] = bi; return; }
     }
-    const uint64_t d0 = hdr64[0];
+    // a piece from a known symbol boundary (the seek index's segments): no warm-up, it starts exactly at lo_bit
+    const bool known = piece && job.piece == BLK_PIECE_KNOWN;
+    if (known) bi.data_bit = job.lo_bit;
+    const uint64_t d0 = known ? job.lo_bit : hdr64[0];
     uint64_t e = job.end_bit;
     if (e > nbytes * 8) e = nbytes * 8;
     if (e < d0 + 1) e = d0 + 1;
