@@ -197,6 +197,16 @@ typedef struct lfx_index_info {
  * index; on any other status, *idx = NULL.  spacing < 4096 -> LFX_E_ARG. */
 int lfx_decode_index_device(lfx_ctx *c, int format, uint32_t flags, const void *d_in, uint64_t n, void *d_out,
                             uint64_t cap, uint64_t *out_len, uint64_t *consumed, uint64_t spacing, lfx_index **idx);
+/* lfx_encode_device plus a seek index of the stream it writes.  Status, *out_len, lfx_ctx_last_error and
+ * d_out[0 .. *out_len) are EXACTLY those of lfx_encode_device(c, format, o, s, d_in, n, d_out, cap, out_len).  On LFX_OK, *idx is
+ * a new index (format = format, flags = 0, n_members = 1, in_len = *out_len, out_len = n); on any other status *idx = NULL.
+ * Candidates: every block start, and inside dynamic and fixed blocks that produce more than `spacing` bytes the first code
+ * boundary in each spacing / 16 bytes of output; the selection is lfx_decode_index_device's.  Where no compressed block
+ * produces more than `spacing` bytes, the index equals the one lfx_decode_index_device builds from the encoded stream.
+ * spacing < 4096 -> LFX_E_ARG.  A NULL context -> LFX_E_DEVICE, nothing written. */
+int lfx_encode_index_device(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_schedule *s,
+                            const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len,
+                            uint64_t spacing, lfx_index **idx);
 /* `count` reads (off, len, out_off, out_len_r, status: HOST arrays).  d_in holds input bytes [in_base, in_base + n).
  * Read i writes output bytes [off[i], off[i] + len[i]) clipped to out_len at d_out + out_off[i], and writes nothing else.
  * out_len_r[i] = bytes written, status[i] = LFX_* per read: LFX_E_ARG if off[i] > out_len or the input the read needs

@@ -33,7 +33,7 @@ EXPORTS = [
     "lfx_sharded_decode", "lfx_sharded_layout", "lfx_sharded_gather_tuples", "lfx_sharded_fold", "lfx_sharded_free",
     "lfx_host_alloc", "lfx_host_free", "lfx_ctx_match_fallbacks", "lfx_decode_members_device", "lfx_decode_members_host",
     "lfx_decode_index_device", "lfx_index_read_device", "lfx_index_span", "lfx_index_get_info", "lfx_index_get_point",
-    "lfx_index_export", "lfx_index_import", "lfx_index_check", "lfx_index_free",
+    "lfx_index_export", "lfx_index_import", "lfx_index_check", "lfx_index_free", "lfx_encode_index_device",
 ]
 
 
@@ -180,6 +180,8 @@ def lib():
     L.lfx_decode_members_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,
                                           C.POINTER(u32)]
     L.lfx_decode_index_device.argtypes = [vp, i32, u32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), u64, C.POINTER(vp)]
+    L.lfx_encode_index_device.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, u64, vp, u64, C.POINTER(u64), u64,
+                                          C.POINTER(vp)]
     L.lfx_index_read_device.argtypes = [vp, vp, vp, u64, u64, u32, vp, vp, vp, vp, vp, vp]
     L.lfx_index_span.argtypes = [vp, u64, u64, C.POINTER(u64), C.POINTER(u64)]
     L.lfx_index_get_info.argtypes = [vp, C.POINTER(IndexInfo)]

@@ -98,6 +98,17 @@ class Context:
             raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
         return out_len.value
 
+    def encode_index_device(self, fmt, d_in, n, d_out, cap, opts=None, schedule=None, spacing=1 << 20):
+        """lfx_encode_device plus a seek index of the stream it writes (lfx_encode_index_device) → (out_len, index_handle);
+        index_handle is a native lfx_index* — libflate_amd.index.Index wraps it.  Raises as encode_device does."""
+        out_len, h = C.c_uint64(0), C.c_void_p(None)
+        rc = _ffi.lib().lfx_encode_index_device(self._h, fmt, C.byref(opts) if opts is not None else None,
+                                                C.byref(schedule) if schedule is not None else None,
+                                                d_in, n, d_out, cap, C.byref(out_len), spacing, C.byref(h))
+        if rc:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return out_len.value, h.value
+
     def decode_device(self, fmt, d_in, n, d_out, cap, flags=0):
         """→ (status, out_len, consumed, message)"""
         out_len, consumed = C.c_uint64(0), C.c_uint64(0)

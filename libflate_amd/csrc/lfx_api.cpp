@@ -17,6 +17,7 @@
 #include "lfx_ctx.h"
 #include "lfx_device.h"
 #include "lfx_huff.h"
+#include "lfx_index.h"
 #include "lfx_plan.h"
 #include "lfx_abi_guard.h"
 
@@ -797,6 +798,8 @@ extern "C" int lfx_encode_device(lfx_ctx *cc, int format, const lfx_encode_opts 
     c->prezero_ptr = nullptr;
     if (rc) return rc;
     if (out_len) *out_len = res.out_bytes;
+    // (an index build, lfx_encode_index_device: the candidates of the stream the last emit wrote, while its buffers hold it)
+    if (c->idx_enc) return idx_encode_cand(c, plan);
     return LFX_OK;
 } LFX_ABI_CATCH
 

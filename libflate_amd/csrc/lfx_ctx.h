@@ -93,12 +93,14 @@ struct Ctx {
         d_dec_temp, d_dec_lanesx;     // round 6: the storing scan's per-lane code regions and BlkLanesX records
     // seek index (lfx_index.hip): copy tasks, probe results, the read path's staging areas
     DevBuf d_idx_tasks, d_idx_probe, d_idx_stage;
+    DevBuf d_idx_enc;                   // lfx_encode_index_device: the candidate kernels' slots and per-tile sums (lfx_index_enc.hip)
     struct IdxCollect *idx = nullptr;   // while lfx_decode_index_device runs: what the decode records for the index
+    struct IdxCollect *idx_enc = nullptr;   // while lfx_encode_index_device runs: the encode leaves its candidates there
     std::vector<DevBuf *> all_bufs() {
         return {&d_chunks, &d_blocks, &d_segs, &d_pwgs, &d_cd, &d_md, &d_codes, &d_ncodes, &d_hist, &d_bc, &d_block_start,
                 &d_tile_bits, &d_tile_start, &d_ck, &d_res, &d_small, &d_hdr, &d_io_in, &d_io_out, &d_vis, &d_segtmp, &d_stage, &d_chunkmap, &d_glnk, &d_ucount,
                 &d_dec_streams, &d_dec_state, &d_dec_tmp, &d_dec_cand, &d_dec_blocks, &d_dec_tabs, &d_dec_sym, &d_dec_win, &d_dec_maps,
-                &d_dec_temp, &d_dec_lanesx, &d_idx_tasks, &d_idx_probe, &d_idx_stage};
+                &d_dec_temp, &d_dec_lanesx, &d_idx_tasks, &d_idx_probe, &d_idx_stage, &d_idx_enc};
     }
     void *h_res = nullptr;  // pinned, 4 KiB (+ the arena below)
     // Small transfers of the decode paths (job lists up, scan results and counters down) go through page-locked memory: a

@@ -570,29 +570,7 @@ __global__ __launch_bounds__(256) void frame_batch_kernel(int format, const Batc
 }
 
 // ------------------------------------------------------------------------------------------------
-// pack: bits of one code word
-__device__ __forceinline__ uint32_t code_bits(uint32_t v, const uint32_t *lit, const uint32_t *dst,
-                                              uint64_t &bits) {
-    const uint32_t dist = v & 0xFFFFu, val = v >> 16;
-    if (dist == 0) {
-        const uint32_t e = lit[val];
-        bits = e & 0xFFFFu;
-        return e >> 16;
-    }
-    uint32_t eb, ex, db, dx;
-    const uint32_t le = lit[len_symbol(val, eb, ex)];
-    const uint32_t de = dst[dist_symbol(dist, db, dx)];
-    uint32_t n = le >> 16;
-    uint64_t acc = le & 0xFFFFu;
-    acc |= (uint64_t)ex << n;
-    n += eb;
-    acc |= (uint64_t)(de & 0xFFFFu) << n;
-    n += de >> 16;
-    acc |= (uint64_t)dx << n;
-    n += db;
-    bits = acc;
-    return n;
-}
+// pack: bits of one code word — code_bits (lfx_huff.h)
 
 constexpr int PACK_THREADS = 256;
 constexpr int PACK_PER_THREAD = PACK_TILE / PACK_THREADS;  // 8

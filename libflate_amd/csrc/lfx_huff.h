@@ -38,6 +38,31 @@ LFX_HD inline uint32_t dist_symbol(uint32_t distance, uint32_t &ebits, uint32_t 
     extra = x & ((1u << e) - 1);
     return 2 * e + 2 + ((x >> e) & 1);
 }
+#ifdef __HIPCC__
+// a code word ((val << 16) | dist) → its bit count; `bits` = its bits, LSB first (lit / dst: BlockCodes::lit / dist)
+__device__ __forceinline__ uint32_t code_bits(uint32_t v, const uint32_t *lit, const uint32_t *dst,
+                                              uint64_t &bits) {
+    const uint32_t dist = v & 0xFFFFu, val = v >> 16;
+    if (dist == 0) {
+        const uint32_t e = lit[val];
+        bits = e & 0xFFFFu;
+        return e >> 16;
+    }
+    uint32_t eb, ex, db, dx;
+    const uint32_t le = lit[len_symbol(val, eb, ex)];
+    const uint32_t de = dst[dist_symbol(dist, db, dx)];
+    uint32_t n = le >> 16;
+    uint64_t acc = le & 0xFFFFu;
+    acc |= (uint64_t)ex << n;
+    n += eb;
+    acc |= (uint64_t)(de & 0xFFFFu) << n;
+    n += de >> 16;
+    acc |= (uint64_t)dx << n;
+    n += db;
+    bits = acc;
+    return n;
+}
+#endif
 LFX_HD inline uint32_t len_extra_bits_of_symbol(uint32_t sym) {  // sym 257..285
     return (sym < 265 || sym == 285) ? 0 : (sym - 261) >> 2;
 }

@@ -14,6 +14,7 @@
 namespace lfx {
 
 struct Ctx;
+struct Plan;
 
 constexpr uint32_t IDX_CRC_BYTES = 64;          // lfx_index_point::in_crc covers so many input bytes from in_bit / 8
 constexpr uint32_t IDX_WINDOW = 32768;
@@ -30,6 +31,7 @@ constexpr uint32_t IDX_BTYPE_READ = 0xFF;
 // blocks larger than `spacing`, gathered on the device before the next chain reuses their slots.
 struct IdxCollect {
     uint64_t spacing = 0;
+    bool in_order = false;                   // cand is sorted by in_bit, without repeats (lfx_encode_index_device): no sort
     uint64_t bit_base = 0, out_base = 0;     // where the current inflate_member call's d_in / d_out start (decode_stream sets them)
     std::vector<IdxCand> cand;
     struct Grab {
@@ -59,6 +61,10 @@ int launch_idx_probe(hipStream_t st, const uint8_t *in, uint64_t n, const uint64
 // the copies (src, dst, len) of any length, split into IDX_COPY_CHUNK tasks, through ONE launch (scratch: Ctx::d_idx_tasks);
 // `tasks` is the upload's source: it must live until the stream has passed the copy
 int idx_copy(Ctx *c, const std::vector<IdxCopy> &copies, std::vector<IdxCopy> &tasks);
+
+// lfx_encode_index_device (lfx_index_enc.hip): the candidates of the stream the last encode_emit wrote with `plan` — every block
+// start, and in blocks larger than Ctx::idx_enc->spacing the first code start of each grain — into Ctx::idx_enc->cand
+int idx_encode_cand(Ctx *c, const Plan &plan);
 
 uint32_t idx_crc32(const void *p, uint64_t n, uint32_t crc = 0);
 // Builds the index from the candidates and the member table of a finished decode (d_in / d_out as the decode saw them)

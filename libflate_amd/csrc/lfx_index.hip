@@ -308,7 +308,9 @@ int idx_finish(Ctx *c, IdxCollect &col, int format, uint32_t flags, const uint8_
             }
         }
     }
-    std::sort(col.cand.begin(), col.cand.end(), [](const IdxCand &a, const IdxCand &b) { return a.in_bit < b.in_bit; });
+    // (candidates that arrive in stream order — the encode-built ones — skip the sort: 1.6 ms of host time for 65536 of them)
+    if (!col.in_order)
+        std::sort(col.cand.begin(), col.cand.end(), [](const IdxCand &a, const IdxCand &b) { return a.in_bit < b.in_bit; });
     col.cand.erase(std::unique(col.cand.begin(), col.cand.end(), [](const IdxCand &a, const IdxCand &b) { return a.in_bit == b.in_bit; }),
                    col.cand.end());
     // ---- greedy selection per member

@@ -2,10 +2,12 @@
 DESIGN.md §12).
 
     decoded, idx = Index.build(data, format="gzip", spacing=1 << 20)     # one decode builds the index
+    encoded, idx = Index.encode(data, format="gzip", spacing=1 << 20)    # or the encode that writes the stream (§13)
     piece = idx.read(data, offset, length)                              # decodes from the access point in front of offset
     blob = idx.to_bytes(); idx2 = Index.from_bytes(blob)                # persistence
 
-`data` is bytes or a CUDA uint8 tensor holding the whole compressed input; reads return CUDA uint8 tensors.
+`data` is bytes or a CUDA uint8 tensor holding the whole compressed input (for encode(): the bytes to compress); reads return
+CUDA uint8 tensors.
 """
 import ctypes as C
 
@@ -72,6 +74,24 @@ class Index:
             if rc != _ffi.OK:
                 raise StreamError(rc, msg)
             return out[:ol], cls(h, ctx)
+
+    @classmethod
+    def encode(cls, data, format="gzip", spacing=1 << 20, options=None, schedule=None, ctx=None):
+        """Compress `data` and index the stream written (lfx_encode_index_device) → (encoded CUDA uint8 tensor, Index).
+        options: an lfx_encode_opts or a {deflate,zlib,gzip}.EncodeOptions; schedule: an lfx_schedule (None: one write_all).
+        The encoded bytes are exactly lfx_encode_device's.  Raises LfxError where the encode fails."""
+        import torch
+        ctx = ctx if ctx is not None else default_context()
+        fmt = _FORMATS[format] if isinstance(format, str) else int(format)
+        opts = options._to_c() if hasattr(options, "_to_c") else options
+        src = _device_bytes(data, ctx.device)
+        n = src.numel()
+        cap = _ffi.lib().lfx_encode_bound(n, C.byref(opts) if opts is not None else None,
+                                          C.byref(schedule) if schedule is not None else None)
+        cap = (max(cap, 64) + 3) & ~3       # (0 for options outside the domain: the encode itself reports them)
+        out = torch.empty(cap, dtype=torch.uint8, device=src.device)
+        ol, h = ctx.encode_index_device(fmt, src.data_ptr(), n, out.data_ptr(), cap, opts, schedule, spacing)
+        return out[:ol], cls(h, ctx)
 
     def to_bytes(self):
         L = _ffi.lib()
