@@ -156,6 +156,39 @@ int lfx_decode_members_host(lfx_ctx *c, const void *in, uint64_t n, void *out, u
                             uint64_t *out_len, uint64_t *consumed,
                             lfx_member *members, uint32_t max_members, uint32_t *n_members);
 
+/* The other direction: d_in[0, n) as gzip members that lie back to back in d_out[0, *out_len) — what lfx_decode_members_device
+ * decodes as one batch, and what zcat, Python's gzip and (with LFX_MEMBERS_BGZF) bgzip / htslib read.  The
+ * input is cut into ceil(n / member_size) slices of member_size bytes (the last may be shorter; n == 0: one slice of no bytes);
+ * member i is byte for byte what lfx_encode_device(c, LFX_GZIP, o, s, slice i, ...) writes, the schedule applied to each slice
+ * alone.  All members are encoded in one launch set and packed at their final offsets: no padding, any byte offset.
+ * LFX_MEMBERS_BGZF: 1 <= member_size <= 65505; o must hold no extra, filename or comment and hcrc = 0, s must be
+ * LFX_SCHED_SINGLE (LFX_E_ARG, the message names the field; also block_size <= member_size with member_size > 65500, where the
+ * stored form below would not fit).  Every member is encoded with extra = 42 43 02 00 lo hi, (lo, hi) = its total length - 1; a
+ * member whose total length would exceed 65536 bytes is written as the same call writes it with no_compression = 1 (decided on
+ * the device before anything of it is written); behind the last member lie the 28 bytes of BGZF's end-of-file marker.  n == 0:
+ * the marker alone, no member.
+ * members[i] = {in_off, in_len: slice i in d_in; out_off, out_len: member i in d_out} (the marker is no member); *n_members =
+ * their count, also when that exceeds max_members (only the first max_members records are written); members may be NULL.
+ * d_out must be 4-byte aligned.  d_out[0, min(cap, lfx_encode_members_bound(...))) is zero-filled first; nothing behind
+ * *out_len is written after that, and nothing behind cap at all.  cap below the bound is no error in itself: LFX_E_NOSPACE only
+ * when the members do not fit, with *out_len = 0 and no member written.  member_size == 0: LFX_E_ARG.  A NULL context:
+ * LFX_E_DEVICE, nothing written.
+ * lfx_encode_members_bound: the sum of lfx_encode_bound over the slices; BGZF: every term capped at 65536, plus 28.  0 for
+ * arguments the encode call would refuse. */
+enum { LFX_MEMBERS_BGZF = 1u };
+uint64_t lfx_encode_members_bound(uint64_t n, uint64_t member_size, uint32_t flags, const lfx_encode_opts *o, const lfx_schedule *s);
+int lfx_encode_members_device(lfx_ctx *c, const lfx_encode_opts *o, const lfx_schedule *s, uint64_t member_size, uint32_t flags,
+                              const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len,
+                              lfx_member *members, uint32_t max_members, uint32_t *n_members);
+/* same, host buffers (staged like lfx_encode_host) */
+int lfx_encode_members_host(lfx_ctx *c, const lfx_encode_opts *o, const lfx_schedule *s, uint64_t member_size, uint32_t flags,
+                            const void *in, uint64_t n, void *out, uint64_t cap, uint64_t *out_len,
+                            lfx_member *members, uint32_t max_members, uint32_t *n_members);
+/* host only: bgzip's .gzi index from the member table of lfx_encode_members_* (out_off = compressed, in_off = uncompressed):
+ * u64 LE count = n_members - 1 (0 for no member), then for members 1 .. count a pair of u64 LE (compressed offset, uncompressed
+ * offset); member 0 is implicit.  *len = its size (also when cap is too small: LFX_E_NOSPACE; buf may then be NULL). */
+int lfx_members_gzi(const lfx_member *members, uint32_t n_members, void *buf, uint64_t cap, uint64_t *len);
+
 /* ---- seek index: random-access reads of a DEFLATE / zlib / gzip stream ---------------------------------
  * One decode builds the index: a list of access points (a bit of the input where decoding can start, the output byte it
  * produces first, the 32 KiB of output in front of it).  A read of output bytes [off, off + len) decodes only from the access

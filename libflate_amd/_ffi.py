@@ -17,6 +17,8 @@ SCHED_SINGLE, SCHED_FIXED, SCHED_LIST = 0, 1, 2
 SCHED_FLUSH = (1 << 64) - 1
 DEC_MULTI = 1
 DEC_NONBLOCKING = 2
+MEMBERS_BGZF = 1
+BGZF_MEMBER_SIZE = 65280      # bgzip's own slice; 65505 is the most a BGZF member holds
 
 # every symbol include/lfx.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -34,6 +36,7 @@ EXPORTS = [
     "lfx_host_alloc", "lfx_host_free", "lfx_ctx_match_fallbacks", "lfx_decode_members_device", "lfx_decode_members_host",
     "lfx_decode_index_device", "lfx_index_read_device", "lfx_index_span", "lfx_index_get_info", "lfx_index_get_point",
     "lfx_index_export", "lfx_index_import", "lfx_index_check", "lfx_index_free", "lfx_encode_index_device",
+    "lfx_encode_members_bound", "lfx_encode_members_device", "lfx_encode_members_host", "lfx_members_gzi",
 ]
 
 
@@ -179,6 +182,12 @@ def lib():
                                             C.POINTER(u32)]
     L.lfx_decode_members_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,
                                           C.POINTER(u32)]
+    L.lfx_encode_members_bound.restype = u64
+    L.lfx_encode_members_bound.argtypes = [u64, u64, u32, C.POINTER(EncodeOpts), C.POINTER(Schedule)]
+    for f in (L.lfx_encode_members_device, L.lfx_encode_members_host):
+        f.argtypes = [vp, C.POINTER(EncodeOpts), C.POINTER(Schedule), u64, u32, vp, u64, vp, u64, C.POINTER(u64),
+                      C.POINTER(Member), u32, C.POINTER(u32)]
+    L.lfx_members_gzi.argtypes = [C.POINTER(Member), u32, vp, u64, C.POINTER(u64)]
     L.lfx_decode_index_device.argtypes = [vp, i32, u32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), u64, C.POINTER(vp)]
     L.lfx_encode_index_device.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, u64, vp, u64, C.POINTER(u64), u64,
                                           C.POINTER(vp)]
@@ -291,6 +300,22 @@ def make_opts(**kw):
             setattr(o, k, v)
     o._keep = keep
     return o
+
+
+def members_to_gzi(members):
+    """bgzip's .gzi index from the member table of an encode_members call, [(in_off, in_len, out_off, out_len)]: u64 LE count,
+    then (compressed offset, uncompressed offset) of members 1 .. count (lfx_members_gzi)"""
+    members = list(members)
+    table = (Member * max(len(members), 1))()
+    for i, m in enumerate(members):
+        table[i].in_off, table[i].in_len, table[i].out_off, table[i].out_len = m
+    need = C.c_uint64(0)
+    lib().lfx_members_gzi(table, len(members), None, 0, C.byref(need))
+    buf = C.create_string_buffer(need.value)
+    rc = lib().lfx_members_gzi(table, len(members), buf, need.value, C.byref(need))
+    if rc:
+        raise LfxError(rc, "lfx_members_gzi")
+    return buf.raw[:need.value]
 
 
 def make_schedule(write_size=0, writes=None):

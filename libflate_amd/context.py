@@ -170,6 +170,37 @@ class Context:
                 continue
             return rc, out.raw[:ol], used, members, msg
 
+    def _encode_members(self, fn, src, n, dst, cap, member_size, flags, opts, schedule, max_members):
+        count = 0 if (flags & _ffi.MEMBERS_BGZF and n == 0) else max(1, -(-n // member_size)) if member_size else 0
+        if max_members is None:
+            max_members = count
+        table = (_ffi.Member * max(int(max_members), 1))()
+        out_len, got = C.c_uint64(0), C.c_uint32(0)
+        rc = fn(self._h, C.byref(opts) if opts is not None else None, C.byref(schedule) if schedule is not None else None,
+                member_size, flags, src, n, dst, cap, C.byref(out_len), table, int(max_members), C.byref(got))
+        if rc in (_ffi.E_DEVICE, _ffi.E_OOM, _ffi.E_ARG, _ffi.E_UNSUPPORTED):
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        members = [(m.in_off, m.in_len, m.out_off, m.out_len) for m in table[:min(got.value, int(max_members))]]
+        return rc, out_len.value, got.value, members, self.last_error() if rc else ""
+
+    def encode_members_device(self, d_in, n, d_out, cap, member_size=1 << 20, flags=0, opts=None, schedule=None, max_members=None):
+        """device bytes as gzip members lying back to back, all encoded in one launch set (lfx_encode_members_device;
+        flags = _ffi.MEMBERS_BGZF: BGZF) → (status, out_len, n_members, members, message); members = [(in_off, in_len, out_off,
+        out_len)]: the slice in d_in, the member in d_out — at most max_members of them (None: all)"""
+        return self._encode_members(_ffi.lib().lfx_encode_members_device, d_in, n, d_out, cap, member_size, flags, opts, schedule,
+                                    max_members)
+
+    def encode_members_host(self, data, member_size=1 << 20, flags=0, opts=None, schedule=None, cap=None, max_members=None):
+        """the same on host bytes (lfx_encode_members_host) → (status, output, n_members, members, message); cap = None: the bound"""
+        data = bytes(data)
+        if cap is None:
+            cap = _ffi.lib().lfx_encode_members_bound(len(data), member_size, flags, C.byref(opts) if opts is not None else None,
+                                                      C.byref(schedule) if schedule is not None else None)
+        out = C.create_string_buffer(max(cap, 1))
+        rc, ol, count, members, msg = self._encode_members(_ffi.lib().lfx_encode_members_host, data, len(data), out, cap, member_size,
+                                                           flags, opts, schedule, max_members)
+        return rc, out.raw[:ol], count, members, msg
+
     def encode_host(self, fmt, data, opts=None, schedule=None):
         data = bytes(data)
         bound = _ffi.lib().lfx_encode_bound(len(data), C.byref(opts) if opts is not None else None,

@@ -934,6 +934,233 @@ extern "C" int lfx_encode_host(lfx_ctx *cc, int format, const lfx_encode_opts *o
     return LFX_OK;
 } LFX_ABI_CATCH
 
+// ---- members encode: one buffer as back-to-back gzip members / BGZF, packed at their final offsets ----------
+static const uint8_t BGZF_EXTRA[6] = {0x42, 0x43, 0x02, 0x00, 0x00, 0x00};   // 'B' 'C', SLEN 2, BSIZE (per member, on the device)
+static const uint32_t BGZF_MAX_MEMBER = 65536, BGZF_EOF_LEN = 28;
+static const uint64_t BGZF_MAX_SLICE = 65505;                               // 18 + 5 + 65505 + 8 = 65536: one stored block still fits
+// the options and the schedule of a members call: *why names the field that is out of its domain
+static int members_check(uint64_t member_size, uint32_t flags, const lfx_encode_opts *o, const lfx_schedule *s, lfx_encode_opts *d,
+                         const char **why) {
+    *d = norm_opts(o);
+    if (flags & ~(uint32_t)LFX_MEMBERS_BGZF) { *why = "flags: unknown bit"; return LFX_E_ARG; }
+    if (member_size == 0) { *why = "member_size: must not be 0"; return LFX_E_ARG; }
+    if (check_opts(*d)) { *why = "block_size / max_length: outside the reference's domain"; return LFX_E_ARG; }
+    if (!(flags & LFX_MEMBERS_BGZF)) return LFX_OK;
+    if (member_size > BGZF_MAX_SLICE) { *why = "member_size: a BGZF member holds at most 65505 bytes"; return LFX_E_ARG; }
+    if (d->extra) { *why = "extra: BGZF carries its own BC subfield"; return LFX_E_ARG; }
+    if (d->filename) { *why = "filename: a BGZF header is 18 bytes"; return LFX_E_ARG; }
+    if (d->comment) { *why = "comment: a BGZF header is 18 bytes"; return LFX_E_ARG; }
+    if (d->hcrc) { *why = "hcrc: a BGZF header is 18 bytes"; return LFX_E_ARG; }
+    if (s && s->kind != LFX_SCHED_SINGLE) { *why = "schedule: BGZF needs LFX_SCHED_SINGLE"; return LFX_E_ARG; }
+    // block_size <= member_size closes the member with an empty second block: the stored form is then 36 + member_size bytes
+    if (d->block_size <= member_size && member_size + 36 > BGZF_MAX_MEMBER) {
+        *why = "block_size: with block_size <= member_size a BGZF member holds at most 65500 bytes";
+        return LFX_E_ARG;
+    }
+    d->extra = BGZF_EXTRA;
+    d->extra_len = sizeof BGZF_EXTRA;
+    return LFX_OK;
+}
+// slices of a members call: `full` of member_size bytes, then one of `last` bytes when have_last
+struct MemberSlices { uint64_t full, last; bool have_last; uint64_t count() const { return full + (have_last ? 1 : 0); } };
+static MemberSlices member_slices(uint64_t n, uint64_t member_size, uint32_t flags) {
+    MemberSlices m{n / member_size, n % member_size, n % member_size != 0};
+    if (n == 0 && !(flags & LFX_MEMBERS_BGZF)) m.have_last = true;     // one member of no bytes (BGZF: the marker alone)
+    return m;
+}
+
+extern "C" uint64_t lfx_encode_members_bound(uint64_t n, uint64_t member_size, uint32_t flags, const lfx_encode_opts *o,
+                                             const lfx_schedule *s) try {
+    lfx_encode_opts d;
+    const char *why = nullptr;
+    if (members_check(member_size, flags, o, s, &d, &why)) return 0;
+    const bool bgzf = (flags & LFX_MEMBERS_BGZF) != 0;
+    const MemberSlices ms = member_slices(n, member_size, flags);
+    // (BGZF: the caller's options, without the BC subfield — lfx_encode_bound leaves 64 bytes for the 10 fixed ones of a header)
+    auto term = [&](uint64_t len) { const uint64_t b = lfx_encode_bound(len, o, s); return bgzf ? std::min<uint64_t>(b, BGZF_MAX_MEMBER) : b; };
+    return (ms.full ? ms.full * term(member_size) : 0) + (ms.have_last ? term(ms.last) : 0) + (bgzf ? BGZF_EOF_LEN : 0);
+} catch (...) { return 0; }
+
+extern "C" int lfx_encode_members_device(lfx_ctx *cc, const lfx_encode_opts *o, const lfx_schedule *s, uint64_t member_size,
+                                         uint32_t flags, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len,
+                                         lfx_member *members, uint32_t max_members, uint32_t *n_members) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (out_len) *out_len = 0;
+    if (n_members) *n_members = 0;
+    lfx_encode_opts d;
+    const char *why = nullptr;
+    int rc = members_check(member_size, flags, o, s, &d, &why);
+    if (rc) { c->set_error(why); return rc; }
+    if (((uintptr_t)d_out & 3) != 0) { c->set_error("output buffer must be 4-byte aligned"); return LFX_E_ARG; }
+    const bool bgzf = (flags & LFX_MEMBERS_BGZF) != 0;
+    std::vector<uint8_t> hdr;
+    if ((rc = container_header(LFX_GZIP, d, hdr))) { c->set_error("extra: longer than 65535 bytes"); return rc; }
+    const MemberSlices ms = member_slices(n, member_size, flags);
+    if (ms.count() >= 0xFFFFFFFFull) { c->set_error("member_size: more than 2^32 - 2 members"); return LFX_E_ARG; }
+    const uint32_t count = (uint32_t)ms.count();
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    if (!count) {
+        // BGZF of no bytes: the end-of-file marker alone
+        static const uint8_t eof[BGZF_EOF_LEN] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43,
+                                                  0x02, 0,    0x1b, 0,    3, 0, 0, 0, 0, 0,    0,    0, 0,    0};
+        if (cap < BGZF_EOF_LEN) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
+        HIP_TRY(hipMemcpyAsync(d_out, eof, BGZF_EOF_LEN, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (out_len) *out_len = BGZF_EOF_LEN;
+        return LFX_OK;
+    }
+    const PlanOpts po = plan_opts(LFX_GZIP, d);
+    // ---- the merged plan: a full slice and the last slice are planned once each (the schedule applies to a slice alone), the
+    // full slice's descriptors are repeated, shifted into the shared index spaces
+    Plan pfull, plast;
+    if (ms.full) { Planner pl(po); apply_schedule(pl, s, member_size); pfull = std::move(pl.finish()); }
+    if (ms.have_last) { Planner pl(po); apply_schedule(pl, s, ms.last); plast = std::move(pl.finish()); }
+    if (bgzf) {
+        // the stored form of a member (no_compression = 1) must have the compressed form's blocks, byte for byte the same
+        // ranges: the device turns one into the other by the blocks' type alone.  (One write of at most 65505 bytes: a block
+        // holding all of it, and an empty final one behind it when block_size <= the slice — in both forms.)
+        PlanOpts ps = po;
+        ps.no_compression = true;
+        for (int k = 0; k < 2; k++) {
+            if (k == 0 ? !ms.full : !ms.have_last) continue;
+            const Plan &pc = k == 0 ? pfull : plast;
+            Planner pl(ps);
+            apply_schedule(pl, s, k == 0 ? member_size : ms.last);
+            const Plan &pr = pl.finish();
+            bool same = pr.blocks.size() == pc.blocks.size();
+            for (size_t b = 0; same && b < pr.blocks.size(); b++)
+                same = pr.blocks[b].in_off == pc.blocks[b].in_off && pr.blocks[b].in_len == pc.blocks[b].in_len &&
+                       pr.blocks[b].final == pc.blocks[b].final && pr.blocks[b].align_after == pc.blocks[b].align_after;
+            if (!same) { c->set_error("block_size: the stored form of a member has other blocks than the compressed form"); return LFX_E_UNSUPPORTED; }
+        }
+    }
+    if ((uint64_t)ms.full * pfull.chunks.size() + plast.chunks.size() > 0xFFFFFFF0ull ||
+        (uint64_t)ms.full * pfull.blocks.size() + plast.blocks.size() > 0xFFFFFFF0ull ||
+        (uint64_t)ms.full * pfull.n_segs + plast.n_segs > 0xFFFFFFF0ull) {
+        c->set_error("member_size: too many blocks for one call");
+        return LFX_E_ARG;
+    }
+    Plan plan;
+    plan.chunks.reserve(ms.full * pfull.chunks.size() + plast.chunks.size());
+    plan.blocks.reserve(ms.full * pfull.blocks.size() + plast.blocks.size());
+    auto append = [&](const Plan &p, uint64_t in_off) {
+        const uint32_t c0 = (uint32_t)plan.chunks.size(), b0 = (uint32_t)plan.blocks.size();
+        for (ChunkDesc ch : p.chunks) {
+            ch.in_off += in_off; ch.code_off += plan.n_codes_cap; ch.block += b0; ch.tile_base += plan.n_tiles;
+            ch.vis_base += plan.n_vis; ch.seg_base += plan.n_segs;
+            plan.chunks.push_back(ch);
+        }
+        for (BlockDesc b : p.blocks) { b.in_off += in_off; b.first_chunk += c0; plan.blocks.push_back(b); }
+        plan.n_codes_cap += p.n_codes_cap; plan.n_tiles += p.n_tiles; plan.n_vis += p.n_vis; plan.n_segs += p.n_segs;
+    };
+    for (uint64_t m = 0; m < ms.full; m++) append(pfull, m * member_size);
+    if (ms.have_last) append(plast, ms.full * member_size);
+    MembersGeom g{};
+    g.n = n; g.member_size = member_size; g.count = count;
+    g.bpm = (uint32_t)(ms.full ? pfull.blocks.size() : plast.blocks.size());
+    g.bpm_last = (uint32_t)(ms.have_last ? plast.blocks.size() : pfull.blocks.size());
+    g.hdr_len = (uint32_t)hdr.size(); g.bgzf = bgzf ? 1u : 0u;
+    const uint32_t nblocks = (uint32_t)plan.blocks.size();
+    // per-member scratch: records, offsets inside the workgroup, lengths, checksums; the workgroup sums; the header
+    const uint32_t nwg = (count + 255) / 256;
+    const size_t cnt = std::max<uint32_t>(count, 1);
+    DevBuf &sb = c->d_dec_streams;     // (decode scratch: free during an encode)
+    if ((rc = sb.reserve((sizeof(lfx_member) + 8 + 8 + 4 + 4) * cnt + 8 * (size_t)std::max<uint32_t>(nwg, 1) + hdr.size() + 64))) return rc;
+    lfx_member *d_members = (lfx_member *)sb.p;
+    uint64_t *d_local = (uint64_t *)(d_members + cnt), *d_mlen = d_local + cnt, *d_wg = d_mlen + cnt;
+    uint32_t *d_crc = (uint32_t *)(d_wg + std::max<uint32_t>(nwg, 1)), *d_adler = d_crc + cnt;
+    uint8_t *d_hdr = (uint8_t *)(d_adler + cnt);
+    // the kernels OR into zeros: [0, min(cap, bound)) is filled once, on the side stream beside the match kernel (as
+    // lfx_encode_device does); no member can end behind the bound, and nothing is written when the total exceeds cap
+    const uint64_t bound = lfx_encode_members_bound(n, member_size, flags, o, s);
+    const uint64_t fill = std::min(cap, bound);
+    bool prezero = fill && hipEventRecord(c->ev_fork, st) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess &&
+                   hipMemsetAsync(d_out, 0, fill, c->side_stream) == hipSuccess && hipEventRecord(c->ev_zero, c->side_stream) == hipSuccess;
+    c->prezero_ptr = nullptr;
+    EncodeResult res{};
+    const uint32_t n_rec = members ? std::min(count, max_members) : 0;
+    auto body = [&]() -> int {
+        for (;;) {
+            int rc2;
+            if ((rc2 = encode_prepare(c, plan, po, (const uint8_t *)d_in, n, 0))) return rc2;
+            HIP_TRY(hipMemcpyAsync(d_hdr, hdr.data(), hdr.size(), hipMemcpyHostToDevice, st));
+            EncodeResult *dres = (EncodeResult *)c->d_res.p;
+            LAUNCH_TRY(launch_members_layout(st, g, (BlockDesc *)c->d_blocks.p, (const BlockCodes *)c->d_bc.p, d_local, d_mlen, d_wg, cap,
+                                             (uint64_t *)c->d_block_start.p, d_members, dres));
+            if (bgzf) c->up_dev[1] = 0;      // the device's block table no longer equals its shadow: the next prepare uploads it
+            c->phase("members_layout");
+            LAUNCH_TRY(launch_checksum_ranges(st, (const uint8_t *)d_in, count, (const uint64_t *)d_members, sizeof(lfx_member) / 8,
+                                              (const uint64_t *)d_members + 1, sizeof(lfx_member) / 8, d_crc, d_adler));
+            c->phase("checksum");
+            if (prezero) HIP_TRY(hipStreamWaitEvent(st, c->ev_zero, 0));
+            else if (fill) HIP_TRY(hipMemsetAsync(d_out, 0, fill, st));
+            prezero = false;
+            LAUNCH_TRY(launch_pack(st, (const uint8_t *)d_in, n, (const ChunkDesc *)c->d_chunks.p, c->cur_nchunks,
+                                   (const BlockDesc *)c->d_blocks.p, nblocks, c->cur_ntiles, (const uint32_t *)c->d_codes.p,
+                                   (const uint32_t *)c->d_ncodes.p, (const BlockCodes *)c->d_bc.p, (const uint64_t *)c->d_block_start.p,
+                                   (uint32_t *)c->d_tile_bits.p, (uint64_t *)c->d_tile_start.p, dres, 0, (uint32_t *)d_out, c->cur_tile_map));
+            c->phase("pack");
+            LAUNCH_TRY(launch_members_frame(st, g, d_hdr, d_members, d_crc, dres, (uint32_t *)d_out));
+            HIP_TRY(hipMemcpyAsync(c->h_res, dres, sizeof(EncodeResult), hipMemcpyDeviceToHost, st));
+            if (n_rec) HIP_TRY(hipMemcpyAsync(members, d_members, sizeof(lfx_member) * (size_t)n_rec, hipMemcpyDeviceToHost, st));
+            c->phase("frame");
+            HIP_TRY(hipStreamSynchronize(st));
+            res = *(EncodeResult *)c->h_res;
+            if (match_violation(c, res)) continue;
+            return LFX_OK;
+        }
+    };
+    rc = body();
+    if (prezero) (void)hipEventSynchronize(c->ev_zero);     // (failed before the stream waited for the fill: it is on the caller's buffer)
+    if (rc) return rc;
+    if (n_members) *n_members = count;
+    if (res.status) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
+    if (out_len) *out_len = res.out_bytes;
+    return LFX_OK;
+} LFX_ABI_CATCH
+
+extern "C" int lfx_encode_members_host(lfx_ctx *cc, const lfx_encode_opts *o, const lfx_schedule *s, uint64_t member_size,
+                                       uint32_t flags, const void *in, uint64_t n, void *out, uint64_t cap, uint64_t *out_len,
+                                       lfx_member *members, uint32_t max_members, uint32_t *n_members) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    if (out_len) *out_len = 0;
+    if (n_members) *n_members = 0;
+    lfx_encode_opts d;
+    const char *why = nullptr;
+    int rc = members_check(member_size, flags, o, s, &d, &why);
+    if (rc) { c->set_error(why); return rc; }
+    const uint64_t bound = lfx_encode_members_bound(n, member_size, flags, o, s);
+    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
+    if ((rc = c->d_io_out.reserve(std::max<uint64_t>(bound, 4)))) return rc;
+    if ((rc = host_to_device(c, c->d_io_in.p, in, n, c->stream))) { c->set_error("host to device copy failed"); return rc; }
+    uint64_t len = 0;
+    rc = lfx_encode_members_device(cc, o, s, member_size, flags, c->d_io_in.p, n, c->d_io_out.p, std::min(cap, bound), &len, members,
+                                   max_members, n_members);
+    // (a page-locked `in` was only queued for DMA: no return before the stream has passed the copy, on any path)
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if ((rc = device_to_host(c, out, c->d_io_out.p, len, c->stream))) { c->set_error("device to host copy failed"); return rc; }
+    if (out_len) *out_len = len;
+    return LFX_OK;
+} LFX_ABI_CATCH
+
+extern "C" int lfx_members_gzi(const lfx_member *members, uint32_t n_members, void *buf, uint64_t cap, uint64_t *len) {
+    if (n_members && !members) return LFX_E_ARG;
+    const uint64_t pairs = n_members ? n_members - 1 : 0, need = 8 + 16 * pairs;
+    if (len) *len = need;
+    if (cap < need || !buf) return cap < need ? LFX_E_NOSPACE : LFX_E_ARG;
+    uint8_t *p = (uint8_t *)buf;
+    auto put64 = [&](uint64_t v) { for (int i = 0; i < 8; i++) *p++ = (uint8_t)(v >> (8 * i)); };
+    put64(pairs);
+    for (uint32_t i = 1; i < n_members; i++) { put64(members[i].out_off); put64(members[i].in_off); }
+    return LFX_OK;
+}
+
 // ---- sharded encode -------------------------------------------------------------------------
 // Where lfx_encode_shard_emit will write: zero-filled on the side stream NOW, beside the match kernel of the prepare call, as
 // lfx_encode_device does for its own output (the pack kernels OR into zeros; on the main stream the fill of a 130 MB shard was

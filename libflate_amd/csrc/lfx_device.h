@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/lfx.h"
 #include "lfx_common.h"
 
 namespace lfx {
@@ -91,6 +92,25 @@ int launch_offsets_batch(hipStream_t st, const BatchStream *streams, uint32_t co
 int launch_frame_batch(hipStream_t st, int format, const BatchStream *streams, uint32_t count, const uint8_t *hdr, uint32_t hdr_len,
                        const uint64_t *stream_end, const uint32_t *crc, const uint32_t *adler, const EncodeResult *res, uint32_t *out,
                        uint64_t *out_len);
+// lfx_encode_members_device (lfx_members_enc.hip): the members are regular, so this is all the kernels need to know of them —
+// member m is input bytes [m * member_size, min(n, (m + 1) * member_size)) and blocks [m * bpm, + bpm) (the last: bpm_last)
+struct MembersGeom {
+    uint64_t n, member_size;
+    uint32_t count;
+    uint32_t bpm, bpm_last;     // blocks per member of the merged plan
+    uint32_t hdr_len;           // the shared gzip header
+    uint32_t bgzf;              // LFX_MEMBERS_BGZF: BSIZE in every header, the stored fallback, the end-of-file marker
+};
+// behind the Huffman kernel: every member's length (BGZF: its stored form where the compressed one exceeds 65536 bytes), the
+// device-wide exclusive scan of the lengths, block_start[] at the final offsets, blocks[].type of fallen-back members = BT_RAW,
+// members[] complete; res->out_bytes = the total (BGZF: marker included), res->status = 1 when it exceeds cap.
+// local_off, mlen: 8 bytes per member; wg_sum: 8 bytes per 256 members (at least 8)
+int launch_members_layout(hipStream_t st, const MembersGeom &g, BlockDesc *blocks, const BlockCodes *bc, uint64_t *local_off,
+                          uint64_t *mlen, uint64_t *wg_sum, uint64_t cap, uint64_t *block_start, lfx_member *members,
+                          EncodeResult *res);
+// behind pack: headers, trailers, the end-of-file marker (nothing when res->status != 0)
+int launch_members_frame(hipStream_t st, const MembersGeom &g, const uint8_t *hdr, const lfx_member *members, const uint32_t *crc,
+                         const EncodeResult *res, uint32_t *out);
 int launch_pack(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks,
                 uint32_t nchunks, const BlockDesc *blocks, uint32_t nblocks, uint64_t ntiles,
                 const uint32_t *codes, const uint32_t *ncodes, const BlockCodes *bc,

@@ -134,3 +134,25 @@ def decode_members(data, context=None):
     if rc != _ffi.OK:
         raise StreamError(rc, msg)
     return out, members
+
+
+def encode_members(data, member_size=1 << 20, bgzf=False, options=None, context=None):
+    """`data` as gzip members of member_size input bytes each, lying back to back: what decode_members, zcat and Python's gzip
+    read, and with bgzf=True (member_size at most 65505; bgzip's own is _ffi.BGZF_MEMBER_SIZE = 65280) a BGZF file with its
+    end-of-file marker.  All members are encoded on the GPU in one pass (lfx_encode_members_host) → (bytes, [(in_off, in_len,
+    out_off, out_len)] per member: the slice of `data`, the member in the result).  members_to_gzi(members) is bgzip's index of
+    them.  Raises StreamError where the call fails."""
+    ctx = context if context is not None else default_context()
+    opts = (options if options is not None else EncodeOptions())._to_c()
+    try:
+        rc, out, _count, members, msg = ctx.encode_members_host(data, member_size, _ffi.MEMBERS_BGZF if bgzf else 0, opts)
+    except _ffi.DeviceError:
+        raise
+    except _ffi.LfxError as e:          # (an argument out of its domain: the message names the field)
+        raise StreamError(e.status, e.message)
+    if rc != _ffi.OK:
+        raise StreamError(rc, msg)
+    return out, members
+
+
+members_to_gzi = _ffi.members_to_gzi
