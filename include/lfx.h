@@ -130,7 +130,8 @@ int lfx_decode_device(lfx_ctx *c, int format, uint32_t flags, const void *d_in, 
 int lfx_decode_host(lfx_ctx *c, int format, uint32_t flags, const void *in, uint64_t n, void *out,
                     uint64_t cap, uint64_t *out_len, uint64_t *consumed);
 /* `count` independent streams, one wavefront each (BASELINE.json configs[2]).
- * offsets/lengths are HOST arrays; status[i] gets LFX_* per stream. */
+ * offsets/lengths are HOST arrays; status[i] gets LFX_* per stream.  lfx_decode_batch_size_device below reports the
+ * out_cap[] a batch needs. */
 int lfx_decode_batch_device(lfx_ctx *c, int format, uint32_t count, const void *d_in,
                             const uint64_t *in_off, const uint64_t *in_len, void *d_out,
                             const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
@@ -143,7 +144,8 @@ int lfx_decode_batch_device(lfx_ctx *c, int format, uint32_t count, const void *
  * lfx_ctx_last_error and d_out[0 .. *out_len) are exactly those of
  * lfx_decode_device(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, d_out, cap, ...).
  * members: the members whose trailer was verified, in input order; *n_members = their count (also when that exceeds
- * max_members: only the first max_members entries are written).  members may be NULL. */
+ * max_members: only the first max_members entries are written).  members may be NULL.  lfx_decode_members_size_device
+ * below reports the cap an input needs. */
 typedef struct lfx_member {
     uint64_t in_off, in_len;   /* the member's bytes in the input: header .. 8-byte trailer */
     uint64_t out_off, out_len; /* its output in d_out */
@@ -155,6 +157,38 @@ int lfx_decode_members_device(lfx_ctx *c, const void *d_in, uint64_t n, void *d_
 int lfx_decode_members_host(lfx_ctx *c, const void *in, uint64_t n, void *out, uint64_t cap,
                             uint64_t *out_len, uint64_t *consumed,
                             lfx_member *members, uint32_t max_members, uint32_t *n_members);
+
+/* ---- decoded size without decoding: `gzip -l` for this library --------------------------------------------
+ * Let D = (status, *out_len, *consumed) of the matching decode call with a cap that is large enough: lfx_decode_device /
+ * lfx_decode_host for lfx_decode_size_*, stream i of lfx_decode_batch_device for the batch call, lfx_decode_members_* for
+ * lfx_decode_members_size_*.  A size call takes no output buffer and produces no bytes:
+ *  1. The checksums (CRC-32 / Adler-32) are NOT computed.  Everything else a decode checks is checked: container header and
+ *     its CRC where present, block headers and code tables, every symbol, stored LEN / NLEN, "Too long backword reference" (a
+ *     distance that reaches in front of the member's first byte), the end of the input inside a block, and the PRESENCE of the
+ *     4- or 8-byte trailer (a missing one is LFX_E_UNEXPECTED_EOF as in the decode).
+ *  2. Where D's status is anything but a checksum mismatch, the size call returns exactly D, on damaged input too: *out_len
+ *     is then the partial output the decode leaves in d_out.  lfx_ctx_last_error is the decode's message.  (One verdict
+ *     differs in *consumed: behind "Invalid huffman coded stream" the decode calls count the 16 bits the reference's decoder
+ *     skips without reading them, up to two bytes; the size calls report the bytes the reference's reader has pulled.)
+ *  3. Where D's status is a checksum mismatch, the size call goes on as if the checksum had matched (LFX_DEC_MULTI: with the
+ *     next member).  So always *out_len >= D's, and a decode with cap = *out_len never returns LFX_E_NOSPACE.
+ *  4. Batch: status[i], out_len[i], consumed[i] (the bytes of stream i consumed, trailer included) by the same rules; the
+ *     return value is LFX_OK as in lfx_decode_batch_device.  Members: members[], *n_members and the truncation at max_members
+ *     as lfx_decode_members_device documents them; by rule 3 a member with a bad CRC is listed and the walk goes on behind it.
+ *  5. A NULL context: LFX_E_DEVICE, nothing written.  n == 0, count == 0, NULL out_len / consumed / status / members: as the
+ *     matching decode call.
+ *  6. The calls write no device memory of the caller's, reserve no output-sized scratch, and leave the context usable. */
+int lfx_decode_size_device(lfx_ctx *c, int format, uint32_t flags, const void *d_in, uint64_t n,
+                           uint64_t *out_len, uint64_t *consumed);
+int lfx_decode_size_host(lfx_ctx *c, int format, uint32_t flags, const void *in, uint64_t n,
+                         uint64_t *out_len, uint64_t *consumed);
+int lfx_decode_batch_size_device(lfx_ctx *c, int format, uint32_t count, const void *d_in,
+                                 const uint64_t *in_off, const uint64_t *in_len,
+                                 uint64_t *out_len, uint64_t *consumed, int32_t *status);
+int lfx_decode_members_size_device(lfx_ctx *c, const void *d_in, uint64_t n, uint64_t *out_len, uint64_t *consumed,
+                                   lfx_member *members, uint32_t max_members, uint32_t *n_members);
+int lfx_decode_members_size_host(lfx_ctx *c, const void *in, uint64_t n, uint64_t *out_len, uint64_t *consumed,
+                                 lfx_member *members, uint32_t max_members, uint32_t *n_members);
 
 /* The other direction: d_in[0, n) as gzip members that lie back to back in d_out[0, *out_len) — what lfx_decode_members_device
  * decodes as one batch, and what zcat, Python's gzip and (with LFX_MEMBERS_BGZF) bgzip / htslib read.  The

@@ -37,6 +37,8 @@ EXPORTS = [
     "lfx_decode_index_device", "lfx_index_read_device", "lfx_index_span", "lfx_index_get_info", "lfx_index_get_point",
     "lfx_index_export", "lfx_index_import", "lfx_index_check", "lfx_index_free", "lfx_encode_index_device",
     "lfx_encode_members_bound", "lfx_encode_members_device", "lfx_encode_members_host", "lfx_members_gzi",
+    "lfx_decode_size_device", "lfx_decode_size_host", "lfx_decode_batch_size_device", "lfx_decode_members_size_device",
+    "lfx_decode_members_size_host",
 ]
 
 
@@ -182,6 +184,11 @@ def lib():
                                             C.POINTER(u32)]
     L.lfx_decode_members_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,
                                           C.POINTER(u32)]
+    for f in (L.lfx_decode_size_device, L.lfx_decode_size_host):
+        f.argtypes = [vp, i32, u32, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.lfx_decode_batch_size_device.argtypes = [vp, i32, u32, vp, vp, vp, vp, vp, vp]
+    for f in (L.lfx_decode_members_size_device, L.lfx_decode_members_size_host):
+        f.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32, C.POINTER(u32)]
     L.lfx_encode_members_bound.restype = u64
     L.lfx_encode_members_bound.argtypes = [u64, u64, u32, C.POINTER(EncodeOpts), C.POINTER(Schedule)]
     for f in (L.lfx_encode_members_device, L.lfx_encode_members_host):

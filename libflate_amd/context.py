@@ -170,6 +170,58 @@ class Context:
                 continue
             return rc, out.raw[:ol], used, members, msg
 
+    def _raise_fatal(self, rc):
+        if rc in (_ffi.E_DEVICE, _ffi.E_OOM, _ffi.E_ARG):
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+
+    def decode_size_device(self, fmt, d_in, n, flags=0):
+        """what decode_device would report with a large enough cap, without an output buffer (lfx_decode_size_device; the
+        checksums are not computed) → (status, out_len, consumed, message)"""
+        out_len, consumed = C.c_uint64(0), C.c_uint64(0)
+        rc = _ffi.lib().lfx_decode_size_device(self._h, fmt, flags, d_in, n, C.byref(out_len), C.byref(consumed))
+        self._raise_fatal(rc)
+        return rc, out_len.value, consumed.value, self.last_error() if rc else ""
+
+    def decode_size_host(self, fmt, data, flags=0):
+        """the same on host bytes (lfx_decode_size_host) → (status, out_len, consumed, message)"""
+        data = bytes(data)
+        out_len, consumed = C.c_uint64(0), C.c_uint64(0)
+        rc = _ffi.lib().lfx_decode_size_host(self._h, fmt, flags, data, len(data), C.byref(out_len), C.byref(consumed))
+        self._raise_fatal(rc)
+        return rc, out_len.value, consumed.value, self.last_error() if rc else ""
+
+    def decode_batch_size_device(self, fmt, d_in, in_offs, in_lens):
+        """the decoded sizes of len(in_offs) independent streams (lfx_decode_batch_size_device) → (out_lens, consumed, statuses):
+        what decode_batch_device needs as out_caps"""
+        k = len(in_offs)
+        a = lambda v: (C.c_uint64 * max(k, 1))(*v)
+        io, il = a(in_offs), a(in_lens)
+        ol, used, st = (C.c_uint64 * max(k, 1))(), (C.c_uint64 * max(k, 1))(), (C.c_int32 * max(k, 1))()
+        rc = _ffi.lib().lfx_decode_batch_size_device(self._h, fmt, k, d_in, io, il, ol, used, st)
+        if rc:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return list(ol[:k]), list(used[:k]), list(st[:k])
+
+    def _members_size(self, fn, src, n, max_members):
+        if max_members is None:
+            max_members = n // 20 + 1           # (a gzip member takes at least 20 bytes)
+        table = (_ffi.Member * max(int(max_members), 1))()
+        out_len, consumed, count = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        rc = fn(self._h, src, n, C.byref(out_len), C.byref(consumed), table, int(max_members), C.byref(count))
+        self._raise_fatal(rc)
+        members = [(m.in_off, m.in_len, m.out_off, m.out_len) for m in table[:min(count.value, int(max_members))]]
+        return rc, out_len.value, consumed.value, members, self.last_error() if rc else ""
+
+    def decode_members_size_device(self, d_in, n, max_members=None):
+        """the member table and total size decode_members_device would report, without an output buffer
+        (lfx_decode_members_size_device) → (status, out_len, consumed, members, message)"""
+        return self._members_size(_ffi.lib().lfx_decode_members_size_device, d_in, n, max_members)
+
+    def decode_members_size_host(self, data, max_members=None):
+        """the same on host bytes (lfx_decode_members_size_host)"""
+        data = bytes(data)
+        return self._members_size(_ffi.lib().lfx_decode_members_size_host, data, len(data), max_members)
+
     def _encode_members(self, fn, src, n, dst, cap, member_size, flags, opts, schedule, max_members):
         count = 0 if (flags & _ffi.MEMBERS_BGZF and n == 0) else max(1, -(-n // member_size)) if member_size else 0
         if max_members is None:

@@ -1893,6 +1893,510 @@ extern "C" int lfx_decode_members_host(lfx_ctx *cc, const void *in, uint64_t n, 
 } LFX_ABI_CATCH
 
 // ------------------------------------------------------------------------------------------------
+// Decoded size without decoding (lfx_decode_size_*).  The verdict of the matching decode call — status,
+// bytes produced, bytes consumed, message — without an output buffer: the blocks are walked on the device by
+// blk_walk_size_kernel (no output, no code words, no checksum), and whatever the walker does not settle is decided by the
+// exact serial kernel in its count-only mode, from the stream's start, as the decode paths fall back to it.
+namespace {
+int run_walk(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<WalkJob> &jobs, std::vector<WalkResult> &res) {
+    const size_t nj = jobs.size();
+    res.resize(nj);
+    if (!nj) return LFX_OK;
+    int rc;
+    if ((rc = c->d_dec_streams.reserve(sizeof(WalkJob) * nj))) return rc;
+    if ((rc = c->d_dec_state.reserve(sizeof(WalkResult) * nj))) return rc;
+    // (ranges of a few tens of KB: 256 lanes a job, as batch_fast picks the scan's instance)
+    uint64_t range_bits = 0;
+    for (const WalkJob &j : jobs) {
+        const uint64_t e = j.stop_bit > j.start_bit && j.stop_bit < j.end_bit ? j.stop_bit : j.end_bit;
+        range_bits += e > j.start_bit ? e - j.start_bit : 0;
+    }
+    const bool small = range_bits / nj < (512ull << 10);
+    HIP_TRY(hipMemcpyAsync(c->d_dec_streams.p, jobs.data(), sizeof(WalkJob) * nj, hipMemcpyHostToDevice, c->stream));
+    LAUNCH_TRY(launch_blk_walk_size(c->stream, d_in, n, (const WalkJob *)c->d_dec_streams.p, (uint32_t)nj,
+                                    (WalkResult *)c->d_dec_state.p, small));
+    HIP_TRY(hipMemcpyAsync(res.data(), c->d_dec_state.p, sizeof(WalkResult) * nj, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return LFX_OK;
+}
+inline bool walk_settled(const WalkResult &r, uint64_t out_before) {
+    return r.status != WALK_STUCK && (r.reach == INT64_MAX || (int64_t)out_before + r.reach >= 0);
+}
+
+// `consumed` behind an "Invalid huffman coded stream" verdict.  The reference's decoder skips 16 bits it never read when a
+// code is unassigned (huffman.rs:157-179), and inflate_kernel's end_bit counts them as the decode's `consumed` does; what
+// the reference's reader has pulled from its input at that point is the shortest prefix of the stream that still gives the
+// same verdict.  That prefix is found with the exact kernel itself: the failing block again, count-only, on the two or three
+// candidate lengths in ONE launch (only on this rare verdict).  probes[i]: stream base, stream length, the exact path's
+// result → used[i] = bytes of the stream consumed.
+struct HuffProbe { uint64_t in_off, in_len; InflateResult r; };
+int huff_consumed(Ctx *c, const uint8_t *d_in, const std::vector<HuffProbe> &probes, std::vector<uint64_t> &used) {
+    used.assign(probes.size(), 0);
+    std::vector<InflateJob> jobs;
+    std::vector<size_t> owner;
+    for (size_t i = 0; i < probes.size(); i++) {
+        const HuffProbe &p = probes[i];
+        const uint64_t hi = std::min<uint64_t>((p.r.end_bit + 7) / 8, p.in_len);
+        const uint64_t before = p.r.end_bit >= 16 ? p.r.end_bit - 16 : 0;
+        used[i] = hi;
+        for (uint64_t k = std::max<uint64_t>((before + 7) / 8, (p.r.blk_start_bit + 7) / 8); k < hi; k++) {
+            InflateJob j{};
+            j.in_off = p.in_off; j.in_len = k; j.start_bit = p.r.blk_start_bit;
+            j.out_cap = ~0ull; j.hist_avail = p.r.blk_out_start; j.flags = JOB_COUNT_ONLY;
+            jobs.push_back(j);
+            owner.push_back(i);
+        }
+    }
+    std::vector<InflateResult> res;
+    if (int rc = run_jobs(c, d_in, nullptr, jobs, res)) return rc;
+    for (size_t q = jobs.size(); q-- > 0;) {      // (descending lengths: the shortest prefix with the same verdict wins)
+        const InflateResult &r = probes[owner[q]].r, &t = res[q];
+        if (t.status == r.status && t.err == r.err && t.end_bit == r.end_bit && t.out_len == r.out_len - r.blk_out_start &&
+            used[owner[q]] == jobs[q].in_len + 1)
+            used[owner[q]] = jobs[q].in_len;
+    }
+    return LFX_OK;
+}
+inline bool huff_verdict(const InflateResult &r) { return r.status == 1 && r.err == ERR_HUFF; }
+
+// the finder of inflate_member for the size path: the sorted block-start candidates of d_in[off0, n), first_bit among them
+int size_candidates(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t off0, uint64_t first_bit, std::vector<uint64_t> &starts,
+                    bool &overflow) {
+    hipStream_t st = c->stream;
+    const uint64_t comp = n - off0;
+    const uint32_t shard_cap = find_shard_cap(comp);
+    const uint32_t final_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1u << 16, comp / 4096), 1u << 24);
+    int rc;
+    if ((rc = c->d_dec_cand.reserve(8ull * shard_cap * FIND_SHARDS + 8ull * final_cap + 4 * FIND_HDR_WORDS))) return rc;
+    uint32_t *d_count = (uint32_t *)c->d_dec_cand.p;
+    uint32_t *d_final_count = d_count + FIND_HDR_FINAL;
+    uint64_t *d_final = (uint64_t *)((uint8_t *)c->d_dec_cand.p + 4 * FIND_HDR_WORDS);
+    uint64_t *d_cand = d_final + final_cap;
+    HIP_TRY(hipMemsetAsync(d_count, 0, 4 * FIND_HDR_WORDS, st));
+    // (the last block is looked for in the stream's tail only, as in the decode: a walk that meets it earlier follows it anyway)
+    const uint64_t tail_bytes = std::max<uint64_t>(comp / 8, 8ull << 20);
+    const uint64_t final_from = comp > tail_bytes ? (n - tail_bytes) * 8 : 0;
+    LAUNCH_TRY(launch_find_stage1(st, d_in, n, off0, d_count, d_cand, shard_cap, final_from, (uint32_t)std::max(c->n_cu, 1)));
+    c->phase("find1");
+    LAUNCH_TRY(launch_find_stage2(st, d_in, n, d_cand, shard_cap, d_count, d_count + FIND_HDR_WORK, d_final_count, d_final, final_cap,
+                                  (uint32_t)std::max(c->n_cu, 1), nullptr));
+    std::vector<uint32_t> hc(FIND_HDR_READ);
+    HIP_TRY(hipMemcpyAsync(hc.data(), d_count, 4ull * FIND_HDR_READ, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    overflow = hc[FIND_SHARDS] != 0;
+    for (uint32_t k = 0; k < FIND_SHARDS; k++) if (hc[k] > shard_cap) overflow = true;
+    starts.clear();
+    starts.push_back(first_bit);
+    if (!overflow) {
+        const uint32_t nf = std::min(hc[FIND_HDR_FINAL], final_cap);
+        std::vector<uint64_t> cand(nf);
+        if (nf) HIP_TRY(hipMemcpy(cand.data(), d_final, 8ull * nf, hipMemcpyDeviceToHost));
+        for (uint64_t b : cand) if (b > first_bit) starts.push_back(b);
+        std::sort(starts.begin(), starts.end());
+        starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    }
+    c->phase("find2");
+    return LFX_OK;
+}
+
+// inflate_member for sizes: mr.status / out_len / end_byte / msg of the DEFLATE stream at byte off0 of d_in[0, n)
+int size_member(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t off0, MemberResult &mr) {
+    const uint64_t first_bit = off0 * 8;
+    const uint64_t comp = n > off0 ? n - off0 : 0;
+    bool done = false;
+    int rc;
+    std::vector<WalkResult> wr;
+    uint64_t total = 0, end_bit = 0;
+    if (comp >= 64 && comp < (256u << 10)) {
+        // a short stream: one workgroup follows its blocks from the known first one
+        if ((rc = run_walk(c, d_in, n, {WalkJob{first_bit, n * 8, 0}}, wr))) return rc;
+        c->phase("walk_size");
+        if (wr[0].status == WALK_FINAL && walk_settled(wr[0], 0)) { done = true; total = wr[0].n_out; end_bit = wr[0].end_bit; }
+    } else if (comp >= 64) {
+        // a long stream: the finder's candidates, one walk from each up to the next, the chain on the host
+        std::vector<uint64_t> starts;
+        bool overflow = false;
+        if ((rc = size_candidates(c, d_in, n, off0, first_bit, starts, overflow))) return rc;
+        std::vector<WalkJob> jobs(starts.size());
+        for (size_t i = 0; i < starts.size(); i++) jobs[i] = WalkJob{starts[i], n * 8, i + 1 < starts.size() ? starts[i + 1] : 0};
+        if ((rc = run_walk(c, d_in, n, jobs, wr))) return rc;
+        c->phase("walk_size");
+        uint64_t pos = first_bit;
+        uint32_t on_demand = 0;
+        for (;;) {
+            const auto it = std::lower_bound(starts.begin(), starts.end(), pos);
+            WalkResult r;
+            if (it != starts.end() && *it == pos) r = wr[(size_t)(it - starts.begin())];
+            else {
+                // a block the finder did not report (stored, fixed, a final block in front of the tail): walked on demand
+                if (on_demand++ >= 64) break;
+                std::vector<WalkResult> one;
+                if ((rc = run_walk(c, d_in, n, {WalkJob{pos, n * 8, it != starts.end() ? *it : 0}}, one))) return rc;
+                r = one[0];
+            }
+            if (!walk_settled(r, total) || r.end_bit <= pos) break;      // the exact path decides, from the stream's start
+            total += r.n_out;
+            if (r.status == WALK_FINAL) { done = true; end_bit = r.end_bit; break; }
+            pos = r.end_bit;
+        }
+        c->phase("chain");
+    }
+    if (done) {
+        mr.status = LFX_OK;
+        mr.out_len = mr.blk_out_start = total;
+        mr.end_bit = end_bit;
+        mr.end_byte = (end_bit + 7) / 8;
+        mr.final_seen = true;
+        return LFX_OK;
+    }
+    // ---- the exact path: the serial kernel, count-only (no stores; its own error codes and message arguments)
+    InflateJob j{};
+    j.in_off = 0; j.in_len = n; j.start_bit = first_bit;
+    j.out_off = 0; j.out_cap = ~0ull; j.hist_avail = 0; j.stop_bit = 0; j.flags = JOB_COUNT_ONLY;
+    std::vector<InflateResult> res;
+    if ((rc = run_jobs(c, d_in, nullptr, {j}, res))) return rc;
+    c->phase("serial");
+    const InflateResult &r = res[0];
+    mr.status = map_status(r.status);
+    mr.out_len = r.out_len;
+    mr.blk_out_start = r.status ? r.blk_out_start : r.out_len;
+    mr.end_byte = std::min<uint64_t>((r.end_bit + 7) / 8, n);
+    if (huff_verdict(r)) {
+        std::vector<uint64_t> used;
+        if ((rc = huff_consumed(c, d_in, {HuffProbe{0, n, r}}, used))) return rc;
+        mr.end_byte = used[0];
+    }
+    mr.end_bit = r.end_bit;
+    mr.final_seen = r.status == 0 && r.final_seen;
+    mr.msg = format_error(r.err, r.a0, r.a1);
+    return LFX_OK;
+}
+
+// decode_stream for sizes: the member loop without output and without the checksum comparison (a trailer must be THERE)
+int size_stream(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_t n, DecodeOutcome &oc, uint64_t base = 0,
+                uint64_t out_at = 0, bool one_member = false, std::vector<lfx_member> *members = nullptr) {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    bool first = base == 0;
+    oc.consumed = base;
+    oc.out_len = oc.delivered_len = out_at;
+    int rc;
+    if ((rc = c->d_small.reserve(70000))) return rc;
+    for (;;) {
+        uint64_t off0 = 0;
+        if (format != LFX_DEFLATE) {
+            DecStream ds{base, n - base, 0, 0};
+            DecHeader dh{};
+            c->pin_reset();
+            HIP_TRY(c->small_up(c->d_small.p, &ds, sizeof ds, st));
+            LAUNCH_TRY(launch_container(st, format, 1, d_in, (const DecStream *)c->d_small.p,
+                                        (DecHeader *)((uint8_t *)c->d_small.p + 256)));
+            HIP_TRY(c->small_down(&dh, (uint8_t *)c->d_small.p + 256, sizeof dh, st));
+            HIP_TRY(c->small_sync(st));
+            if (dh.status != 0) {
+                if (!first && dh.status == 2) { oc.consumed = n; break; }     // MultiDecoder: a cut header behind a member = clean end
+                oc.status = map_status(dh.status);
+                oc.header_failed = first;
+                oc.msg = format_error(dh.err, dh.a0, dh.a1);
+                oc.consumed = base + dh.deflate_off;
+                oc.out_len = oc.delivered_len = out_at;
+                return LFX_OK;
+            }
+            off0 = dh.deflate_off;
+        }
+        MemberResult mr;
+        if ((rc = size_member(c, d_in + base, n - base, off0, mr))) return rc;
+        oc.out_len = out_at + mr.out_len;
+        oc.delivered_len = out_at + mr.blk_out_start;
+        oc.consumed = base + mr.end_byte;
+        if (mr.status != LFX_OK) { oc.status = mr.status; oc.msg = mr.msg; return LFX_OK; }
+        if (format != LFX_DEFLATE) {
+            const uint64_t need = format == LFX_GZIP ? 8 : 4;
+            const uint64_t tpos = base + mr.end_byte;
+            if (n - tpos < need) {
+                oc.status = LFX_E_UNEXPECTED_EOF;
+                oc.msg = "failed to fill whole buffer";
+                oc.consumed = n;
+                return LFX_OK;
+            }
+            oc.consumed = tpos + need;
+        }
+        if (members) members->push_back(lfx_member{base, oc.consumed - base, out_at, mr.out_len});
+        out_at = oc.out_len;
+        if (one_member) { oc.more = true; break; }
+        if (!(format == LFX_GZIP && (flags & LFX_DEC_MULTI))) break;
+        base = oc.consumed;
+        first = false;
+    }
+    oc.out_len = oc.delivered_len = out_at;
+    return LFX_OK;
+}
+
+// decode_members for sizes: candidates, header parse, ONE walker launch per group of candidates, the chain on the host; a
+// start the walk did not settle goes through size_stream for one member, and the member loop gives the verdict of the tail
+int size_members(Ctx *c, const uint8_t *d_in, uint64_t n, DecodeOutcome &oc, std::vector<lfx_member> &members) {
+    hipStream_t st = c->stream;
+    int rc;
+    std::vector<uint64_t> cand;
+    if ((rc = member_candidates(c, d_in, n, cand))) return rc;
+    c->phase("candidates");
+    std::vector<MemberWalk> walk(cand.size());
+    members.clear();
+    uint64_t base = 0, out_at = 0;
+    size_t walked_to = 0;
+    while (base < n) {
+        const size_t k = (size_t)(std::lower_bound(cand.begin(), cand.end(), base) - cand.begin());
+        const bool is_cand = k < cand.size() && cand[k] == base;
+        if (is_cand && k >= walked_to) {
+            const size_t k1 = std::min<size_t>(cand.size(), k + MEMBER_GROUP);
+            const uint32_t cnt = (uint32_t)(k1 - k);
+            std::vector<DecStream> ds(cnt);
+            for (uint32_t i = 0; i < cnt; i++) ds[i] = DecStream{cand[k + i], std::min(n - cand[k + i], MEMBER_HDR_BYTES), 0, 0};
+            const size_t sz_ds = sizeof(DecStream) * cnt, sz_dh = sizeof(DecHeader) * cnt;
+            if ((rc = c->d_dec_blocks.reserve(sz_ds + sz_dh))) return rc;
+            DecStream *d_ds = (DecStream *)c->d_dec_blocks.p;
+            DecHeader *d_dh = (DecHeader *)((uint8_t *)c->d_dec_blocks.p + sz_ds);
+            HIP_TRY(hipMemcpyAsync(d_ds, ds.data(), sz_ds, hipMemcpyHostToDevice, st));
+            LAUNCH_TRY(launch_container(st, LFX_GZIP, cnt, d_in, d_ds, d_dh));
+            std::vector<DecHeader> dh(cnt);
+            HIP_TRY(hipMemcpyAsync(dh.data(), d_dh, sz_dh, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            std::vector<WalkJob> jobs;
+            std::vector<size_t> owner;
+            for (uint32_t i = 0; i < cnt; i++) {
+                walk[k + i].state = 2;
+                if (dh[i].status != 0) continue;
+                const uint64_t data = cand[k + i] + dh[i].deflate_off;
+                // (a member's trailer lies in front of the next member's header; a member longer than MEMBER_WALK_BYTES is "long")
+                uint64_t lim = std::min<uint64_t>(n, cand[k + i] + MEMBER_WALK_BYTES);
+                const auto nx = std::upper_bound(cand.begin(), cand.end(), data);
+                if (nx != cand.end() && *nx < lim) lim = *nx;
+                if (lim <= data) continue;
+                jobs.push_back(WalkJob{data * 8, lim * 8, 0});
+                owner.push_back(k + i);
+            }
+            std::vector<WalkResult> wr;
+            if ((rc = run_walk(c, d_in, n, jobs, wr))) return rc;
+            for (size_t q = 0; q < jobs.size(); q++)
+                if (wr[q].status == WALK_FINAL && walk_settled(wr[q], 0)) {
+                    MemberWalk &w = walk[owner[q]];
+                    w.end_byte = (wr[q].end_bit + 7) / 8;
+                    w.n_out = wr[q].n_out;
+                    w.state = 1;
+                }
+            walked_to = k1;
+            if (c->n_ev + 6 < 17) c->phase("walk_size");
+        }
+        if (is_cand && walk[k].state == 1) {
+            const MemberWalk &w = walk[k];
+            if (n - w.end_byte < 8) break;        // a cut trailer: the tail says so
+            members.push_back(lfx_member{base, w.end_byte + 8 - base, out_at, w.n_out});
+            base = w.end_byte + 8;
+            out_at += w.n_out;
+            continue;
+        }
+        DecodeOutcome one;
+        std::vector<lfx_member> got;
+        {
+            PhaseMute mute(c);
+            if ((rc = size_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, one, base, out_at, true, &got))) return rc;
+        }
+        if (!one.more || got.size() != 1) break;
+        members.push_back(got[0]);
+        base = one.consumed;
+        out_at = one.out_len;
+    }
+    c->phase("chain");
+    {
+        PhaseMute mute(c);
+        if ((rc = size_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, oc, base, out_at, false, &members))) return rc;
+    }
+    c->phase("tail");
+    return LFX_OK;
+}
+
+// the input of a host variant, staged like lfx_decode_host's
+int size_stage_in(Ctx *c, const void *in, uint64_t n) {
+    int rc;
+    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
+    if (int hr = host_to_device(c, c->d_io_in.p, in, n, c->stream)) { c->set_error("host to device copy failed"); return hr; }
+    return LFX_OK;
+}
+}  // namespace
+
+extern "C" int lfx_decode_size_device(lfx_ctx *cc, int format, uint32_t flags, const void *d_in, uint64_t n,
+                                      uint64_t *out_len, uint64_t *consumed) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (format < 0 || format > 2) return LFX_E_ARG;
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    DecodeOutcome oc;
+    int rc = size_stream(c, format, flags, (const uint8_t *)d_in, n, oc);
+    if (rc) return rc;
+    if (oc.status == LFX_OK) c->phase("done");
+    if (out_len) *out_len = oc.out_len;
+    if (consumed) *consumed = oc.consumed;
+    if (oc.status != LFX_OK) c->set_error(oc.msg);
+    return oc.status;
+} LFX_ABI_CATCH
+
+extern "C" int lfx_decode_size_host(lfx_ctx *cc, int format, uint32_t flags, const void *in, uint64_t n,
+                                    uint64_t *out_len, uint64_t *consumed) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    if (int rc = size_stage_in(c, in, n)) return rc;
+    const int rc = lfx_decode_size_device(cc, format, flags, c->d_io_in.p, n, out_len, consumed);
+    (void)hipStreamSynchronize(c->stream);   // (a page-locked `in` was only queued for DMA)
+    return rc;
+} LFX_ABI_CATCH
+
+extern "C" int lfx_decode_batch_size_device(lfx_ctx *cc, int format, uint32_t count, const void *d_in_, const uint64_t *in_off,
+                                            const uint64_t *in_len, uint64_t *out_len, uint64_t *consumed, int32_t *status) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    if (!count) return LFX_OK;
+    if (format < 0 || format > 2) return LFX_E_ARG;
+    hipStream_t st = c->stream;
+    const uint8_t *d_in = (const uint8_t *)d_in_;
+    int rc;
+    // ---- container headers (container_kernel)
+    std::vector<DecStream> streams(count);
+    for (uint32_t i = 0; i < count; i++) streams[i] = DecStream{in_off[i], in_len[i], 0, 0};
+    std::vector<DecHeader> hdrs(count, DecHeader{});
+    if (format != LFX_DEFLATE) {
+        const size_t sz_streams = sizeof(DecStream) * count, sz_hdr = sizeof(DecHeader) * count;
+        if ((rc = c->d_dec_blocks.reserve(sz_streams + sz_hdr))) return rc;
+        DecStream *d_streams = (DecStream *)c->d_dec_blocks.p;
+        DecHeader *d_hdrs = (DecHeader *)((uint8_t *)c->d_dec_blocks.p + sz_streams);
+        HIP_TRY(hipMemcpyAsync(d_streams, streams.data(), sz_streams, hipMemcpyHostToDevice, st));
+        LAUNCH_TRY(launch_container(st, format, count, d_in, d_streams, d_hdrs));
+        HIP_TRY(hipMemcpyAsync(hdrs.data(), d_hdrs, sz_hdr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    c->phase("headers");
+    uint64_t n_in = 0;
+    for (uint32_t i = 0; i < count; i++) n_in = std::max(n_in, in_off[i] + in_len[i]);
+    // ---- the walker for every stream of at least 64 bytes whose header stands
+    std::vector<InflateResult> res(count, InflateResult{});
+    std::vector<uint8_t> settled(count, 0);
+    std::vector<WalkJob> wj;
+    std::vector<uint32_t> widx;
+    for (uint32_t i = 0; i < count; i++) {
+        if (hdrs[i].status != 0 || in_len[i] < 64) continue;
+        wj.push_back(WalkJob{(in_off[i] + hdrs[i].deflate_off) * 8, (in_off[i] + in_len[i]) * 8, 0});
+        widx.push_back(i);
+    }
+    std::vector<WalkResult> wr;
+    if ((rc = run_walk(c, d_in, n_in, wj, wr))) return rc;
+    uint64_t walk_blocks = 0;
+    for (size_t q = 0; q < wj.size(); q++) {
+        walk_blocks += wr[q].nblocks;
+        if (wr[q].status != WALK_FINAL || !walk_settled(wr[q], 0)) continue;
+        InflateResult &o = res[widx[q]];
+        o.end_bit = wr[q].end_bit - in_off[widx[q]] * 8;
+        o.out_len = o.blk_out_start = wr[q].n_out;
+        o.final_seen = 1;
+        o.nblocks = wr[q].nblocks;
+        settled[widx[q]] = 1;
+    }
+    c->phase("walk_size");
+    // ---- the exact path for the rest
+    std::vector<InflateJob> slow;
+    std::vector<uint32_t> slow_idx;
+    for (uint32_t i = 0; i < count; i++) {
+        if (settled[i]) continue;
+        InflateJob j{};
+        j.in_off = in_off[i];
+        j.in_len = hdrs[i].status != 0 ? 0 : in_len[i];     // (header failed: nothing to decode)
+        j.start_bit = hdrs[i].deflate_off * 8;
+        j.out_cap = ~0ull;
+        j.flags = JOB_COUNT_ONLY;
+        slow.push_back(j);
+        slow_idx.push_back(i);
+    }
+    std::vector<InflateResult> sres;
+    if ((rc = run_jobs(c, d_in, nullptr, slow, sres))) return rc;
+    for (size_t q = 0; q < slow.size(); q++) res[slow_idx[q]] = sres[q];
+    std::vector<HuffProbe> probes;
+    std::vector<uint32_t> probe_idx;
+    for (size_t q = 0; q < slow.size(); q++)
+        if (huff_verdict(sres[q])) { probes.push_back(HuffProbe{slow[q].in_off, slow[q].in_len, sres[q]}); probe_idx.push_back(slow_idx[q]); }
+    std::vector<uint64_t> probe_used;
+    if ((rc = huff_consumed(c, d_in, probes, probe_used))) return rc;
+    std::vector<uint64_t> huff_used(count, ~0ull);
+    for (size_t q = 0; q < probes.size(); q++) huff_used[probe_idx[q]] = probe_used[q];
+    c->phase("serial");
+    if (c->diag.debug) fprintf(stderr, "[lfx] batch size: %zu streams walked (%llu blocks), %zu through the exact path\n", wj.size(),
+                               (unsigned long long)walk_blocks, slow.size());
+    // ---- the trailer's presence and `consumed` (verify_trailers_kernel without the checksum comparison)
+    int worst = LFX_OK;
+    for (uint32_t i = 0; i < count; i++) {
+        InflateResult &r = res[i];
+        const DecHeader &h = hdrs[i];
+        const uint64_t n = in_len[i];
+        uint64_t used = h.deflate_off;
+        if (h.status != 0) { r.status = h.status; r.err = h.err; r.a0 = h.a0; r.a1 = h.a1; r.out_len = 0; }
+        else {
+            used = std::min<uint64_t>((r.end_bit + 7) >> 3, n);
+            if (huff_used[i] != ~0ull) used = huff_used[i];
+            if (r.status == 0 && format != LFX_DEFLATE) {
+                const uint64_t need = format == LFX_GZIP ? 8 : 4;
+                if (n - used < need) { r.status = 2; r.err = ERR_EOF; used = n; }
+                else used += need;
+            }
+        }
+        if (out_len) out_len[i] = r.out_len;
+        if (consumed) consumed[i] = used;
+        const int s = map_status(r.status);
+        if (status) status[i] = s;
+        if (s != LFX_OK && worst == LFX_OK) { worst = s; c->set_error(format_error(r.err, r.a0, r.a1)); }
+    }
+    c->phase("trailers");
+    return LFX_OK;   // per-stream results are in status[]
+} LFX_ABI_CATCH
+
+extern "C" int lfx_decode_members_size_device(lfx_ctx *cc, const void *d_in, uint64_t n, uint64_t *out_len, uint64_t *consumed,
+                                              lfx_member *members, uint32_t max_members, uint32_t *n_members) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    DecodeOutcome oc;
+    std::vector<lfx_member> got;
+    int rc = size_members(c, (const uint8_t *)d_in, n, oc, got);
+    if (rc) return rc;
+    if (out_len) *out_len = oc.out_len;
+    if (consumed) *consumed = oc.consumed;
+    if (n_members) *n_members = (uint32_t)std::min<size_t>(got.size(), 0xFFFFFFFFu);
+    if (members) memcpy(members, got.data(), sizeof(lfx_member) * std::min<size_t>(got.size(), max_members));
+    if (oc.status != LFX_OK) c->set_error(oc.msg);
+    return oc.status;
+} LFX_ABI_CATCH
+
+extern "C" int lfx_decode_members_size_host(lfx_ctx *cc, const void *in, uint64_t n, uint64_t *out_len, uint64_t *consumed,
+                                            lfx_member *members, uint32_t max_members, uint32_t *n_members) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    if (int rc = size_stage_in(c, in, n)) return rc;
+    const int rc = lfx_decode_members_size_device(cc, c->d_io_in.p, n, out_len, consumed, members, max_members, n_members);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+} LFX_ABI_CATCH
+
+// ------------------------------------------------------------------------------------------------
 // seek index: the decode of lfx_decode_device (LFX_DEC_MULTI: of lfx_decode_members_device), unchanged, with
 // Ctx::idx set — its chains record their block starts and the lanes of their large blocks — then the index from those
 // candidates (lfx_index.hip)

@@ -120,7 +120,27 @@ struct BlkEmit {
     uint64_t temp_off;   // ... at temp + temp_off + lane * cap
     uint32_t cap, _pad;
 };
-constexpr uint32_t MAX_FREE_UNITS = 64;   // marker units per block (a schedule-S1 stream is ONE block)
+// the block walker of the size calls (blk_walk_size_kernel): one job = one workgroup that follows a stream's blocks on the device
+enum : uint32_t { WALK_FINAL = 0,    // walked to the end of the BFINAL block
+                  WALK_STOP = 1,     // a block ended at or behind stop_bit (no BFINAL block so far)
+                  WALK_STUCK = 2 };  // the block at stuck_bit is not one the walker settles (the exact path decides what it is)
+struct WalkJob {
+    uint64_t start_bit;  // header bit of the first block (relative to `in`)
+    uint64_t end_bit;    // the stream's end: a block that runs past it is not settled
+    uint64_t stop_bit;   // != 0: the walk ends behind the first block that ends at or behind this bit (the next candidate)
+};
+struct WalkResult {
+    uint64_t end_bit;    // bit behind the last settled block
+    uint64_t n_out;      // bytes the settled blocks produce
+    uint64_t stuck_bit, stuck_out;   // header bit of the last block the walk stood at, and the bytes produced in front of it
+    int64_t reach;       // smallest (bytes produced so far - distance) over the matches of the settled blocks, relative to the
+                         //   job's first output byte; INT64_MAX: no match.  reach + (bytes in front of the job) < 0: the decode
+                         //   fails there with "Too long backword reference"
+    uint32_t status, nblocks;
+};
+int launch_blk_walk_size(hipStream_t st, const uint8_t *in, uint64_t nbytes, const WalkJob *jobs, uint32_t njobs,
+                         WalkResult *results, bool small_blocks);   // small_blocks: 256 lanes a job instead of 1024
+constexpr uint32_t MAX_FREE_UNITS = 64;  // marker units per block (a schedule-S1 stream is ONE block)
 struct BlkUnits {
     uint32_t n;          // independent units of the block (no back-reference crosses a cut)
     uint32_t code0[9];   // unit u covers codes [code0[u], code0[u+1]) of the block

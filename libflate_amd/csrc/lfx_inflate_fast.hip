@@ -1164,6 +1164,188 @@ __global__ __launch_bounds__(NT, STORE ? 4 : 8) void blk_scan_kernel(const uint8
 }
 
 // ------------------------------------------------------------------------------------------------
+// The block walker of the size calls (lfx_decode_size_*): one workgroup follows the blocks of ONE stream (a
+// member, or the blocks from a finder candidate up to the next one) on the device — header, count-only scan, next header —
+// in one launch, and produces no output.  A compressed block is scanned a WINDOW of NT slices at a time with the lane
+// scheme of blk_scan_kernel (speculative starts, exits chained from the exact first lane until nothing changes); a window
+// without EndOfBlock is "open": the next window starts at the exit of its last lane with the same tables, so a block of any
+// length is walked with bounded state.  Besides the byte counts every lane tracks how far its matches reach in front of its
+// slice; the workgroup's minimum over the walk (relative to the job's first output byte) lets the host see a "Too long
+// backword reference" without the bytes.  Whatever the walker cannot settle — an undecodable header or code, a block that
+// runs past the range, lanes that do not converge — ends the walk with WALK_STUCK and the position of the block it stood at;
+// the host then takes the exact serial kernel (count-only) from the stream's start.
+// The symbol loop: lane_decode_fifo<false> plus the reach of the matches (the scan kernel's own loop is left as it is).
+__device__ __forceinline__ int lane_count_reach(const FastTabs &T, const uint8_t *in, uint64_t nbytes, uint64_t start,
+                                                uint64_t limit, uint32_t &nout, int32_t &reach_rel, uint64_t &endpos) {
+    FastBits b;
+    b.init(in, nbytes, start);
+    const uint64_t span = limit > start ? limit - start : 0;
+    const uint32_t lim = span > 0xFFFFFF00ull ? 0xFFFFFF00u : (uint32_t)span;
+    int ret = 0;
+    uint32_t no = 0;
+    int32_t rr = INT32_MAX;          // smallest (bytes produced by this call - distance) over the matches
+    while (b.used < lim && ret == 0) {
+        bool act = b.qn >= 2;
+        while (act) {
+            b.append();
+            uint32_t e = T.lit[(uint32_t)b.buf & ((1u << LIT_BITS) - 1)];
+            if (__builtin_expect((e & 15) == 0, 0))
+                e = e == E_LONG ? long_lookup(T.lit_count, T.lit_sorted, T.lit_info, 286, b.buf) : 0;
+            const bool bad1 = e == 0;
+            const uint32_t kind = (e >> 4) & 3;
+            const bool eob = kind == K_EOB;
+            const bool is_match = kind == K_LEN;
+            const uint32_t w = e & 15, eb = (e >> 6) & 31;
+            const uint32_t val = (e >> 16) + (((uint32_t)(b.buf >> w)) & ((1u << eb) - 1));
+            b.skip(w + eb);
+            b.append();
+            uint32_t d = T.dist[(uint32_t)b.buf & ((1u << DIST_BITS) - 1)];
+            if (__builtin_expect(is_match && (d & 15) == 0, 0))
+                d = d == E_LONG ? long_lookup(T.dist_count, T.dist_sorted, T.dist_info, 30, b.buf) : 0;
+            const bool bad2 = is_match && d == 0;
+            const bool ok = !(bad1 || eob || bad2);
+            const bool okm = ok && is_match;
+            const uint32_t dw = d & 15, db = (d >> 6) & 31;
+            const uint32_t distance = (d >> 16) + (((uint32_t)(b.buf >> dw)) & ((1u << db) - 1));
+            b.skip(okm ? dw + db : 0u);
+            ret = (bad1 || bad2) ? 2 : eob ? 1 : 0;
+            const int32_t rel = (int32_t)no - (int32_t)distance;
+            rr = okm && rel < rr ? rel : rr;
+            no += ok ? (is_match ? val : 1u) : 0u;
+            act = ok && b.qn >= 2 && b.used < lim;
+        }
+        if (ret == 0 && b.used < lim && b.qn < 2) b.reload();
+    }
+    nout = no;
+    reach_rel = rr;
+    endpos = start + b.used;
+    return ret;
+}
+
+constexpr uint64_t WALK_SLICE_MAX = 4096;     // bits of a lane's slice at most: a window is NT * 4096 bits (NT = 1024: 4 Mbit, the piece size of the decode)
+template <int NT>
+__global__ __launch_bounds__(NT) void blk_walk_size_kernel(const uint8_t *__restrict__ in, uint64_t nbytes,
+                                                          const WalkJob *__restrict__ jobs, WalkResult *__restrict__ results) {
+    __shared__ FastTabs T;
+    __shared__ __attribute__((aligned(4))) uint8_t lens[640];
+    __shared__ uint32_t hdr[8];
+    __shared__ uint64_t hdr64[2];
+    __shared__ uint64_t s_start[NT + 1];
+    __shared__ uint32_t s_flag[NT];
+    __shared__ uint64_t s_exit[NT];
+    __shared__ uint64_t s_sum[NT / 64];
+    __shared__ long long s_min[NT / 64];
+    __shared__ uint32_t s_eob;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const WalkJob job = jobs[blockIdx.x];
+    // the range: nothing behind end_bits belongs to the stream, and no load goes behind the buffer
+    const uint64_t end_bits = job.end_bit < nbytes * 8 ? job.end_bit : nbytes * 8;
+    const uint64_t nb = (end_bits + 7) >> 3;
+    uint64_t cur = job.start_bit, produced = 0;
+    uint64_t blk_bit = cur, blk_out = 0;
+    long long reach = INT64_MAX;
+    uint32_t nblocks = 0, status = WALK_STUCK;
+    for (;;) {
+        blk_bit = cur; blk_out = produced;
+        if (cur + 3 > end_bits) break;
+        parse_header<NT>(in, nb, cur, T, lens, hdr, hdr64, tid);
+        const uint32_t btype = hdr[0], bfinal = hdr[1], hbad = hdr[2];
+        const uint64_t d0 = hdr64[0];
+        if (hbad) break;
+        uint64_t blk_end = 0;
+        if (btype == 0) {
+            // stored block (decode.rs:81-111): LEN / NLEN after byte alignment; every lane reads the same four bytes
+            const uint64_t byte = (d0 + 7) >> 3;
+            if (byte + 4 > nb) break;
+            const uint32_t len = in[byte] | in[byte + 1] << 8, nlen = in[byte + 2] | in[byte + 3] << 8;
+            if (((~len) & 0xFFFF) != nlen || byte + 4 + len > nb) break;
+            produced += len;
+            blk_end = (byte + 4 + len) * 8;
+        } else {
+            uint64_t w0 = d0;
+            bool closed = false, fail = false;
+            while (!closed && !fail) {
+                // one window [w0, e): w0 is a known symbol boundary
+                uint64_t guess = job.stop_bit > w0 && job.stop_bit < end_bits ? job.stop_bit : end_bits;
+                uint64_t slice = (guess - w0 + NT - 1) / NT;
+                slice = slice < 128 ? 128 : slice > WALK_SLICE_MAX ? WALK_SLICE_MAX : slice;   // (>= 128: a symbol of <= 48 bits never skips a slice)
+                uint64_t e = w0 + (uint64_t)NT * slice;
+                if (e > end_bits) e = end_bits;
+                if (e < w0 + 1) e = w0 + 1;
+                const uint32_t nl = (uint32_t)((e - w0 + slice - 1) / slice);      // lanes in use (1 .. NT)
+                const uint64_t my_bound = w0 + (uint64_t)(tid + 1) * slice;
+                s_start[tid] = tid < nl ? w0 + (uint64_t)tid * slice : ~0ull;
+                if (tid == 0) { s_start[NT] = ~0ull; s_eob = 0xFFFFFFFFu; }
+                __syncthreads();
+                uint32_t rounds = 0, no = 0, flag = 4;
+                int32_t rr = INT32_MAX;
+                uint64_t exitpos = ~0ull, decoded_from = ~0ull;
+                for (;;) {
+                    const uint64_t st = s_start[tid];
+                    if (tid < nl && st != ~0ull) {
+                        if (st != decoded_from) {
+                            // (the last lane stops at the first symbol boundary at or behind e: the next window starts exactly there)
+                            const int r = lane_count_reach(T, in, nb, st, tid + 1 == nl ? e : my_bound, no, rr, exitpos);
+                            flag = r == 1 ? 1 : r == 2 ? 2 : 0;
+                            decoded_from = st;
+                        }
+                    } else flag = 4;
+                    s_flag[tid] = flag; s_exit[tid] = exitpos;
+                    __syncthreads();
+                    bool changed = false;
+                    if (tid + 1 < nl && flag == 0 && s_start[tid + 1] != exitpos) { s_start[tid + 1] = exitpos; changed = true; }
+                    rounds++;
+                    const int any = __syncthreads_or(changed ? 1 : 0);
+                    if (!any || rounds >= 64) break;
+                }
+                if (rounds >= 64) { fail = true; break; }
+                if (tid < nl && s_flag[tid] != 0) atomicMin(&s_eob, tid);      // first flagged lane of the chain
+                __syncthreads();
+                uint32_t eobl = s_eob;
+                if (eobl == 0xFFFFFFFFu) eobl = nl - 1;                        // an open window: all its lanes count
+                else if (s_flag[eobl] != 1) { fail = true; break; }            // an undecodable code on the proven chain
+                else closed = true;
+                // bytes of the window (lanes <= eobl) and the smallest byte position a match reads, relative to the job's output
+                const uint64_t myno = tid <= eobl ? no : 0;
+                uint64_t y = myno;
+                for (int o = 1; o < 64; o <<= 1) {
+                    const uint64_t c = __shfl_up(y, o);
+                    if ((int)lane >= o) y += c;
+                }
+                if (lane == 63) s_sum[wave] = y;
+                __syncthreads();
+                uint64_t py = 0, tot = 0;
+                for (uint32_t w = 0; w < NT / 64; ++w) { const uint64_t s = s_sum[w]; py += w < wave ? s : 0; tot += s; }
+                long long m = tid <= eobl && rr != INT32_MAX ? (long long)(produced + py + y - myno) + (long long)rr : INT64_MAX;
+                for (int o = 32; o; o >>= 1) { const long long c = __shfl_xor(m, o); m = c < m ? c : m; }
+                if (lane == 0) s_min[wave] = m;
+                const uint64_t last_exit = s_exit[eobl];
+                __syncthreads();
+                for (uint32_t w = 0; w < NT / 64; ++w) { const long long c = s_min[w]; reach = c < reach ? c : reach; }
+                produced += tot;
+                if (closed) blk_end = last_exit;
+                else if (last_exit <= w0 || last_exit >= end_bits) fail = true;   // (no EndOfBlock inside the range)
+                else w0 = last_exit;
+                __syncthreads();             // (s_start / s_eob / s_sum are written again by the next window)
+            }
+            if (fail) { produced = blk_out; break; }
+        }
+        if (blk_end <= cur || blk_end > end_bits) { produced = blk_out; break; }
+        nblocks++;
+        cur = blk_end;
+        if (bfinal) { status = WALK_FINAL; break; }
+        if (job.stop_bit && cur >= job.stop_bit) { status = WALK_STOP; break; }
+        __syncthreads();                     // (hdr / lens / T belong to the next header from here on)
+    }
+    if (tid == 0) {
+        WalkResult r;
+        r.end_bit = cur; r.n_out = produced; r.stuck_bit = blk_bit; r.stuck_out = blk_out;
+        r.reach = reach; r.status = status; r.nblocks = nblocks;
+        results[blockIdx.x] = r;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K2: validated lanes decode their slices into the code array; the block is then cut into units
 // that no back-reference crosses (reference-made blocks fall apart at every LZ77 chunk boundary,
 // default.rs:73) so that K3 can materialise them concurrently.
@@ -2457,6 +2639,16 @@ int launch_blk_scan(hipStream_t st, const uint8_t *in, uint64_t nbytes, const Bl
     else
         hipLaunchKernelGGL((blk_scan_kernel<false, SCAN_THREADS>), dim3(njobs), dim3(SCAN_THREADS), 0, st, in, nbytes, jobs, infos, lanes,
                            (FastTabs *)tabs, (uint32_t *)nullptr, (BlkLanesX *)nullptr);
+    LFX_LAUNCH_CHECK();
+    return 0;
+}
+int launch_blk_walk_size(hipStream_t st, const uint8_t *in, uint64_t nbytes, const WalkJob *jobs, uint32_t njobs,
+                         WalkResult *results, bool small_blocks) {
+    if (!njobs) return 0;
+    if (small_blocks)
+        hipLaunchKernelGGL((blk_walk_size_kernel<SCAN_SMALL>), dim3(njobs), dim3(SCAN_SMALL), 0, st, in, nbytes, jobs, results);
+    else
+        hipLaunchKernelGGL((blk_walk_size_kernel<SCAN_THREADS>), dim3(njobs), dim3(SCAN_THREADS), 0, st, in, nbytes, jobs, results);
     LFX_LAUNCH_CHECK();
     return 0;
 }

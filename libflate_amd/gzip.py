@@ -136,6 +136,17 @@ def decode_members(data, context=None):
     return out, members
 
 
+def list_members(data, context=None):
+    """`gzip -l` over concatenated members (BGZF, `cat a.gz b.gz`): the member table decode_members would return, without
+    decoding (lfx_decode_members_size_host; the CRCs are not checked) → [(in_off, in_len, out_off, out_len)].  Raises
+    StreamError where the walk fails."""
+    ctx = context if context is not None else default_context()
+    rc, _out_len, _used, members, msg = ctx.decode_members_size_host(data)
+    if rc != _ffi.OK:
+        raise StreamError(rc, msg)
+    return members
+
+
 def encode_members(data, member_size=1 << 20, bgzf=False, options=None, context=None):
     """`data` as gzip members of member_size input bytes each, lying back to back: what decode_members, zcat and Python's gzip
     read, and with bgzf=True (member_size at most 65505; bgzip's own is _ffi.BGZF_MEMBER_SIZE = 65280) a BGZF file with its
