@@ -237,12 +237,8 @@ void Diag::read() {
     if (const char *rc7 = getenv("LFX_R7_CAP")) r7_cap = atoi(rc7);
     no_serial = on("LFX_NO_SERIAL");
     batch_serial = on("LFX_BATCH_SERIAL");
-    no_markers = on("LFX_NO_MARKERS");
     no_pieces = on("LFX_NO_PIECES");
     no_final_cand = on("LFX_NO_FINAL_CAND");
-    window_chain = on("LFX_WINDOW_CHAIN");
-    if (const char *fs = getenv("LFX_FREE_SHIFT")) free_shift = atoi(fs);
-    if (const char *pm = getenv("LFX_POCR_MAX")) pocr_max = atoi(pm);
     if (const char *eb = getenv("LFX_ENC_BATCH_MB")) enc_batch_mb = atoi(eb);
     two_pass = on("LFX_TWO_PASS");
     hist_separate = on("LFX_HIST_SEPARATE");

@@ -32,11 +32,8 @@ struct Diag {
     int match_parts = 1;         // LFX_MATCH_PARTS: lfx_match7 in up to four launches, each part's resolver on the side stream
     bool no_serial = false;      // LFX_NO_SERIAL: the serial fallback of the single-stream decoder is an error
     bool batch_serial = false;   // LFX_BATCH_SERIAL: every stream of a batch through the serial kernel
-    bool no_markers = false;     // LFX_NO_MARKERS
     bool no_pieces = false;      // LFX_NO_PIECES
     bool no_final_cand = false;  // LFX_NO_FINAL_CAND: the finder reports no BFINAL header at all (the chain walk scans the last block on demand)
-    bool window_chain = false;   // LFX_WINDOW_CHAIN
-    int free_shift = -1;         // LFX_FREE_SHIFT
     bool no_small_scan = false;  // LFX_NO_SMALL_SCAN: 1024 slices a block also for small blocks (round 5's geometry)
     bool two_pass = false;       // LFX_TWO_PASS: every block through blk_emit_kernel (no storing scan)
     bool no_pin_slots = false;   // LFX_NO_PIN_SLOTS: the decode's small transfers as plain pageable copies (the path of a full arena)
@@ -44,7 +41,6 @@ struct Diag {
     bool hist_separate = false;  // LFX_HIST_SEPARATE: the blocks' symbol counts by histogram_kernel (round 5) instead of inside parse_emit
     bool store_tight = false;    // LFX_STORE_TIGHT: the storing scan's regions sized for 16 bits a code (tests: lanes overflow, blocks fall back)
     int enc_batch_mb = 0;        // LFX_ENC_BATCH_MB: the stream encoder encodes closed blocks once so many MiB wait (0: the default, 8)
-    int pocr_max = 100;          // LFX_POCR_MAX: most candidate ranges the decoder scans in pieces at once
     void read();
 };
 

@@ -544,3 +544,19 @@ def test_planner_write_repeat_equals_the_loop_of_writes(tmp_path):
     subprocess.run([gxx, "-O2", "-std=c++17", "-o", exe, os.path.join(root, "tests", "c", "plan_repeat.cpp")], check=True)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
     assert "plan_repeat ok: 20000 cases" in out
+
+
+def test_decode_stage_arithmetic_tiles_ranges_and_regions(tmp_path):
+    """The member decode's host arithmetic (libflate_amd/csrc/lfx_stages.h: no HIP call, a plain host compiler builds it).
+    tests/c/plan_stages.cpp, over 20000 seeded random ranges: the pieces of a range tile it exactly — no gap, no overlap,
+    interior cuts a multiple of 64 bits behind its start — their number is what the split formula gives, alternative scan
+    jobs widen their candidate's range, and the storing scan's lane regions never overlap."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "plan_stages")
+    subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "c", "plan_stages.cpp")], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "plan_stages ok: 20000 cases" in out.stdout, out.stdout[-400:]
