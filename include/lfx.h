@@ -223,6 +223,66 @@ int lfx_encode_members_host(lfx_ctx *c, const lfx_encode_opts *o, const lfx_sche
  * offset); member 0 is implicit.  *len = its size (also when cap is too small: LFX_E_NOSPACE; buf may then be NULL). */
 int lfx_members_gzi(const lfx_member *members, uint32_t n_members, void *buf, uint64_t cap, uint64_t *len);
 
+/* ---- BGZF reads by virtual offset: what htslib's bgzf_seek + bgzf_read serve, batched, with no index ------
+ * .bai / .tbi / .csi / .gzi address a BGZF file by virtual offset, coffset << 16 | uoffset: the byte at which a block starts
+ * in the file, and a byte inside that block's output.  Every block is a gzip member of at most 64 KiB that names its own length
+ * (BSIZE), so a read hops from block to block and decodes only the blocks it covers.  `count` reads in one call; reads and res
+ * are HOST arrays; d_in holds file bytes [in_base, in_base + n) (as in lfx_index_read_device).
+ *  1. Block form.  A block is accepted in htslib's form only: the 18 bytes 1f 8b 08 04, six bytes (mtime, xfl, os), 06 00 42 43
+ *     02 00, BSIZE; BSIZE + 1 >= 26 bytes in all, the last four of them ISIZE <= 65536.  Anything else at a position the walk
+ *     reaches (a voff that points into the middle of a block) is LFX_E_INVALID_DATA for that read; the message names the coffset.
+ *  2. Walk.  A read starts in the block at voff >> 16, at byte voff & 0xffff of its output, and continues through the blocks
+ *     that follow.  Empty blocks contribute nothing and are passed (the 28-byte end-of-file marker, also in the middle of
+ *     `cat a b`).  It ends, with LFX_OK, at the first of: len bytes; end_voff (compared as coffset, then uoffset: the block at
+ *     end_voff's coffset is not even looked at when nothing of it is wanted); the bytes held ending exactly at a block boundary
+ *     (a short read).  end_voff <= voff: 0 bytes, LFX_OK, nothing is looked at.
+ *  3. Start.  coffset outside [in_base, in_base + n]: LFX_E_ARG.  coffset == in_base + n: 0 bytes, LFX_OK, next_voff = voff.
+ *     uoffset == ISIZE is a valid start (the read continues in the next block); uoffset > ISIZE: LFX_E_ARG.  The start block is
+ *     checked (rules 1, 4) also when len == 0.
+ *  4. Cut-off block.  A block that starts inside the bytes held but does not end inside them (or whose 18 header bytes do not):
+ *     LFX_E_UNEXPECTED_EOF, out_len = the bytes in front of it, next_voff = that block's start (in the start block: voff) — the
+ *     caller fetches more of the file and goes on from there.
+ *  5. Verification.  Every block that contributes a byte is decoded whole: its CRC-32 is verified, its decoded length must be
+ *     ISIZE and its DEFLATE stream must end 8 bytes in front of BSIZE + 1.  A block that fails makes every read that touches
+ *     it LFX_E_INVALID_DATA with out_len = the bytes in front of that block, n_blocks = the blocks in front of it and next_voff
+ *     = the first byte wanted of it; reads that do not touch it are unaffected.
+ *  6. next_voff = coffset << 16 | uoffset of the first byte not delivered; where that is the end of a block, the start of the next
+ *     block with uoffset 0 (bgzf_tell).
+ *  7. Exactly d_out[out_off, out_off + out_len) is written for each read and nothing else.  Output ranges [out_off, out_off +
+ *     len) that overlap: LFX_E_ARG for the call, res is not written.
+ *  8. The return value is LFX_OK when every read is, otherwise the first failing read's status, lfx_ctx_last_error its message.
+ *     res is written all at once, by a call that settled every read.  A call refused as a whole — rule 7, rule 11, bytes held
+ *     that end behind coffset 2^48 (LFX_E_ARG), a device error, no memory — leaves every byte of res as the caller set it,
+ *     which is how a caller tells such a refusal from a read's own LFX_E_ARG.
+ *  9. A block covered by several reads is decoded once; *blocks_decoded (may be NULL) = the distinct blocks decoded.
+ * 10. Size mode: d_out == NULL (out == NULL) walks and decodes nothing — out_len, next_voff, n_blocks and status come from the
+ *     headers and ISIZEs alone; rule 5 is the only rule skipped, len still bounds out_len; *blocks_decoded = 0.
+ * 11. A NULL context: LFX_E_DEVICE, nothing written.  count == 0: LFX_OK.  NULL reads or res with count > 0: LFX_E_ARG.
+ * lfx_bgzf_read_host does not upload the file: the walk runs on the CPU over `in`, only the distinct covered blocks cross the
+ * link; its results equal the device call's field for field. */
+typedef struct lfx_bgzf_read {
+    uint64_t voff;      /* first byte of the read: coffset << 16 | uoffset (coffset relative to byte 0 of the file) */
+    uint64_t end_voff;  /* the read stops in front of this position; UINT64_MAX: no such bound */
+    uint64_t len;       /* bytes delivered at most = the size of its output range */
+    uint64_t out_off;   /* the bytes go to d_out + out_off */
+} lfx_bgzf_read;        /* 32 bytes */
+typedef struct lfx_bgzf_result {
+    uint64_t out_len;   /* bytes delivered (size mode: bytes a read would deliver) */
+    uint64_t next_voff; /* position behind the last byte delivered (bgzf_tell) */
+    int32_t  status;    /* LFX_* of this read */
+    uint32_t n_blocks;  /* blocks that contributed at least one byte */
+} lfx_bgzf_result;      /* 24 bytes */
+int lfx_bgzf_read_device(lfx_ctx *c, const void *d_in, uint64_t in_base, uint64_t n, uint32_t count,
+                         const lfx_bgzf_read *reads, void *d_out, lfx_bgzf_result *res, uint64_t *blocks_decoded);
+int lfx_bgzf_read_host(lfx_ctx *c, const void *in, uint64_t in_base, uint64_t n, uint32_t count,
+                       const lfx_bgzf_read *reads, void *out, lfx_bgzf_result *res, uint64_t *blocks_decoded);
+/* host only: uncompressed offset -> virtual offset through a member table (lfx_encode_members_*: out_off = compressed,
+ * in_off = uncompressed; `swapped` != 0 for the table of lfx_decode_members_* / _size_*, where the roles are exchanged).  A
+ * binary search over a table in file order: uoff at a member boundary is the later member with uoffset 0, uoff equal to the
+ * total the position behind the last member (an empty table: 0), uoff behind that LFX_E_ARG — as is a position more than 65535
+ * bytes into its member, which no virtual offset names. */
+int lfx_members_voffset(const lfx_member *members, uint32_t n_members, int swapped, uint64_t uoff, uint64_t *voff);
+
 /* ---- seek index: random-access reads of a DEFLATE / zlib / gzip stream ---------------------------------
  * One decode builds the index: a list of access points (a bit of the input where decoding can start, the output byte it
  * produces first, the 32 KiB of output in front of it).  A read of output bytes [off, off + len) decodes only from the access

@@ -19,6 +19,7 @@ DEC_MULTI = 1
 DEC_NONBLOCKING = 2
 MEMBERS_BGZF = 1
 BGZF_MEMBER_SIZE = 65280      # bgzip's own slice; 65505 is the most a BGZF member holds
+VOFF_NONE = 2**64 - 1         # lfx_bgzf_read.end_voff: no such bound
 
 # every symbol include/lfx.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -38,7 +39,7 @@ EXPORTS = [
     "lfx_index_export", "lfx_index_import", "lfx_index_check", "lfx_index_free", "lfx_encode_index_device",
     "lfx_encode_members_bound", "lfx_encode_members_device", "lfx_encode_members_host", "lfx_members_gzi",
     "lfx_decode_size_device", "lfx_decode_size_host", "lfx_decode_batch_size_device", "lfx_decode_members_size_device",
-    "lfx_decode_members_size_host",
+    "lfx_decode_members_size_host", "lfx_bgzf_read_device", "lfx_bgzf_read_host", "lfx_members_voffset",
 ]
 
 
@@ -68,6 +69,16 @@ class BlkTuple(C.Structure):
 class Member(C.Structure):
     """lfx_member: one verified member of a multi-member gzip input (32 bytes)"""
     _fields_ = [("in_off", C.c_uint64), ("in_len", C.c_uint64), ("out_off", C.c_uint64), ("out_len", C.c_uint64)]
+
+
+class BgzfRead(C.Structure):
+    """lfx_bgzf_read: one read of a BGZF file by virtual offset (32 bytes)"""
+    _fields_ = [("voff", C.c_uint64), ("end_voff", C.c_uint64), ("len", C.c_uint64), ("out_off", C.c_uint64)]
+
+
+class BgzfResult(C.Structure):
+    """lfx_bgzf_result: what one read delivered (24 bytes)"""
+    _fields_ = [("out_len", C.c_uint64), ("next_voff", C.c_uint64), ("status", C.c_int32), ("n_blocks", C.c_uint32)]
 
 
 class IndexPoint(C.Structure):
@@ -195,6 +206,9 @@ def lib():
         f.argtypes = [vp, C.POINTER(EncodeOpts), C.POINTER(Schedule), u64, u32, vp, u64, vp, u64, C.POINTER(u64),
                       C.POINTER(Member), u32, C.POINTER(u32)]
     L.lfx_members_gzi.argtypes = [C.POINTER(Member), u32, vp, u64, C.POINTER(u64)]
+    for f in (L.lfx_bgzf_read_device, L.lfx_bgzf_read_host):
+        f.argtypes = [vp, vp, u64, u64, u32, C.POINTER(BgzfRead), vp, C.POINTER(BgzfResult), C.POINTER(u64)]
+    L.lfx_members_voffset.argtypes = [C.POINTER(Member), u32, i32, u64, C.POINTER(u64)]
     L.lfx_decode_index_device.argtypes = [vp, i32, u32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), u64, C.POINTER(vp)]
     L.lfx_encode_index_device.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, u64, vp, u64, C.POINTER(u64), u64,
                                           C.POINTER(vp)]
@@ -323,6 +337,20 @@ def members_to_gzi(members):
     if rc:
         raise LfxError(rc, "lfx_members_gzi")
     return buf.raw[:need.value]
+
+
+def members_voffset(members, uoff, swapped=False):
+    """the virtual offset (coffset << 16 | uoffset) of uncompressed byte `uoff` through a member table [(in_off, in_len, out_off,
+    out_len)] — an encode_members table, or with swapped=True a decode_members / list_members one (lfx_members_voffset)"""
+    members = list(members)
+    table = (Member * max(len(members), 1))()
+    for i, m in enumerate(members):
+        table[i].in_off, table[i].in_len, table[i].out_off, table[i].out_len = m
+    voff = C.c_uint64(0)
+    rc = lib().lfx_members_voffset(table, len(members), 1 if swapped else 0, uoff, C.byref(voff))
+    if rc:
+        raise LfxError(rc, "lfx_members_voffset: offset %d has no virtual offset in this table" % uoff)
+    return voff.value
 
 
 def make_schedule(write_size=0, writes=None):

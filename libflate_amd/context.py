@@ -170,6 +170,50 @@ class Context:
                 continue
             return rc, out.raw[:ol], used, members, msg
 
+    # ---- BGZF reads by virtual offset (lfx_bgzf_read_*) ---------------------------------------------
+    @staticmethod
+    def _bgzf_reads(reads):
+        """reads: (voff, length, end_voff, out_off) each → the lfx_bgzf_read array"""
+        k = len(reads)
+        arr = (_ffi.BgzfRead * max(k, 1))()
+        for i, (voff, length, end_voff, out_off) in enumerate(reads):
+            arr[i].voff, arr[i].len, arr[i].end_voff, arr[i].out_off = voff, length, end_voff, out_off
+        return arr
+
+    def _bgzf_call(self, fn, src, in_base, n, reads, arr, dst):
+        k = len(reads)
+        res = (_ffi.BgzfResult * max(k, 1))()
+        res[0].status = unwritten = 0x7fffffff          # (no LFX_* code)
+        decoded = C.c_uint64(0)
+        rc = fn(self._h, src, in_base, n, k, arr, dst, res, C.byref(decoded))
+        # LFX_E_ARG is a read's own verdict (a coffset outside the bytes held) or a refusal of the whole call; res is written
+        # all at once and a refused call leaves it as it was (include/lfx.h, rule 8)
+        if rc in (_ffi.E_DEVICE, _ffi.E_OOM) or (rc == _ffi.E_ARG and res[0].status == unwritten):
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        out = [(r.out_len, r.next_voff, r.status, r.n_blocks) for r in res[:k]]
+        return rc, out, decoded.value, self.last_error() if rc else ""
+
+    def bgzf_read_device(self, d_in_ptr, in_base, n, reads, d_out_ptr):
+        """`reads` of a BGZF file by virtual offset (lfx_bgzf_read_device): d_in_ptr holds file bytes [in_base, in_base + n),
+        reads = [(voff, length, end_voff, out_off)], the bytes go to d_out_ptr + out_off (d_out_ptr = None: size mode)
+        → (rc, [(out_len, next_voff, status, n_blocks)], blocks_decoded, None, message)"""
+        rc, out, decoded, msg = self._bgzf_call(_ffi.lib().lfx_bgzf_read_device, d_in_ptr, in_base, n, reads, self._bgzf_reads(reads),
+                                                d_out_ptr)
+        return rc, out, decoded, None, msg
+
+    def bgzf_read_host(self, data, reads, in_base=0, sizes_only=False):
+        """the same on host bytes (lfx_bgzf_read_host; only the covered blocks are uploaded): reads = [(voff, length)] or [(voff,
+        length, end_voff)] → (rc, [(out_len, next_voff, status, n_blocks)], blocks_decoded, [bytes per read] or None, message)"""
+        data = bytes(data)
+        full, at = [], 0
+        for r in reads:
+            full.append((r[0], r[1], r[2] if len(r) > 2 else _ffi.VOFF_NONE, at))
+            at += r[1]
+        buf = None if sizes_only else C.create_string_buffer(max(at, 1))
+        rc, out, decoded, msg = self._bgzf_call(_ffi.lib().lfx_bgzf_read_host, data, in_base, len(data), full, self._bgzf_reads(full), buf)
+        got = None if sizes_only else [buf.raw[f[3]:f[3] + o[0]] for f, o in zip(full, out)]
+        return rc, out, decoded, got, msg
+
     def _raise_fatal(self, rc):
         if rc in (_ffi.E_DEVICE, _ffi.E_OOM, _ffi.E_ARG):
             raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())

@@ -256,7 +256,7 @@ void Ctx::phase(const char *name) {
         const char *const *pr = pair[timing_on - 2];
         if (strcmp(name, pr[0]) != 0 && strcmp(name, pr[1]) != 0) return;
     }
-    if (n_ev >= 17) return;
+    if (n_ev >= MAX_EV) return;
     if (!ev[n_ev]) (void)hipEventCreate(&ev[n_ev]);
     (void)hipEventRecord(ev[n_ev], stream);
     snprintf(ev_name[n_ev], sizeof ev_name[n_ev], "%s", name);

@@ -90,13 +90,17 @@ struct Ctx {
     // seek index (lfx_index.hip): copy tasks, probe results, the read path's staging areas
     DevBuf d_idx_tasks, d_idx_probe, d_idx_stage;
     DevBuf d_idx_enc;                   // lfx_encode_index_device: the candidate kernels' slots and per-tile sums (lfx_index_enc.hip)
+    // BGZF reads by virtual offset (lfx_bgzf.hip): the walk's reads, results and segment list; the gather's tasks; the blocks a
+    // group decodes into (at most 4096 x 64 KiB); the covered blocks of a host call, packed
+    DevBuf d_bgzf_meta, d_bgzf_tasks, d_bgzf_scratch, d_bgzf_pack;
     struct IdxCollect *idx = nullptr;   // while lfx_decode_index_device runs: what the decode records for the index
     struct IdxCollect *idx_enc = nullptr;   // while lfx_encode_index_device runs: the encode leaves its candidates there
     std::vector<DevBuf *> all_bufs() {
         return {&d_chunks, &d_blocks, &d_segs, &d_pwgs, &d_cd, &d_md, &d_codes, &d_ncodes, &d_hist, &d_bc, &d_block_start,
                 &d_tile_bits, &d_tile_start, &d_ck, &d_res, &d_small, &d_hdr, &d_io_in, &d_io_out, &d_vis, &d_segtmp, &d_stage, &d_chunkmap, &d_glnk, &d_ucount,
                 &d_dec_streams, &d_dec_state, &d_dec_tmp, &d_dec_cand, &d_dec_blocks, &d_dec_tabs, &d_dec_sym, &d_dec_win, &d_dec_maps,
-                &d_dec_temp, &d_dec_lanesx, &d_idx_tasks, &d_idx_probe, &d_idx_stage, &d_idx_enc};
+                &d_dec_temp, &d_dec_lanesx, &d_idx_tasks, &d_idx_probe, &d_idx_stage, &d_idx_enc,
+                &d_bgzf_meta, &d_bgzf_tasks, &d_bgzf_scratch, &d_bgzf_pack};
     }
     void *h_res = nullptr;  // pinned, 4 KiB (+ the arena below)
     // Small transfers of the decode paths (job lists up, scan results and counters down) go through page-locked memory: a
@@ -188,8 +192,9 @@ struct Ctx {
                             // round trip) — 2: lz77_walk, 3: blk_scan, 4: lz77_cand, 5: lz77_copy; 6: every phase, the encode's match and
                             // parse phases split by kernel (lz77_cand + lz77_resolve for lz77_match, lz77_walk + lz77_chain for lz77_parse)
     bool timing_fine() const { return timing_on >= 2; }
-    hipEvent_t ev[17] = {};
-    char ev_name[17][24] = {};
+    static constexpr int MAX_EV = 17;   // events a call can record: who stamps several phases at once asks for the room first
+    hipEvent_t ev[MAX_EV] = {};
+    char ev_name[MAX_EV][24] = {};
     int n_ev = 0;
     void phase(const char *name);
 };

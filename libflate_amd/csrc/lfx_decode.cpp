@@ -17,6 +17,7 @@
 #include "lfx_decode_int.h"
 #include "lfx_container.h"
 #include "lfx_index.h"
+#include "lfx_bgzf.h"
 #include <thread>
 #include <chrono>
 
@@ -555,7 +556,7 @@ static int batch_fast(Ctx *c, const uint8_t *d_in, uint64_t n_in, uint8_t *d_out
         LAUNCH_TRY(launch_blk_scan(st, d_in, n_in, (const BlkJob *)c->d_dec_streams.p, nj, (BlkInfo *)c->d_dec_state.p,
                                    (BlkLanes *)c->d_dec_cand.p, c->d_dec_tabs.p, small));
         // (phase brackets of the first rounds only: the timer holds sixteen, and "fast" / "inflate" / "verify" close the call)
-        const bool stamp = c->n_ev + 6 < 17;
+        const bool stamp = c->n_ev + 6 < Ctx::MAX_EV;
         if (stamp) c->phase("blk_scan");
         std::vector<BlkInfo> bi(nj);
         HIP_TRY(hipMemcpyAsync(bi.data(), c->d_dec_state.p, sizeof(BlkInfo) * nj, hipMemcpyDeviceToHost, st));
@@ -896,7 +897,7 @@ int decode_members(Ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint
             const size_t k1 = std::min<size_t>(cand.size(), k + MEMBER_GROUP);
             if ((rc = member_walk(c, d_in, n, cand, k, k1, walk))) return rc;
             walked_to = k1;
-            if (c->n_ev + 6 < 17) c->phase("walk");
+            if (c->n_ev + 6 < Ctx::MAX_EV) c->phase("walk");
         }
         if (is_cand && walk[k].state == 1) {
             const MemberWalk &w = walk[k];
@@ -1004,6 +1005,318 @@ extern "C" int lfx_decode_members_host(lfx_ctx *cc, const void *in, uint64_t n, 
     if (out_len) *out_len = ol;
     return rc;
 } LFX_ABI_CATCH
+
+// ------------------------------------------------------------------------------------------------
+// BGZF reads by virtual offset (lfx_bgzf_read_*).  Four steps: the walk of every read's BSIZE chain (on the
+// device by bgzf_hop_kernel, in the host call on the CPU — the same bgzf_walk of lfx_bgzf.h) that settles out_len, next_voff
+// and n_blocks from headers and ISIZEs alone and lists the (read, block) segments; the plan on the host (the distinct blocks
+// in file order); per group of MEMBER_GROUP blocks ONE decode_batch into scratch, which verifies each block's CRC-32; and the
+// gather of the wanted bytes into the reads' output ranges.
+namespace {
+struct BgzfBlock {
+    uint64_t coffset, in_off;   // in the file; in the buffer the decode reads
+    uint32_t blen, isize;
+};
+
+std::string bgzf_walk_message(const BgzfWalk &w) {
+    char b[160];
+    switch (w.err) {
+    case BGZF_ERR_RANGE: snprintf(b, sizeof b, "BGZF read: coffset %llu lies outside the bytes held", (unsigned long long)w.err_coff); break;
+    case BGZF_ERR_HEADER: snprintf(b, sizeof b, "BGZF read: no BGZF block header at coffset %llu", (unsigned long long)w.err_coff); break;
+    case BGZF_ERR_ISIZE: snprintf(b, sizeof b, "BGZF read: the block at coffset %llu has an ISIZE above 65536", (unsigned long long)w.err_coff); break;
+    case BGZF_ERR_CUT: snprintf(b, sizeof b, "BGZF read: the block at coffset %llu does not end inside the bytes held", (unsigned long long)w.err_coff); break;
+    case BGZF_ERR_UOFFSET: snprintf(b, sizeof b, "BGZF read: uoffset lies behind the ISIZE of the block at coffset %llu", (unsigned long long)w.err_coff); break;
+    default: snprintf(b, sizeof b, "BGZF read failed at coffset %llu", (unsigned long long)w.err_coff);
+    }
+    return b;
+}
+
+// rules 7 and 11 (include/lfx.h): what needs no device
+int bgzf_check_args(Ctx *c, uint32_t count, const lfx_bgzf_read *reads, const lfx_bgzf_result *res) {
+    if (!reads || !res) { c->set_error("BGZF read: reads and res must not be NULL"); return LFX_E_ARG; }
+    std::vector<std::pair<uint64_t, uint64_t>> rg;
+    rg.reserve(count);
+    for (uint32_t i = 0; i < count; i++) {
+        if (!reads[i].len) continue;
+        const uint64_t end = reads[i].out_off + reads[i].len;
+        rg.emplace_back(reads[i].out_off, end < reads[i].out_off ? ~0ull : end);
+    }
+    std::sort(rg.begin(), rg.end());
+    for (size_t k = 1; k < rg.size(); k++)
+        if (rg[k].first < rg[k - 1].second) {
+            char b[128];
+            snprintf(b, sizeof b, "BGZF read: two output ranges overlap at byte %llu", (unsigned long long)rg[k].first);
+            c->set_error(b);
+            return LFX_E_ARG;
+        }
+    return LFX_OK;
+}
+
+// the walk on the device: walk[i] for every read, and (want_segs) the segments of all reads, each read's in walk order.  At
+// most three round trips whatever the reads are: the walk with a list sized by a guess, the walk again with the exact sizes
+// when a read had more segments than guessed, the list.
+int bgzf_hop_device(Ctx *c, const uint8_t *d_in, uint64_t in_base, uint64_t n, uint32_t count, const lfx_bgzf_read *reads,
+                    bool want_segs, std::vector<BgzfWalk> &walk, std::vector<BgzfSeg> &segs) {
+    hipStream_t st = c->stream;
+    int rc;
+    walk.resize(count);
+    segs.clear();
+    std::vector<uint64_t> off(count + 1, 0);
+    if (want_segs) {
+        // a block of 64 KiB of output seldom takes less than 8 KiB of input
+        constexpr uint64_t GUESS_CAP = 1ull << 20;
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < count && total <= GUESS_CAP; i++) {
+            const uint64_t co = reads[i].voff >> 16;
+            const uint64_t by_in = co >= in_base && co - in_base <= n ? (in_base + n - co) / 8192 + 2 : 0;
+            total += std::min(reads[i].len / 32768 + 2, by_in);
+            off[i + 1] = total;
+        }
+        if (total > GUESS_CAP) std::fill(off.begin(), off.end(), 0);    // count first, then list
+    }
+    const size_t sz_reads = sizeof(lfx_bgzf_read) * count, sz_off = 8ull * (count + 1), sz_walk = sizeof(BgzfWalk) * count;
+    for (int pass = 0; pass < 2; pass++) {
+        const uint64_t slots = off[count];
+        if ((rc = c->d_bgzf_meta.reserve(sz_reads + sz_off + sz_walk + sizeof(BgzfSeg) * slots + 64))) return rc;
+        uint8_t *base = (uint8_t *)c->d_bgzf_meta.p;
+        lfx_bgzf_read *d_reads = (lfx_bgzf_read *)base;
+        uint64_t *d_off = (uint64_t *)(base + sz_reads);
+        BgzfWalk *d_walk = (BgzfWalk *)(base + sz_reads + sz_off);
+        BgzfSeg *d_segs = (BgzfSeg *)(base + sz_reads + sz_off + sz_walk);
+        HIP_TRY(hipMemcpyAsync(d_reads, reads, sz_reads, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_off, off.data(), sz_off, hipMemcpyHostToDevice, st));
+        LAUNCH_TRY(launch_bgzf_hop(st, d_in, in_base, n, count, d_reads, d_off, want_segs && slots ? d_segs : nullptr, d_walk));
+        HIP_TRY(hipMemcpyAsync(walk.data(), d_walk, sz_walk, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (!want_segs) return LFX_OK;
+        bool fits = true;
+        for (uint32_t i = 0; i < count; i++) fits = fits && walk[i].n_blocks <= off[i + 1] - off[i];
+        if (fits) {
+            if (!slots) return LFX_OK;
+            std::vector<BgzfSeg> all(slots);
+            HIP_TRY(hipMemcpyAsync(all.data(), d_segs, sizeof(BgzfSeg) * slots, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (uint32_t i = 0; i < count; i++) segs.insert(segs.end(), all.begin() + off[i], all.begin() + off[i] + walk[i].n_blocks);
+            return LFX_OK;
+        }
+        for (uint32_t i = 0; i < count; i++) off[i + 1] = off[i] + walk[i].n_blocks;
+    }
+    c->set_error("BGZF read: the segment list did not fit its exact size");
+    return LFX_E_DEVICE;
+}
+
+// segs sorted by (coffset, read) — a read's segments stay in walk order, the walk only moves forward — and the distinct blocks
+void bgzf_plan(std::vector<BgzfSeg> &segs, std::vector<BgzfBlock> &blocks) {
+    std::sort(segs.begin(), segs.end(), [](const BgzfSeg &a, const BgzfSeg &b) {
+        return a.coffset != b.coffset ? a.coffset < b.coffset : a.read < b.read;
+    });
+    blocks.clear();
+    for (const BgzfSeg &s : segs)
+        if (blocks.empty() || blocks.back().coffset != s.coffset) blocks.push_back(BgzfBlock{s.coffset, 0, s.blen, s.isize});
+}
+
+// decode and gather: blocks[i].in_off is block i's first byte in d_src; read r's bytes go to d_out + dst[r].  A block that
+// fails ends every read that touches it there (rule 5): walk[r] becomes that verdict, msg[r] its message.
+int bgzf_run(Ctx *c, const uint8_t *d_src, const std::vector<BgzfSeg> &segs, const std::vector<BgzfBlock> &blocks, uint8_t *d_out,
+             const std::vector<uint64_t> &dst, std::vector<BgzfWalk> &walk, std::vector<std::string> &msg) {
+    hipStream_t st = c->stream;
+    int rc;
+    std::vector<uint8_t> failed(walk.size(), 0);
+    size_t s0 = 0;
+    for (size_t g0 = 0; g0 < blocks.size(); g0 += MEMBER_GROUP) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(MEMBER_GROUP, blocks.size() - g0);
+        std::vector<uint64_t> in_off(nb), in_len(nb), out_off(nb), out_cap(nb), used;
+        uint64_t at = 0;
+        for (uint32_t q = 0; q < nb; q++) {
+            const BgzfBlock &b = blocks[g0 + q];
+            in_off[q] = b.in_off; in_len[q] = b.blen; out_off[q] = at; out_cap[q] = b.isize;
+            at += (b.isize + 15u) & ~15u;       // (16-byte aligned: the gather's dword loads never leave a block's slot)
+        }
+        if ((rc = c->d_bgzf_scratch.reserve(std::max<uint64_t>(at, 16)))) return rc;
+        uint8_t *d_scratch = (uint8_t *)c->d_bgzf_scratch.p;
+        std::vector<InflateResult> res;
+        {
+            PhaseMute mute(c);
+            if ((rc = decode_batch(c, LFX_GZIP, nb, d_src, in_off.data(), in_len.data(), d_scratch, out_off.data(), out_cap.data(), res,
+                                   &used)))
+                return rc;
+        }
+        if (c->n_ev + 2 < Ctx::MAX_EV) c->phase("batch");
+        std::vector<BgzfCopy> tasks;
+        const uint64_t last_co = blocks[g0 + nb - 1].coffset;
+        uint32_t q = 0;
+        for (; s0 < segs.size() && segs[s0].coffset <= last_co; s0++) {
+            const BgzfSeg &s = segs[s0];
+            while (blocks[g0 + q].coffset < s.coffset) q++;
+            if (failed[s.read]) continue;
+            const InflateResult &r = res[q];
+            if (r.status != 0 || r.out_len != s.isize || used[q] != s.blen) {
+                failed[s.read] = 1;
+                BgzfWalk &w = walk[s.read];
+                w.status = LFX_E_INVALID_DATA;
+                w.out_len = s.out_pos;
+                w.n_blocks = s.ord;
+                w.next_voff = s.coffset << 16 | s.first;
+                w.err_coff = s.coffset;
+                char b[96];
+                snprintf(b, sizeof b, "BGZF block at coffset %llu: ", (unsigned long long)s.coffset);
+                if (r.status != 0 && r.status != 3) msg[s.read] = b + format_error(r.err, r.a0, r.a1);
+                else if (r.status == 3 || r.out_len != s.isize) msg[s.read] = std::string(b) + "the decoded length differs from ISIZE";
+                else msg[s.read] = std::string(b) + "the member does not end at BSIZE + 1";
+                continue;
+            }
+            for (uint32_t p = s.first; p < s.last; p += BGZF_GATHER_PIECE)
+                tasks.push_back(BgzfCopy{out_off[q] + p, dst[s.read] + s.out_pos + (p - s.first), std::min(BGZF_GATHER_PIECE, s.last - p), 0});
+        }
+        if (!tasks.empty()) {
+            if ((rc = c->d_bgzf_tasks.reserve(sizeof(BgzfCopy) * tasks.size()))) return rc;
+            HIP_TRY(hipMemcpyAsync(c->d_bgzf_tasks.p, tasks.data(), sizeof(BgzfCopy) * tasks.size(), hipMemcpyHostToDevice, st));
+            LAUNCH_TRY(launch_bgzf_gather(st, d_scratch, d_out, (const BgzfCopy *)c->d_bgzf_tasks.p, (uint32_t)tasks.size()));
+        }
+        HIP_TRY(hipStreamSynchronize(st));     // (the task list must outlive its copy; the next group decodes into the same scratch)
+        if (c->n_ev + 1 < Ctx::MAX_EV) c->phase("gather");
+    }
+    return LFX_OK;
+}
+
+// res[] and the call's return value from the walks (rule 8).  The ONLY place that writes res: every return in front of it — a
+// refusal of the call, a device error — leaves res as the caller set it (include/lfx.h; Context._bgzf_call relies on it)
+int bgzf_finish(Ctx *c, uint32_t count, const std::vector<BgzfWalk> &walk, const std::vector<std::string> &msg, lfx_bgzf_result *res) {
+    int worst = LFX_OK;
+    for (uint32_t i = 0; i < count; i++) {
+        res[i].out_len = walk[i].out_len;
+        res[i].next_voff = walk[i].next_voff;
+        res[i].status = walk[i].status;
+        res[i].n_blocks = walk[i].n_blocks;
+        if (walk[i].status != LFX_OK && worst == LFX_OK) {
+            worst = walk[i].status;
+            c->set_error(msg[i].empty() ? bgzf_walk_message(walk[i]) : msg[i]);
+        }
+    }
+    return worst;
+}
+}  // namespace
+
+extern "C" int lfx_bgzf_read_device(lfx_ctx *cc, const void *d_in, uint64_t in_base, uint64_t n, uint32_t count,
+                                    const lfx_bgzf_read *reads, void *d_out, lfx_bgzf_result *res, uint64_t *blocks_decoded) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    if (blocks_decoded) *blocks_decoded = 0;
+    if (!count) return LFX_OK;
+    int rc;
+    if ((rc = bgzf_check_args(c, count, reads, res))) return rc;
+    if (in_base + n < in_base || (in_base + n) >> 48) { c->set_error("BGZF read: the bytes held end behind coffset 2^48"); return LFX_E_ARG; }
+    std::vector<BgzfWalk> walk;
+    std::vector<BgzfSeg> segs;
+    if ((rc = bgzf_hop_device(c, (const uint8_t *)d_in, in_base, n, count, reads, d_out != nullptr, walk, segs))) return rc;
+    c->phase("hop");
+    std::vector<std::string> msg(count);
+    if (d_out && !segs.empty()) {
+        std::vector<BgzfBlock> blocks;
+        bgzf_plan(segs, blocks);
+        for (BgzfBlock &b : blocks) b.in_off = b.coffset - in_base;
+        std::vector<uint64_t> dst(count);
+        for (uint32_t i = 0; i < count; i++) dst[i] = reads[i].out_off;
+        c->phase("plan");
+        if ((rc = bgzf_run(c, (const uint8_t *)d_in, segs, blocks, (uint8_t *)d_out, dst, walk, msg))) return rc;
+        if (blocks_decoded) *blocks_decoded = blocks.size();
+    }
+    return bgzf_finish(c, count, walk, msg, res);
+} LFX_ABI_CATCH
+
+extern "C" int lfx_bgzf_read_host(lfx_ctx *cc, const void *in_, uint64_t in_base, uint64_t n, uint32_t count,
+                                  const lfx_bgzf_read *reads, void *out, lfx_bgzf_result *res, uint64_t *blocks_decoded) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    if (blocks_decoded) *blocks_decoded = 0;
+    if (!count) return LFX_OK;
+    int rc;
+    if ((rc = bgzf_check_args(c, count, reads, res))) return rc;
+    if (in_base + n < in_base || (in_base + n) >> 48) { c->set_error("BGZF read: the bytes held end behind coffset 2^48"); return LFX_E_ARG; }
+    // the walk on the CPU over the caller's bytes: the file is not uploaded
+    const uint8_t *in = (const uint8_t *)in_;
+    const uint64_t lo = in_base, hi = in_base + n;
+    std::vector<BgzfWalk> walk(count);
+    std::vector<BgzfSeg> segs;
+    auto fetch = [&](uint64_t p, uint8_t *w) {
+        for (uint32_t k = 0; k < BGZF_WINDOW; k++) {
+            const uint64_t a = p + k - 4;
+            w[k] = a >= lo && a < hi ? in[a - lo] : 0;
+        }
+    };
+    for (uint32_t i = 0; i < count; i++) {
+        if (out) bgzf_walk(reads[i], i, lo, hi, fetch, [&](const BgzfSeg &s) { segs.push_back(s); }, walk[i]);
+        else bgzf_walk(reads[i], i, lo, hi, fetch, [](const BgzfSeg &) {}, walk[i]);
+    }
+    c->phase("hop");
+    std::vector<std::string> msg(count);
+    if (out && !segs.empty()) {
+        // only the distinct covered blocks cross the link, packed back to back
+        std::vector<BgzfBlock> blocks;
+        bgzf_plan(segs, blocks);
+        uint64_t packed = 0, total = 0;
+        for (BgzfBlock &b : blocks) { b.in_off = packed; packed += b.blen; }
+        std::vector<uint8_t> pack(packed);
+        for (const BgzfBlock &b : blocks) memcpy(pack.data() + b.in_off, in + (b.coffset - lo), b.blen);
+        std::vector<uint64_t> dst(count);
+        for (uint32_t i = 0; i < count; i++) { dst[i] = total; total += walk[i].out_len; }
+        if ((rc = c->d_bgzf_pack.reserve(std::max<uint64_t>(packed, 4)))) return rc;
+        if ((rc = c->d_io_out.reserve(std::max<uint64_t>(total, 4)))) return rc;
+        if (int hr = host_to_device(c, c->d_bgzf_pack.p, pack.data(), packed, c->stream)) { c->set_error("host to device copy failed"); return hr; }
+        c->phase("plan");
+        if ((rc = bgzf_run(c, (const uint8_t *)c->d_bgzf_pack.p, segs, blocks, (uint8_t *)c->d_io_out.p, dst, walk, msg))) return rc;
+        if (blocks_decoded) *blocks_decoded = blocks.size();
+        // the reads' byte ranges come back: a few long reads each straight into its range, many reads in one transfer
+        const uint8_t *d_res = (const uint8_t *)c->d_io_out.p;
+        if (count <= 8) {
+            for (uint32_t i = 0; i < count; i++)
+                if (walk[i].out_len)
+                    if (int hr = device_to_host(c, (uint8_t *)out + reads[i].out_off, d_res + dst[i], walk[i].out_len, c->stream)) {
+                        c->set_error("device to host copy failed");
+                        return hr;
+                    }
+        } else if (total) {
+            std::vector<uint8_t> back(total);
+            if (int hr = device_to_host(c, back.data(), d_res, total, c->stream)) { c->set_error("device to host copy failed"); return hr; }
+            for (uint32_t i = 0; i < count; i++)
+                if (walk[i].out_len) memcpy((uint8_t *)out + reads[i].out_off, back.data() + dst[i], walk[i].out_len);
+        }
+    }
+    return bgzf_finish(c, count, walk, msg, res);
+} LFX_ABI_CATCH
+
+// host only: uncompressed offset -> virtual offset through a member table
+extern "C" int lfx_members_voffset(const lfx_member *members, uint32_t n_members, int swapped, uint64_t uoff, uint64_t *voff) {
+    if (!voff || (n_members && !members)) return LFX_E_ARG;
+    auto u_off = [&](uint32_t i) { return swapped ? members[i].out_off : members[i].in_off; };
+    auto u_len = [&](uint32_t i) { return swapped ? members[i].out_len : members[i].in_len; };
+    auto c_off = [&](uint32_t i) { return swapped ? members[i].in_off : members[i].out_off; };
+    auto c_len = [&](uint32_t i) { return swapped ? members[i].in_len : members[i].out_len; };
+    const uint64_t total = n_members ? u_off(n_members - 1) + u_len(n_members - 1) : 0;
+    if (uoff > total) return LFX_E_ARG;
+    uint64_t co, uo = 0;
+    if (uoff == total) co = n_members ? c_off(n_members - 1) + c_len(n_members - 1) : 0;
+    else {
+        uint32_t lo = 0, hi = n_members;        // the last member that starts at or in front of uoff
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (u_off(mid) <= uoff) lo = mid; else hi = mid;
+        }
+        co = c_off(lo);
+        uo = uoff - u_off(lo);
+    }
+    if (uo > 0xffff || co >> 48) return LFX_E_ARG;     // not a BGZF table: the position has no virtual offset
+    *voff = co << 16 | uo;
+    return LFX_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Decoded size without decoding (lfx_decode_size_*).  The verdict of the matching decode call — status,
@@ -1213,7 +1526,7 @@ int size_members(Ctx *c, const uint8_t *d_in, uint64_t n, DecodeOutcome &oc, std
                     w.state = 1;
                 }
             walked_to = k1;
-            if (c->n_ev + 6 < 17) c->phase("walk_size");
+            if (c->n_ev + 6 < Ctx::MAX_EV) c->phase("walk_size");
         }
         if (is_cand && walk[k].state == 1) {
             const MemberWalk &w = walk[k];
