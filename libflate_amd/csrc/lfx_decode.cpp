@@ -160,6 +160,40 @@ int decode_stream(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint6
     return member_loop(c, format, flags, d_in, n, d_out, cap, false, oc, base, out_at, one_member, members);
 }
 
+// The container headers of a list of streams in one launch: hdrs[i] = stream i's parse.  The streams and the headers stay in
+// d_dec_blocks (*d_streams, *d_hdrs, with extra_bytes of room behind the headers) for the kernels of a caller that go on from
+// them.  LFX_DEFLATE has no header: all-zero ones, on the device too, without a round trip.
+int parse_headers(Ctx *c, int format, const uint8_t *d_in, const std::vector<DecStream> &streams, std::vector<DecHeader> &hdrs,
+                  size_t extra_bytes = 0, DecStream **d_streams = nullptr, DecHeader **d_hdrs = nullptr) {
+    hipStream_t st = c->stream;
+    const uint32_t count = (uint32_t)streams.size();
+    const size_t sz_streams = sizeof(DecStream) * count, sz_hdr = sizeof(DecHeader) * count;
+    int rc;
+    if ((rc = c->d_dec_blocks.reserve(sz_streams + sz_hdr + extra_bytes))) return rc;
+    DecStream *ds = (DecStream *)c->d_dec_blocks.p;
+    DecHeader *dh = (DecHeader *)((uint8_t *)c->d_dec_blocks.p + sz_streams);
+    HIP_TRY(hipMemcpyAsync(ds, streams.data(), sz_streams, hipMemcpyHostToDevice, st));
+    LAUNCH_TRY(launch_container(st, format, count, d_in, ds, dh));
+    hdrs.assign(count, DecHeader{});
+    if (format != LFX_DEFLATE) {
+        HIP_TRY(hipMemcpyAsync(hdrs.data(), dh, sz_hdr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        HIP_TRY(hipMemsetAsync(dh, 0, sz_hdr, st));
+    }
+    if (d_streams) *d_streams = ds;
+    if (d_hdrs) *d_hdrs = dh;
+    return LFX_OK;
+}
+
+// the input of a host variant, staged like lfx_decode_host's
+int stage_in(Ctx *c, const void *in, uint64_t n) {
+    int rc;
+    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
+    if (int hr = host_to_device(c, c->d_io_in.p, in, n, c->stream)) { c->set_error("host to device copy failed"); return hr; }
+    return LFX_OK;
+}
+
 }  // namespace
 
 extern "C" int lfx_decode_device(lfx_ctx *cc, int format, uint32_t flags, const void *d_in, uint64_t n,
@@ -521,13 +555,11 @@ extern "C" int lfx_decode_host(lfx_ctx *cc, int format, uint32_t flags, const vo
 // round (a block's start is only known once the block before it has been scanned; reference-made streams
 // have two blocks).  A stream leaves the fast path — and is decoded again, exactly, by the serial kernel —
 // on any anomaly: undecodable block, a block that runs past the stream's end or its output capacity, a
-// back-reference that reaches in front of its block, more than MAX_ROUNDS blocks.
+// back-reference that reaches in front of its block, more than BLOCK_ROUNDS blocks.
 // fast[i] = 1: d_out holds the stream's bytes and res[i] is filled in.
 namespace lfx {
 static int batch_fast(Ctx *c, const uint8_t *d_in, uint64_t n_in, uint8_t *d_out, uint32_t count,
                       const std::vector<InflateJob> &jobs, std::vector<uint8_t> &fast, std::vector<InflateResult> &res) {
-    constexpr uint32_t MAX_ROUNDS = 4;
-    hipStream_t st = c->stream;
     struct Live { uint32_t stream; uint64_t bit, produced; uint32_t nblocks; };
     std::vector<Live> live;
     fast.assign(count, 0);
@@ -536,31 +568,18 @@ static int batch_fast(Ctx *c, const uint8_t *d_in, uint64_t n_in, uint8_t *d_out
         if (jobs[i].in_len >= 64 && jobs[i].in_off + jobs[i].in_len <= n_in)
             live.push_back(Live{i, jobs[i].in_off * 8 + jobs[i].start_bit, 0, 0});
     int rc;
-    for (uint32_t round = 0; round < MAX_ROUNDS && !live.empty(); round++) {
+    for (uint32_t round = 0; round < BLOCK_ROUNDS && !live.empty(); round++) {
         const uint32_t nj = (uint32_t)live.size();
         std::vector<BlkJob> bj(nj);
         for (uint32_t k = 0; k < nj; k++) {
             const InflateJob &j = jobs[live[k].stream];
             bj[k] = BlkJob{live[k].bit, (j.in_off + j.in_len) * 8};
         }
-        if ((rc = c->d_dec_streams.reserve(sizeof(BlkJob) * nj))) return rc;
-        if ((rc = c->d_dec_state.reserve(sizeof(BlkInfo) * nj))) return rc;
-        if ((rc = c->d_dec_cand.reserve(sizeof(BlkLanes) * (size_t)nj))) return rc;
-        if ((rc = c->d_dec_tabs.reserve(blk_tabs_bytes() * nj))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->d_dec_streams.p, bj.data(), sizeof(BlkJob) * nj, hipMemcpyHostToDevice, st));
-        // (streams of a few tens of KB: the 256-lane instances of the scan and the emit kernel — a 32 KB block in 1024 slices is
-        //  17 symbols a lane; LFX_NO_SMALL_SCAN=1 keeps 1024)
-        uint64_t range_bits = 0;
-        for (uint32_t k = 0; k < nj; k++) range_bits += bj[k].end_bit - bj[k].start_bit;
-        const bool small = !c->diag.no_small_scan && range_bits / nj < (512ull << 10);
-        LAUNCH_TRY(launch_blk_scan(st, d_in, n_in, (const BlkJob *)c->d_dec_streams.p, nj, (BlkInfo *)c->d_dec_state.p,
-                                   (BlkLanes *)c->d_dec_cand.p, c->d_dec_tabs.p, small));
         // (phase brackets of the first rounds only: the timer holds sixteen, and "fast" / "inflate" / "verify" close the call)
         const bool stamp = c->n_ev + 6 < Ctx::MAX_EV;
-        if (stamp) c->phase("blk_scan");
-        std::vector<BlkInfo> bi(nj);
-        HIP_TRY(hipMemcpyAsync(bi.data(), c->d_dec_state.p, sizeof(BlkInfo) * nj, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<BlkInfo> bi;
+        bool small = false;
+        if ((rc = scan_round(c, d_in, n_in, bj, true, bi, small, stamp))) return rc;
         // blocks that scanned cleanly and fit are emitted; the others drop their stream out of the fast path
         std::vector<BlkEmit> emit;
         std::vector<uint32_t> owner;
@@ -578,25 +597,8 @@ static int batch_fast(Ctx *c, const uint8_t *d_in, uint64_t n_in, uint8_t *d_out
             total_codes += r.n_codes;
         }
         const uint32_t ne = (uint32_t)emit.size();
-        std::vector<uint32_t> jf(ne, 0);
-        if (ne) {
-            if ((rc = c->d_dec_tmp.reserve(sizeof(BlkEmit) * ne + 4ull * ne + 128))) return rc;
-            if ((rc = c->d_hist.reserve(sizeof(BlkUnits) * (size_t)ne + 64))) return rc;
-            if ((rc = c->d_codes.reserve(4 * std::max<uint64_t>(total_codes, 1)))) return rc;
-            uint32_t *d_flags = (uint32_t *)c->d_dec_tmp.p;
-            uint32_t *d_jf = d_flags + 16;
-            BlkEmit *d_emit = (BlkEmit *)((uint8_t *)c->d_dec_tmp.p + 64 + 4ull * ne + (8 - (4ull * ne) % 8) % 8);
-            HIP_TRY(hipMemsetAsync(d_flags, 0, 64 + 4ull * ne, st));
-            HIP_TRY(hipMemcpyAsync(d_emit, emit.data(), sizeof(BlkEmit) * ne, hipMemcpyHostToDevice, st));
-            LAUNCH_TRY(launch_blk_emit(st, d_in, n_in, d_emit, ne, (const BlkLanes *)c->d_dec_cand.p, (uint32_t *)c->d_codes.p,
-                                       d_flags, (BlkUnits *)c->d_hist.p, emit_unit_target(total_codes, c->n_cu), d_jf, c->d_dec_tabs.p, 17, false, small));
-            if (stamp) c->phase("blk_emit");
-            LAUNCH_TRY(launch_blk_materialize(st, d_in, d_emit, ne, (const BlkLanes *)c->d_dec_cand.p,
-                                              (const BlkUnits *)c->d_hist.p, (const uint32_t *)c->d_codes.p, d_out, nullptr));
-            if (stamp) c->phase("lz77_copy");
-            HIP_TRY(hipMemcpyAsync(jf.data(), d_jf, 4ull * ne, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
+        std::vector<uint32_t> jf;
+        if (ne && (rc = emit_round(c, d_in, n_in, emit, total_codes, small, d_out, jf, stamp))) return rc;
         if (c->idx && ne) {   // (an index build: the blocks this round proved)
             std::vector<BlkEmit> ok;
             for (uint32_t q = 0; q < ne; q++) if (!jf[q]) ok.push_back(emit[q]);
@@ -642,22 +644,13 @@ int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uin
     std::vector<DecStream> streams(count);
     for (uint32_t i = 0; i < count; i++) streams[i] = DecStream{in_off[i], in_len[i], out_off[i], out_cap[i]};
     int rc;
-    const size_t sz_streams = sizeof(DecStream) * count, sz_hdr = sizeof(DecHeader) * count;
-    if ((rc = c->d_dec_blocks.reserve(sz_streams + sz_hdr + 16ull * count + 64))) return rc;
-    DecStream *d_streams = (DecStream *)c->d_dec_blocks.p;
-    DecHeader *d_hdrs = (DecHeader *)((uint8_t *)c->d_dec_blocks.p + sz_streams);
-    uint32_t *d_crc = (uint32_t *)((uint8_t *)d_hdrs + sz_hdr);
+    std::vector<DecHeader> hdrs;
+    DecStream *d_streams;
+    DecHeader *d_hdrs;       // (behind the headers: each stream's checksums and its bytes consumed)
+    if ((rc = parse_headers(c, format, (const uint8_t *)d_in, streams, hdrs, 16ull * count + 64, &d_streams, &d_hdrs))) return rc;
+    uint32_t *d_crc = (uint32_t *)(d_hdrs + count);
     uint32_t *d_adler = d_crc + count;
     uint64_t *d_consumed = (uint64_t *)(d_adler + count);
-    HIP_TRY(hipMemcpyAsync(d_streams, streams.data(), sz_streams, hipMemcpyHostToDevice, st));
-    LAUNCH_TRY(launch_container(st, format, count, (const uint8_t *)d_in, d_streams, d_hdrs));
-    std::vector<DecHeader> hdrs(count);
-    if (format != LFX_DEFLATE) {
-        HIP_TRY(hipMemcpyAsync(hdrs.data(), d_hdrs, sz_hdr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    } else {
-        HIP_TRY(hipMemsetAsync(d_hdrs, 0, sz_hdr, st));
-    }
     c->phase("headers");
     std::vector<InflateJob> jobs(count);
     for (uint32_t i = 0; i < count; i++) {
@@ -755,8 +748,6 @@ namespace {
 constexpr uint32_t MEMBER_DENSE = 64;          // a tile with more candidates than this (one per 256 bytes) is not listed: a chain
                                                // start inside it goes through the sequential loop (a stored member full of magic)
 constexpr uint32_t MEMBER_GROUP = 4096;        // candidates parsed and walked together, members decoded by one batch call
-constexpr uint32_t MEMBER_WALK_ROUNDS = 4;     // blocks a walk follows (batch_fast's MAX_ROUNDS) ...
-constexpr uint64_t MEMBER_WALK_BYTES = 4ull << 20;   // ... and input bytes it covers; a member beyond either is "long"
 constexpr uint64_t MEMBER_HDR_BYTES = 64ull << 10;   // header bytes a candidate's parse may read (a longer header: sequential)
 
 // the nested decodes record phases of their own: the members path names only its five (and "start")
@@ -803,139 +794,83 @@ int member_candidates(Ctx *c, const uint8_t *d_in, uint64_t n, std::vector<uint6
     return LFX_OK;
 }
 
-// header parse and block walk of candidates [k0, k1): walk[k] for each
-int member_walk(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<uint64_t> &cand, size_t k0, size_t k1,
+// the size path's pieces, defined with the size calls below
+int run_walk(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<WalkJob> &jobs, std::vector<WalkResult> &res);
+bool walk_settled(const WalkResult &r, uint64_t out_before);
+int size_stream(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_t n, DecodeOutcome &oc, uint64_t base = 0,
+                uint64_t out_at = 0, bool one_member = false, std::vector<lfx_member> *members = nullptr);
+
+// header parse and block walk of candidates [k0, k1): walk[k] for each.  The decode follows a member's blocks with the scan
+// kernel of the batch path, a block per round (no output); sizes_only: ONE launch of the size calls' walker.
+int member_walk(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<uint64_t> &cand, size_t k0, size_t k1, bool sizes_only,
                 std::vector<MemberWalk> &walk) {
-    hipStream_t st = c->stream;
     const uint32_t cnt = (uint32_t)(k1 - k0);
     if (!cnt) return LFX_OK;
     int rc;
     std::vector<DecStream> ds(cnt);
     for (uint32_t i = 0; i < cnt; i++) ds[i] = DecStream{cand[k0 + i], std::min(n - cand[k0 + i], MEMBER_HDR_BYTES), 0, 0};
-    const size_t sz_ds = sizeof(DecStream) * cnt, sz_dh = sizeof(DecHeader) * cnt;
-    if ((rc = c->d_dec_blocks.reserve(sz_ds + sz_dh))) return rc;
-    DecStream *d_ds = (DecStream *)c->d_dec_blocks.p;
-    DecHeader *d_dh = (DecHeader *)((uint8_t *)c->d_dec_blocks.p + sz_ds);
-    HIP_TRY(hipMemcpyAsync(d_ds, ds.data(), sz_ds, hipMemcpyHostToDevice, st));
-    LAUNCH_TRY(launch_container(st, LFX_GZIP, cnt, d_in, d_ds, d_dh));
-    std::vector<DecHeader> dh(cnt);
-    HIP_TRY(hipMemcpyAsync(dh.data(), d_dh, sz_dh, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // the walk: one block per live candidate and round, the scan kernel of the batch path (no output)
+    std::vector<DecHeader> dh;
+    if ((rc = parse_headers(c, LFX_GZIP, d_in, ds, dh))) return rc;
     struct Live { size_t k; uint64_t bit, end_bit, produced; };
     std::vector<Live> live;
     for (uint32_t i = 0; i < cnt; i++) {
         const size_t k = k0 + i;
         walk[k].state = 2;
         if (dh[i].status != 0) continue;
-        const uint64_t data = cand[k] + dh[i].deflate_off;
-        // the range a block may end in: up to the next candidate (a member's trailer lies in front of the next member's
-        // header), at most MEMBER_WALK_BYTES
-        uint64_t lim = std::min<uint64_t>(n, cand[k] + MEMBER_WALK_BYTES);
-        const auto nx = std::upper_bound(cand.begin(), cand.end(), data);
-        if (nx != cand.end() && *nx < lim) lim = *nx;
-        if (lim <= data) continue;
-        live.push_back(Live{k, data * 8, lim * 8, 0});
+        const uint64_t data = cand[k] + dh[i].deflate_off, lim = member_walk_limit(cand, k, data, n);
+        if (lim > data) live.push_back(Live{k, data * 8, lim * 8, 0});
     }
-    for (uint32_t round = 0; round < MEMBER_WALK_ROUNDS && !live.empty(); round++) {
-        const uint32_t nj = (uint32_t)live.size();
-        std::vector<BlkJob> bj(nj);
-        uint64_t range_bits = 0;
-        for (uint32_t q = 0; q < nj; q++) {
-            bj[q] = BlkJob{live[q].bit, live[q].end_bit};
-            range_bits += live[q].end_bit - live[q].bit;
-        }
-        if ((rc = c->d_dec_streams.reserve(sizeof(BlkJob) * nj))) return rc;
-        if ((rc = c->d_dec_state.reserve(sizeof(BlkInfo) * nj))) return rc;
-        if ((rc = c->d_dec_cand.reserve(sizeof(BlkLanes) * (size_t)nj))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->d_dec_streams.p, bj.data(), sizeof(BlkJob) * nj, hipMemcpyHostToDevice, st));
-        const bool small = !c->diag.no_small_scan && range_bits / nj < (512ull << 10);
-        LAUNCH_TRY(launch_blk_scan(st, d_in, n, (const BlkJob *)c->d_dec_streams.p, nj, (BlkInfo *)c->d_dec_state.p,
-                                   (BlkLanes *)c->d_dec_cand.p, nullptr, small));
-        std::vector<BlkInfo> bi(nj);
-        HIP_TRY(hipMemcpyAsync(bi.data(), c->d_dec_state.p, sizeof(BlkInfo) * nj, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+    auto settle = [&](const Live &l, uint64_t end_bit, uint64_t n_out) {
+        MemberWalk &w = walk[l.k];
+        w.end_byte = (end_bit + 7) / 8;
+        w.n_out = n_out;
+        w.state = 1;
+    };
+    if (sizes_only) {
+        std::vector<WalkJob> jobs;
+        for (const Live &l : live) jobs.push_back(WalkJob{l.bit, l.end_bit, 0});
+        std::vector<WalkResult> wr;
+        if ((rc = run_walk(c, d_in, n, jobs, wr))) return rc;
+        for (size_t q = 0; q < jobs.size(); q++)
+            if (wr[q].status == WALK_FINAL && walk_settled(wr[q], 0)) settle(live[q], wr[q].end_bit, wr[q].n_out);
+        return LFX_OK;
+    }
+    for (uint32_t round = 0; round < BLOCK_ROUNDS && !live.empty(); round++) {
+        std::vector<BlkJob> bj;
+        for (const Live &l : live) bj.push_back(BlkJob{l.bit, l.end_bit});
+        std::vector<BlkInfo> bi;
+        bool small = false;
+        if ((rc = scan_round(c, d_in, n, bj, false, bi, small))) return rc;
         std::vector<Live> next;
-        for (uint32_t q = 0; q < nj; q++) {
+        for (size_t q = 0; q < live.size(); q++) {
             Live l = live[q];
             const BlkInfo &r = bi[q];
             if (r.status != BLK_OK || r.end_bit <= l.bit || r.end_bit > l.end_bit) continue;    // state stays 2
             l.produced += r.n_out;
-            if (r.bfinal) {
-                MemberWalk &w = walk[l.k];
-                w.end_byte = (r.end_bit + 7) / 8;
-                w.n_out = l.produced;
-                w.state = 1;
-            } else { l.bit = r.end_bit; next.push_back(l); }
+            if (r.bfinal) settle(l, r.end_bit, l.produced);
+            else { l.bit = r.end_bit; next.push_back(l); }
         }
         live.swap(next);
     }
     return LFX_OK;   // (still live after the last round: a long member, state 2)
 }
 
-struct ChainEntry {
-    lfx_member m;
-    bool batch;   // decoded by the batch (else: already decoded and verified by the sequential loop)
-};
-
-int decode_members(Ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, DecodeOutcome &oc,
-                   std::vector<lfx_member> &members) {
+// the chained members that the walk settled through the batch decoder, MEMBER_GROUP at a time: keep = the first one it does
+// not verify (or that comes out other than walked)
+int members_batch(Ctx *c, const uint8_t *d_in, uint8_t *d_out, const std::vector<lfx_member> &chain, const std::vector<uint8_t> &walked,
+                  size_t &keep) {
     int rc;
-    // ---- 1. candidates
-    std::vector<uint64_t> cand;
-    if ((rc = member_candidates(c, d_in, n, cand))) return rc;
-    c->phase("candidates");
-    // ---- 2.-4. header parse and walk (a group of candidates at a time, from the one the chain has reached), the chain
-    std::vector<MemberWalk> walk(cand.size());
-    std::vector<ChainEntry> chain;
-    uint64_t base = 0, out_at = 0;
-    size_t walked_to = 0;   // candidates in front of this one were walked or passed over
-    while (base < n) {
-        const size_t k = (size_t)(std::lower_bound(cand.begin(), cand.end(), base) - cand.begin());
-        const bool is_cand = k < cand.size() && cand[k] == base;
-        if (is_cand && k >= walked_to) {
-            const size_t k1 = std::min<size_t>(cand.size(), k + MEMBER_GROUP);
-            if ((rc = member_walk(c, d_in, n, cand, k, k1, walk))) return rc;
-            walked_to = k1;
-            if (c->n_ev + 6 < Ctx::MAX_EV) c->phase("walk");
-        }
-        if (is_cand && walk[k].state == 1) {
-            const MemberWalk &w = walk[k];
-            if (n - w.end_byte < 8 || w.n_out > cap - out_at) break;   // a cut trailer, output that does not fit: the tail says so
-            chain.push_back(ChainEntry{lfx_member{base, w.end_byte + 8 - base, out_at, w.n_out}, true});
-            base = w.end_byte + 8;
-            out_at += w.n_out;
-            continue;
-        }
-        // no candidate here (a dense tile, reserved FLG bits, not a header at all), or one the walk could not follow (a long
-        // member, a damaged one): ONE member through the sequential loop; anything but a verified member ends the chain
-        DecodeOutcome one;
-        std::vector<lfx_member> got;
-        {
-            PhaseMute mute(c);
-            if ((rc = decode_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, d_out, cap, one, base, out_at, true, &got))) return rc;
-        }
-        if (!one.more || got.size() != 1) break;
-        chain.push_back(ChainEntry{got[0], false});
-        base = one.consumed;
-        out_at = one.out_len;
-    }
-    c->phase("chain");
-    // ---- 5. the chained members through the batch decoder, MEMBER_GROUP at a time; the first one it does not verify
-    // (or that comes out other than walked) is where the tail starts
-    uint64_t tail_base = base, tail_out = out_at;
-    size_t keep = chain.size();
     for (size_t e0 = 0; e0 < chain.size() && keep == chain.size();) {
         std::vector<size_t> idx;
         size_t e1 = e0;
         for (; e1 < chain.size() && idx.size() < MEMBER_GROUP; e1++)
-            if (chain[e1].batch) idx.push_back(e1);
+            if (walked[e1]) idx.push_back(e1);
         e0 = e1;
         if (idx.empty()) continue;
         const uint32_t nb = (uint32_t)idx.size();
         std::vector<uint64_t> in_off(nb), in_len(nb), out_off(nb), out_cap(nb), used;
         for (uint32_t q = 0; q < nb; q++) {
-            const lfx_member &m = chain[idx[q]].m;
+            const lfx_member &m = chain[idx[q]];
             in_off[q] = m.in_off; in_len[q] = m.in_len; out_off[q] = m.out_off; out_cap[q] = m.out_len;
         }
         std::vector<InflateResult> res;
@@ -946,23 +881,88 @@ int decode_members(Ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint
                 return rc;
         }
         for (uint32_t q = 0; q < nb; q++)
-            if (res[q].status != 0 || used[q] != in_len[q] || res[q].out_len != out_cap[q]) {
-                keep = idx[q];
-                tail_base = in_off[q];
-                tail_out = out_off[q];
-                break;
-            }
+            if (res[q].status != 0 || used[q] != in_len[q] || res[q].out_len != out_cap[q]) { keep = idx[q]; break; }
     }
-    c->phase("batch");
-    // ---- 6. the sequential member loop from there on: the exact verdict, partial output and clean end
-    members.clear();
-    for (size_t e = 0; e < keep; e++) members.push_back(chain[e].m);
-    {
+    return LFX_OK;
+}
+
+// The members of d_in[0, n) and the verdict of the sequential member loop over them.  Candidates; the header parse and the
+// walk of a group of candidates at a time, from the one the chain has reached; the chain from byte 0 on the host; then, for
+// the decode, the chained members through the batch decoder; the member loop from the first member not settled.
+// sizes_only: the chain of the size calls — the walker instead of scan rounds, no output, no capacity and no batch; a start the
+// walk did not settle goes through size_stream for one member instead of decode_stream.
+int members_chain(Ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, bool sizes_only, DecodeOutcome &oc,
+                  std::vector<lfx_member> &members) {
+    auto loop = [&](DecodeOutcome &o, uint64_t base, uint64_t out_at, bool one_member, std::vector<lfx_member> *got) {
         PhaseMute mute(c);
-        if ((rc = decode_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, d_out, cap, oc, tail_base, tail_out, false, &members))) return rc;
+        return sizes_only ? size_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, o, base, out_at, one_member, got)
+                          : decode_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, d_out, cap, o, base, out_at, one_member, got);
+    };
+    int rc;
+    // ---- 1. candidates
+    std::vector<uint64_t> cand;
+    if ((rc = member_candidates(c, d_in, n, cand))) return rc;
+    c->phase("candidates");
+    // ---- 2.-4. header parse and walk, the chain
+    std::vector<MemberWalk> walk(cand.size());
+    std::vector<lfx_member> chain;
+    std::vector<uint8_t> walked;   // chain[e] was settled by the walk (else: already decoded and verified by the sequential loop)
+    uint64_t base = 0, out_at = 0;
+    size_t walked_to = 0;   // candidates in front of this one were walked or passed over
+    while (base < n) {
+        const size_t k = (size_t)(std::lower_bound(cand.begin(), cand.end(), base) - cand.begin());
+        const bool is_cand = k < cand.size() && cand[k] == base;
+        if (is_cand && k >= walked_to) {
+            const size_t k1 = std::min<size_t>(cand.size(), k + MEMBER_GROUP);
+            if ((rc = member_walk(c, d_in, n, cand, k, k1, sizes_only, walk))) return rc;
+            walked_to = k1;
+            if (c->n_ev + 6 < Ctx::MAX_EV) c->phase(sizes_only ? "walk_size" : "walk");
+        }
+        if (is_cand && walk[k].state == 1) {
+            const MemberWalk &w = walk[k];
+            // a cut trailer, output that does not fit: the tail says so
+            if (n - w.end_byte < 8 || (!sizes_only && w.n_out > cap - out_at)) break;
+            chain.push_back(lfx_member{base, w.end_byte + 8 - base, out_at, w.n_out});
+            walked.push_back(1);
+            base = w.end_byte + 8;
+            out_at += w.n_out;
+            continue;
+        }
+        // no candidate here (a dense tile, reserved FLG bits, not a header at all), or one the walk could not follow (a long
+        // member, a damaged one): ONE member through the sequential loop; anything but a verified member ends the chain
+        DecodeOutcome one;
+        std::vector<lfx_member> got;
+        if ((rc = loop(one, base, out_at, true, &got))) return rc;
+        if (!one.more || got.size() != 1) break;
+        chain.push_back(got[0]);
+        walked.push_back(0);
+        base = one.consumed;
+        out_at = one.out_len;
     }
+    c->phase("chain");
+    // ---- 5. the decode: the batch; the tail starts at the first member it does not settle
+    size_t keep = chain.size();
+    if (!sizes_only) {
+        if ((rc = members_batch(c, d_in, d_out, chain, walked, keep))) return rc;
+        c->phase("batch");
+    }
+    if (keep < chain.size()) { base = chain[keep].in_off; out_at = chain[keep].out_off; }
+    // ---- 6. the sequential member loop from there on: the exact verdict, partial output and clean end
+    members.assign(chain.begin(), chain.begin() + keep);
+    if ((rc = loop(oc, base, out_at, false, &members))) return rc;
     c->phase("tail");
     return LFX_OK;
+}
+
+// what the four members entry points hand back
+int members_out(Ctx *c, const DecodeOutcome &oc, const std::vector<lfx_member> &got, uint64_t *out_len, uint64_t *consumed,
+                lfx_member *members, uint32_t max_members, uint32_t *n_members) {
+    if (out_len) *out_len = oc.out_len;
+    if (consumed) *consumed = oc.consumed;
+    if (n_members) *n_members = (uint32_t)std::min<size_t>(got.size(), 0xFFFFFFFFu);
+    if (members) memcpy(members, got.data(), sizeof(lfx_member) * std::min<size_t>(got.size(), max_members));
+    if (oc.status != LFX_OK) c->set_error(oc.msg);
+    return oc.status;
 }
 }  // namespace
 
@@ -977,15 +977,10 @@ extern "C" int lfx_decode_members_device(lfx_ctx *cc, const void *d_in, uint64_t
     c->phase("start");
     DecodeOutcome oc;
     std::vector<lfx_member> got;
-    int rc = decode_members(c, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, oc, got);
+    int rc = members_chain(c, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, false, oc, got);
     if (rc) return rc;
     if (oc.out_len > cap) oc.out_len = cap;  // (as lfx_decode_device)
-    if (out_len) *out_len = oc.out_len;
-    if (consumed) *consumed = oc.consumed;
-    if (n_members) *n_members = (uint32_t)std::min<size_t>(got.size(), 0xFFFFFFFFu);
-    if (members) memcpy(members, got.data(), sizeof(lfx_member) * std::min<size_t>(got.size(), max_members));
-    if (oc.status != LFX_OK) c->set_error(oc.msg);
-    return oc.status;
+    return members_out(c, oc, got, out_len, consumed, members, max_members, n_members);
 } LFX_ABI_CATCH
 
 extern "C" int lfx_decode_members_host(lfx_ctx *cc, const void *in, uint64_t n, void *out, uint64_t cap, uint64_t *out_len,
@@ -995,9 +990,8 @@ extern "C" int lfx_decode_members_host(lfx_ctx *cc, const void *in, uint64_t n, 
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     (void)hipSetDevice(c->device);
     int rc;
-    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
     if ((rc = c->d_io_out.reserve(std::max<uint64_t>(cap, 4)))) return rc;
-    if (int hr = host_to_device(c, c->d_io_in.p, in, n, c->stream)) { c->set_error("host to device copy failed"); return hr; }
+    if ((rc = stage_in(c, in, n))) return rc;
     uint64_t ol = 0;
     rc = lfx_decode_members_device(cc, c->d_io_in.p, n, c->d_io_out.p, cap, &ol, consumed, members, max_members, n_members);
     if (rc == LFX_E_DEVICE || rc == LFX_E_OOM || rc == LFX_E_ARG) { (void)hipStreamSynchronize(c->stream); return rc; }
@@ -1345,7 +1339,7 @@ int run_walk(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<WalkJob>
     HIP_TRY(hipStreamSynchronize(c->stream));
     return LFX_OK;
 }
-inline bool walk_settled(const WalkResult &r, uint64_t out_before) {
+bool walk_settled(const WalkResult &r, uint64_t out_before) {
     return r.status != WALK_STUCK && (r.reach == INT64_MAX || (int64_t)out_before + r.reach >= 0);
 }
 
@@ -1468,100 +1462,9 @@ int size_member(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t off0, MemberRe
 }
 
 // decode_stream for sizes: the member loop without output and without the checksum comparison (a trailer must be THERE)
-int size_stream(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_t n, DecodeOutcome &oc, uint64_t base = 0,
-                uint64_t out_at = 0, bool one_member = false, std::vector<lfx_member> *members = nullptr) {
+int size_stream(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_t n, DecodeOutcome &oc, uint64_t base,
+                uint64_t out_at, bool one_member, std::vector<lfx_member> *members) {
     return member_loop(c, format, flags, d_in, n, nullptr, 0, true, oc, base, out_at, one_member, members);
-}
-
-// decode_members for sizes: candidates, header parse, ONE walker launch per group of candidates, the chain on the host; a
-// start the walk did not settle goes through size_stream for one member, and the member loop gives the verdict of the tail
-int size_members(Ctx *c, const uint8_t *d_in, uint64_t n, DecodeOutcome &oc, std::vector<lfx_member> &members) {
-    hipStream_t st = c->stream;
-    int rc;
-    std::vector<uint64_t> cand;
-    if ((rc = member_candidates(c, d_in, n, cand))) return rc;
-    c->phase("candidates");
-    std::vector<MemberWalk> walk(cand.size());
-    members.clear();
-    uint64_t base = 0, out_at = 0;
-    size_t walked_to = 0;
-    while (base < n) {
-        const size_t k = (size_t)(std::lower_bound(cand.begin(), cand.end(), base) - cand.begin());
-        const bool is_cand = k < cand.size() && cand[k] == base;
-        if (is_cand && k >= walked_to) {
-            const size_t k1 = std::min<size_t>(cand.size(), k + MEMBER_GROUP);
-            const uint32_t cnt = (uint32_t)(k1 - k);
-            std::vector<DecStream> ds(cnt);
-            for (uint32_t i = 0; i < cnt; i++) ds[i] = DecStream{cand[k + i], std::min(n - cand[k + i], MEMBER_HDR_BYTES), 0, 0};
-            const size_t sz_ds = sizeof(DecStream) * cnt, sz_dh = sizeof(DecHeader) * cnt;
-            if ((rc = c->d_dec_blocks.reserve(sz_ds + sz_dh))) return rc;
-            DecStream *d_ds = (DecStream *)c->d_dec_blocks.p;
-            DecHeader *d_dh = (DecHeader *)((uint8_t *)c->d_dec_blocks.p + sz_ds);
-            HIP_TRY(hipMemcpyAsync(d_ds, ds.data(), sz_ds, hipMemcpyHostToDevice, st));
-            LAUNCH_TRY(launch_container(st, LFX_GZIP, cnt, d_in, d_ds, d_dh));
-            std::vector<DecHeader> dh(cnt);
-            HIP_TRY(hipMemcpyAsync(dh.data(), d_dh, sz_dh, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            std::vector<WalkJob> jobs;
-            std::vector<size_t> owner;
-            for (uint32_t i = 0; i < cnt; i++) {
-                walk[k + i].state = 2;
-                if (dh[i].status != 0) continue;
-                const uint64_t data = cand[k + i] + dh[i].deflate_off;
-                // (a member's trailer lies in front of the next member's header; a member longer than MEMBER_WALK_BYTES is "long")
-                uint64_t lim = std::min<uint64_t>(n, cand[k + i] + MEMBER_WALK_BYTES);
-                const auto nx = std::upper_bound(cand.begin(), cand.end(), data);
-                if (nx != cand.end() && *nx < lim) lim = *nx;
-                if (lim <= data) continue;
-                jobs.push_back(WalkJob{data * 8, lim * 8, 0});
-                owner.push_back(k + i);
-            }
-            std::vector<WalkResult> wr;
-            if ((rc = run_walk(c, d_in, n, jobs, wr))) return rc;
-            for (size_t q = 0; q < jobs.size(); q++)
-                if (wr[q].status == WALK_FINAL && walk_settled(wr[q], 0)) {
-                    MemberWalk &w = walk[owner[q]];
-                    w.end_byte = (wr[q].end_bit + 7) / 8;
-                    w.n_out = wr[q].n_out;
-                    w.state = 1;
-                }
-            walked_to = k1;
-            if (c->n_ev + 6 < Ctx::MAX_EV) c->phase("walk_size");
-        }
-        if (is_cand && walk[k].state == 1) {
-            const MemberWalk &w = walk[k];
-            if (n - w.end_byte < 8) break;        // a cut trailer: the tail says so
-            members.push_back(lfx_member{base, w.end_byte + 8 - base, out_at, w.n_out});
-            base = w.end_byte + 8;
-            out_at += w.n_out;
-            continue;
-        }
-        DecodeOutcome one;
-        std::vector<lfx_member> got;
-        {
-            PhaseMute mute(c);
-            if ((rc = size_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, one, base, out_at, true, &got))) return rc;
-        }
-        if (!one.more || got.size() != 1) break;
-        members.push_back(got[0]);
-        base = one.consumed;
-        out_at = one.out_len;
-    }
-    c->phase("chain");
-    {
-        PhaseMute mute(c);
-        if ((rc = size_stream(c, LFX_GZIP, LFX_DEC_MULTI, d_in, n, oc, base, out_at, false, &members))) return rc;
-    }
-    c->phase("tail");
-    return LFX_OK;
-}
-
-// the input of a host variant, staged like lfx_decode_host's
-int size_stage_in(Ctx *c, const void *in, uint64_t n) {
-    int rc;
-    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
-    if (int hr = host_to_device(c, c->d_io_in.p, in, n, c->stream)) { c->set_error("host to device copy failed"); return hr; }
-    return LFX_OK;
 }
 }  // namespace
 
@@ -1590,7 +1493,7 @@ extern "C" int lfx_decode_size_host(lfx_ctx *cc, int format, uint32_t flags, con
     Ctx *c = reinterpret_cast<Ctx *>(cc);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     (void)hipSetDevice(c->device);
-    if (int rc = size_stage_in(c, in, n)) return rc;
+    if (int rc = stage_in(c, in, n)) return rc;
     const int rc = lfx_decode_size_device(cc, format, flags, c->d_io_in.p, n, out_len, consumed);
     (void)hipStreamSynchronize(c->stream);   // (a page-locked `in` was only queued for DMA)
     return rc;
@@ -1606,23 +1509,13 @@ extern "C" int lfx_decode_batch_size_device(lfx_ctx *cc, int format, uint32_t co
     c->phase("start");
     if (!count) return LFX_OK;
     if (format < 0 || format > 2) return LFX_E_ARG;
-    hipStream_t st = c->stream;
     const uint8_t *d_in = (const uint8_t *)d_in_;
     int rc;
     // ---- container headers (container_kernel)
     std::vector<DecStream> streams(count);
     for (uint32_t i = 0; i < count; i++) streams[i] = DecStream{in_off[i], in_len[i], 0, 0};
     std::vector<DecHeader> hdrs(count, DecHeader{});
-    if (format != LFX_DEFLATE) {
-        const size_t sz_streams = sizeof(DecStream) * count, sz_hdr = sizeof(DecHeader) * count;
-        if ((rc = c->d_dec_blocks.reserve(sz_streams + sz_hdr))) return rc;
-        DecStream *d_streams = (DecStream *)c->d_dec_blocks.p;
-        DecHeader *d_hdrs = (DecHeader *)((uint8_t *)c->d_dec_blocks.p + sz_streams);
-        HIP_TRY(hipMemcpyAsync(d_streams, streams.data(), sz_streams, hipMemcpyHostToDevice, st));
-        LAUNCH_TRY(launch_container(st, format, count, d_in, d_streams, d_hdrs));
-        HIP_TRY(hipMemcpyAsync(hdrs.data(), d_hdrs, sz_hdr, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    if (format != LFX_DEFLATE && (rc = parse_headers(c, format, d_in, streams, hdrs))) return rc;
     c->phase("headers");
     uint64_t n_in = 0;
     for (uint32_t i = 0; i < count; i++) n_in = std::max(n_in, in_off[i] + in_len[i]);
@@ -1715,14 +1608,9 @@ extern "C" int lfx_decode_members_size_device(lfx_ctx *cc, const void *d_in, uin
     c->phase("start");
     DecodeOutcome oc;
     std::vector<lfx_member> got;
-    int rc = size_members(c, (const uint8_t *)d_in, n, oc, got);
+    int rc = members_chain(c, (const uint8_t *)d_in, n, nullptr, 0, true, oc, got);
     if (rc) return rc;
-    if (out_len) *out_len = oc.out_len;
-    if (consumed) *consumed = oc.consumed;
-    if (n_members) *n_members = (uint32_t)std::min<size_t>(got.size(), 0xFFFFFFFFu);
-    if (members) memcpy(members, got.data(), sizeof(lfx_member) * std::min<size_t>(got.size(), max_members));
-    if (oc.status != LFX_OK) c->set_error(oc.msg);
-    return oc.status;
+    return members_out(c, oc, got, out_len, consumed, members, max_members, n_members);
 } LFX_ABI_CATCH
 
 extern "C" int lfx_decode_members_size_host(lfx_ctx *cc, const void *in, uint64_t n, uint64_t *out_len, uint64_t *consumed,
@@ -1731,7 +1619,7 @@ extern "C" int lfx_decode_members_size_host(lfx_ctx *cc, const void *in, uint64_
     Ctx *c = reinterpret_cast<Ctx *>(cc);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     (void)hipSetDevice(c->device);
-    if (int rc = size_stage_in(c, in, n)) return rc;
+    if (int rc = stage_in(c, in, n)) return rc;
     const int rc = lfx_decode_members_size_device(cc, c->d_io_in.p, n, out_len, consumed, members, max_members, n_members);
     (void)hipStreamSynchronize(c->stream);
     return rc;
@@ -1768,7 +1656,7 @@ extern "C" int lfx_decode_index_device(lfx_ctx *cc, int format, uint32_t flags, 
     {
         IdxScope scope(c, &col);
         PhaseMute mute(c);
-        if (multi) rc = decode_members(c, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, oc, members);
+        if (multi) rc = members_chain(c, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, false, oc, members);
         else rc = decode_stream(c, format, flags, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, oc, 0, 0, false, &members);
     }
     if (rc) return rc;

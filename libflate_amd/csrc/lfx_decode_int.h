@@ -123,4 +123,15 @@ struct EmitBufs {
 int emit_codes(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkEmit> &emit, uint64_t total_codes, uint32_t n_placed,
                uint32_t free_shift, bool scan_small, EmitBufs &eb);
 
+// ---- the two steps of a block round: one block of every live stream (the batch's fast path, the members walk, the reads
+// of a seek index).  What a caller makes of a BlkInfo or a job flag — accept, drop, retry — is the caller's business.
+// The scan of bj[]: bi[q] = job q's verdict, its lanes in d_dec_cand (want_tabs: its tables in d_dec_tabs, for emit_round).
+// small = the 256-lane instances were picked (ranges of a few tens of KB); stamp: phase "blk_scan" behind the launch.
+int scan_round(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkJob> &bj, bool want_tabs, std::vector<BlkInfo> &bi,
+               bool &small, bool stamp = false);
+// emit[] (jobs of the scan_round before it, want_tabs) decoded to code words and materialised into d_out; jf[q] != 0: job q
+// reads in front of its history.  stamp: phases "blk_emit" and "lz77_copy".
+int emit_round(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkEmit> &emit, uint64_t total_codes, bool small,
+               uint8_t *d_out, std::vector<uint32_t> &jf, bool stamp = false);
+
 }  // namespace lfx

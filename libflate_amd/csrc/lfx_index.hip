@@ -16,26 +16,9 @@
 #include <vector>
 
 #include "../../include/lfx.h"
-#include "lfx_ctx.h"
+#include "lfx_decode_int.h"
 #include "lfx_index.h"
 #include "lfx_abi_guard.h"
-
-#define IX_HIP(expr)                                                                  \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess) {                                                       \
-            c->set_error(std::string(#expr) + ": " + hipGetErrorString(e_));          \
-            return LFX_E_DEVICE;                                                      \
-        }                                                                             \
-    } while (0)
-#define IX_LAUNCH(call)                                                               \
-    do {                                                                              \
-        int e_ = (call);                                                              \
-        if (e_) {                                                                     \
-            c->set_error(std::string(#call) + ": " + hipGetErrorString((hipError_t)e_)); \
-            return LFX_E_DEVICE;                                                      \
-        }                                                                             \
-    } while (0)
 
 namespace lfx {
 
@@ -201,9 +184,9 @@ int idx_copy(Ctx *c, const std::vector<IdxCopy> &copies, std::vector<IdxCopy> &t
     if (tasks.empty()) return LFX_OK;
     int rc;
     if ((rc = c->d_idx_tasks.reserve(sizeof(IdxCopy) * tasks.size()))) return rc;
-    IX_HIP(hipMemcpyAsync(c->d_idx_tasks.p, tasks.data(), sizeof(IdxCopy) * tasks.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_idx_tasks.p, tasks.data(), sizeof(IdxCopy) * tasks.size(), hipMemcpyHostToDevice, c->stream));
     for (size_t t0 = 0; t0 < tasks.size(); t0 += 1u << 30)
-        IX_LAUNCH(launch_idx_copy(c->stream, (const IdxCopy *)c->d_idx_tasks.p + t0, (uint32_t)std::min<size_t>(tasks.size() - t0, 1u << 30)));
+        LAUNCH_TRY(launch_idx_copy(c->stream, (const IdxCopy *)c->d_idx_tasks.p + t0, (uint32_t)std::min<size_t>(tasks.size() - t0, 1u << 30)));
     return LFX_OK;
 }
 
@@ -230,12 +213,12 @@ int idx_record_chain(Ctx *c, const BlkEmit *emit, uint32_t ne, const BlkLanes *d
     }
     if (g.slots.empty()) return LFX_OK;
     const uint32_t n = (uint32_t)g.slots.size();
-    IX_HIP(hipMalloc(&g.dev, 8ull * 2048 * n + 4ull * n));
+    HIP_TRY(hipMalloc(&g.dev, 8ull * 2048 * n + 4ull * n));
     uint32_t *d_slots = (uint32_t *)((uint8_t *)g.dev + 8ull * 2048 * n);
     col.grabs.push_back(std::move(g));
     IdxCollect::Grab &G = col.grabs.back();
-    IX_HIP(hipMemcpyAsync(d_slots, G.slots.data(), 4ull * n, hipMemcpyHostToDevice, c->stream));
-    IX_LAUNCH(launch_idx_lanes(c->stream, d_lanes, d_slots, n, (uint64_t *)G.dev));
+    HIP_TRY(hipMemcpyAsync(d_slots, G.slots.data(), 4ull * n, hipMemcpyHostToDevice, c->stream));
+    LAUNCH_TRY(launch_idx_lanes(c->stream, d_lanes, d_slots, n, (uint64_t *)G.dev));
     return LFX_OK;
 }
 
@@ -294,8 +277,8 @@ int idx_finish(Ctx *c, IdxCollect &col, int format, uint32_t flags, const uint8_
     for (IdxCollect::Grab &g : col.grabs) {
         const uint32_t n = (uint32_t)g.slots.size();
         std::vector<uint64_t> h(2048ull * n);
-        IX_HIP(hipMemcpyAsync(h.data(), g.dev, 8ull * 2048 * n, hipMemcpyDeviceToHost, st));
-        IX_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(h.data(), g.dev, 8ull * 2048 * n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         for (uint32_t s = 0; s < n; s++) {
             const IdxCollect::Grab::Meta &m = g.meta[s];
             for (uint32_t l = m.skip0 ? 1 : 0; l < m.nlanes; l++) {
@@ -359,7 +342,7 @@ int idx_finish(Ctx *c, IdxCollect &col, int format, uint32_t flags, const uint8_
     const uint32_t np = (uint32_t)x->pts.size();
     // ---- windows out of the output, and each point's probe of the input (CRC-32, BTYPE of a block header)
     layout_windows(x);
-    IX_HIP(hipMalloc((void **)&x->d_win, std::max<uint64_t>(x->win_bytes, 16)));
+    HIP_TRY(hipMalloc((void **)&x->d_win, std::max<uint64_t>(x->win_bytes, 16)));
     std::vector<IdxCopy> copies, tasks;
     for (uint32_t i = 0; i < np; i++) {
         const lfx_index_point &p = x->pts[i];
@@ -372,12 +355,12 @@ int idx_finish(Ctx *c, IdxCollect &col, int format, uint32_t flags, const uint8_
     if ((rc = c->d_idx_probe.reserve(16ull * np))) return rc;
     uint64_t *d_bits = (uint64_t *)c->d_idx_probe.p;
     uint32_t *d_crc = (uint32_t *)(d_bits + np), *d_bt = d_crc + np;
-    IX_HIP(hipMemcpyAsync(d_bits, bits.data(), 8ull * np, hipMemcpyHostToDevice, st));
-    IX_LAUNCH(launch_idx_probe(st, d_in, consumed, d_bits, np, d_crc, d_bt));
+    HIP_TRY(hipMemcpyAsync(d_bits, bits.data(), 8ull * np, hipMemcpyHostToDevice, st));
+    LAUNCH_TRY(launch_idx_probe(st, d_in, consumed, d_bits, np, d_crc, d_bt));
     std::vector<uint32_t> crc(np), bt(np);
-    IX_HIP(hipMemcpyAsync(crc.data(), d_crc, 4ull * np, hipMemcpyDeviceToHost, st));
-    IX_HIP(hipMemcpyAsync(bt.data(), d_bt, 4ull * np, hipMemcpyDeviceToHost, st));
-    IX_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(crc.data(), d_crc, 4ull * np, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(bt.data(), d_bt, 4ull * np, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     c->phase("index_windows");
     for (uint32_t i = 0; i < np; i++) {
         x->pts[i].in_crc = crc[i];
@@ -497,7 +480,7 @@ extern "C" int lfx_index_export(lfx_ctx *cc, const lfx_index *idx, void *buf, ui
     if (!buf || cap < sz) return LFX_E_NOSPACE;
     (void)hipSetDevice(c->device);
     std::vector<uint8_t> w(idx->win_bytes);
-    if (idx->win_bytes) IX_HIP(hipMemcpy(w.data(), idx->d_win, idx->win_bytes, hipMemcpyDeviceToHost));
+    if (idx->win_bytes) HIP_TRY(hipMemcpy(w.data(), idx->d_win, idx->win_bytes, hipMemcpyDeviceToHost));
     uint8_t *o = (uint8_t *)buf;
     memset(o, 0, 64);
     memcpy(o, "LFXINDEX", 8);
@@ -592,8 +575,8 @@ int decode_group(Ctx *c, const lfx_index *x, const uint8_t *d_in, uint64_t in_ba
         uint64_t *d_bits = (uint64_t *)c->d_idx_probe.p;
         uint32_t *d_crc = (uint32_t *)(d_bits + ns), *d_bt = d_crc + ns;
         const uint64_t held = std::min<uint64_t>(n, x->info.in_len > in_base ? x->info.in_len - in_base : 0);
-        IX_HIP(hipMemcpyAsync(d_bits, bits.data(), 8ull * ns, hipMemcpyHostToDevice, st));
-        IX_LAUNCH(launch_idx_probe(st, d_in, held, d_bits, ns, d_crc, d_bt));
+        HIP_TRY(hipMemcpyAsync(d_bits, bits.data(), 8ull * ns, hipMemcpyHostToDevice, st));
+        LAUNCH_TRY(launch_idx_probe(st, d_in, held, d_bits, ns, d_crc, d_bt));
         std::vector<IdxCopy> copies, tasks;
         for (const Seg &s : segs) {
             const lfx_index_point &p = x->pts[s.p];
@@ -601,8 +584,8 @@ int decode_group(Ctx *c, const lfx_index *x, const uint8_t *d_in, uint64_t in_ba
         }
         if ((rc = idx_copy(c, copies, tasks))) return rc;
         std::vector<uint32_t> crc(ns);
-        IX_HIP(hipMemcpyAsync(crc.data(), d_crc, 4ull * ns, hipMemcpyDeviceToHost, st));
-        IX_HIP(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(crc.data(), d_crc, 4ull * ns, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         for (uint32_t k = 0; k < ns; k++)
             if (crc[k] != x->pts[segs[k].p].in_crc) {
                 segs[k].live = false;
@@ -612,14 +595,12 @@ int decode_group(Ctx *c, const lfx_index *x, const uint8_t *d_in, uint64_t in_ba
     }
     // ---- rounds: every live segment takes one step (a block from its header, or the rest of a block from a known symbol
     // boundary), bounded by the bits its remaining need is estimated to take; the steps that fit are materialised at once
-    const size_t tab_bytes = blk_tabs_bytes();
     for (;;) {
         std::vector<uint32_t> live;
         for (uint32_t k = 0; k < ns; k++) if (segs[k].live) live.push_back(k);
         if (live.empty()) break;
         const uint32_t nj = (uint32_t)live.size();
         std::vector<BlkJob> bj(nj);
-        uint64_t range_bits = 0;
         for (uint32_t q = 0; q < nj; q++) {
             const Seg &s = segs[live[q]];
             const lfx_index_point &p = x->pts[s.p];
@@ -637,19 +618,10 @@ int decode_group(Ctx *c, const lfx_index *x, const uint8_t *d_in, uint64_t in_ba
             j.warm_bit = 0;
             j.piece = s.in_block ? BLK_PIECE_KNOWN : 1u;
             bj[q] = j;
-            range_bits += e - s.bit;
         }
-        if ((rc = c->d_dec_streams.reserve(sizeof(BlkJob) * nj))) return rc;
-        if ((rc = c->d_dec_state.reserve(sizeof(BlkInfo) * nj))) return rc;
-        if ((rc = c->d_dec_cand.reserve(sizeof(BlkLanes) * (size_t)nj))) return rc;
-        if ((rc = c->d_dec_tabs.reserve(tab_bytes * nj))) return rc;
-        IX_HIP(hipMemcpyAsync(c->d_dec_streams.p, bj.data(), sizeof(BlkJob) * nj, hipMemcpyHostToDevice, st));
-        const bool small = !c->diag.no_small_scan && range_bits / nj < (512ull << 10);
-        IX_LAUNCH(launch_blk_scan(st, d_in, n, (const BlkJob *)c->d_dec_streams.p, nj, (BlkInfo *)c->d_dec_state.p,
-                                  (BlkLanes *)c->d_dec_cand.p, c->d_dec_tabs.p, small));
-        std::vector<BlkInfo> bi(nj);
-        IX_HIP(hipMemcpyAsync(bi.data(), c->d_dec_state.p, sizeof(BlkInfo) * nj, hipMemcpyDeviceToHost, st));
-        IX_HIP(hipStreamSynchronize(st));
+        std::vector<BlkInfo> bi;
+        bool small = false;
+        if ((rc = scan_round(c, d_in, n, bj, true, bi, small))) return rc;
         std::vector<BlkEmit> emit;
         std::vector<uint32_t> owner;
         uint64_t total_codes = 0;
@@ -677,13 +649,9 @@ int decode_group(Ctx *c, const lfx_index *x, const uint8_t *d_in, uint64_t in_ba
                 fail("the segment produces more output than the index says");
                 continue;
             }
-            BlkEmit e{};
-            e.start_bit = s.hdr - base_bit; e.data_bit = r.data_bit; e.code_off = total_codes;
-            e.out_off = s.stage + IDX_WINDOW + s.produced;
-            e.n_out = r.n_out; e.n_codes = r.n_codes; e.nlanes = r.nlanes; e.btype = r.btype; e.cand = q;
-            e.hist = x->pts[s.p].win_len + s.produced;
+            BlkEmit e = blk_emit_of(r, s.hdr - base_bit, q, s.stage + IDX_WINDOW + s.produced, total_codes,
+                                    x->pts[s.p].win_len + s.produced);
             e.preload = e.hist != 0;
-            e.end_limit = r.status == BLK_NO_EOB ? r.end_bit : 0;
             emit.push_back(e);
             owner.push_back(live[q]);
             total_codes += r.n_codes;
@@ -712,23 +680,8 @@ int decode_group(Ctx *c, const lfx_index *x, const uint8_t *d_in, uint64_t in_ba
         }
         const uint32_t ne = (uint32_t)emit.size();
         if (!ne) continue;
-        std::vector<uint32_t> jf(ne, 0);
-        if ((rc = c->d_dec_tmp.reserve(sizeof(BlkEmit) * ne + 4ull * ne + 128))) return rc;
-        if ((rc = c->d_hist.reserve(sizeof(BlkUnits) * (size_t)ne + 64))) return rc;
-        if ((rc = c->d_codes.reserve(4 * std::max<uint64_t>(total_codes, 1)))) return rc;
-        uint32_t *d_flags = (uint32_t *)c->d_dec_tmp.p;
-        uint32_t *d_jf = d_flags + 16;
-        BlkEmit *d_emit = (BlkEmit *)((uint8_t *)c->d_dec_tmp.p + 64 + 4ull * ne + (8 - (4ull * ne) % 8) % 8);
-        IX_HIP(hipMemsetAsync(d_flags, 0, 64 + 4ull * ne, st));
-        IX_HIP(hipMemcpyAsync(d_emit, emit.data(), sizeof(BlkEmit) * ne, hipMemcpyHostToDevice, st));
-        const uint64_t slots = 4ull * (uint64_t)std::max(c->n_cu, 1);
-        const uint32_t unit_target = (uint32_t)std::min<uint64_t>((total_codes + slots - 1) / slots + 1, 0x7FFFFFFFu);
-        IX_LAUNCH(launch_blk_emit(st, d_in, n, d_emit, ne, (const BlkLanes *)c->d_dec_cand.p, (uint32_t *)c->d_codes.p, d_flags,
-                                  (BlkUnits *)c->d_hist.p, unit_target, d_jf, c->d_dec_tabs.p, 17, false, small));
-        IX_LAUNCH(launch_blk_materialize(st, d_in, d_emit, ne, (const BlkLanes *)c->d_dec_cand.p, (const BlkUnits *)c->d_hist.p,
-                                         (const uint32_t *)c->d_codes.p, d_stage, nullptr));
-        IX_HIP(hipMemcpyAsync(jf.data(), d_jf, 4ull * ne, hipMemcpyDeviceToHost, st));
-        IX_HIP(hipStreamSynchronize(st));
+        std::vector<uint32_t> jf;
+        if ((rc = emit_round(c, d_in, n, emit, total_codes, small, d_stage, jf))) return rc;
         for (uint32_t q = 0; q < ne; q++)
             if (jf[q] && segs[owner[q]].status == LFX_OK) {     // a back-reference in front of the point's window
                 Seg &s = segs[owner[q]];
@@ -824,7 +777,7 @@ extern "C" int lfx_index_read_device(lfx_ctx *cc, const lfx_index *idx, const vo
             }
         }
         if ((rc = idx_copy(c, copies, tasks))) return rc;
-        IX_HIP(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
         g0 = g1;
     }
     if (c->n_ev < 16) c->phase("seg_copy");

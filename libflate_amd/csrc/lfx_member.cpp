@@ -193,6 +193,57 @@ int emit_codes(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkEmi
     return LFX_OK;
 }
 
+// ---- block rounds
+int scan_round(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkJob> &bj, bool want_tabs, std::vector<BlkInfo> &bi,
+               bool &small, bool stamp) {
+    hipStream_t st = c->stream;
+    const uint32_t nj = (uint32_t)bj.size();
+    int rc;
+    if ((rc = c->d_dec_streams.reserve(sizeof(BlkJob) * nj))) return rc;
+    if ((rc = c->d_dec_state.reserve(sizeof(BlkInfo) * nj))) return rc;
+    if ((rc = c->d_dec_cand.reserve(sizeof(BlkLanes) * (size_t)nj))) return rc;
+    if (want_tabs && (rc = c->d_dec_tabs.reserve(blk_tabs_bytes() * nj))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_dec_streams.p, bj.data(), sizeof(BlkJob) * nj, hipMemcpyHostToDevice, st));
+    // (ranges of a few tens of KB: the 256-lane instances of the scan and the emit kernel — a 32 KB block in 1024 slices is
+    //  17 symbols a lane; LFX_NO_SMALL_SCAN=1 keeps 1024.  A job that continues a block covers the bits from lo_bit on.)
+    uint64_t range_bits = 0;
+    for (const BlkJob &j : bj) range_bits += j.end_bit - std::max(j.start_bit, j.lo_bit);
+    small = !c->diag.no_small_scan && range_bits / nj < (512ull << 10);
+    LAUNCH_TRY(launch_blk_scan(st, d_in, n, (const BlkJob *)c->d_dec_streams.p, nj, (BlkInfo *)c->d_dec_state.p,
+                               (BlkLanes *)c->d_dec_cand.p, want_tabs ? c->d_dec_tabs.p : nullptr, small));
+    if (stamp) c->phase("blk_scan");
+    bi.resize(nj);
+    HIP_TRY(hipMemcpyAsync(bi.data(), c->d_dec_state.p, sizeof(BlkInfo) * nj, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LFX_OK;
+}
+
+int emit_round(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkEmit> &emit, uint64_t total_codes, bool small,
+               uint8_t *d_out, std::vector<uint32_t> &jf, bool stamp) {
+    hipStream_t st = c->stream;
+    const uint32_t ne = (uint32_t)emit.size();
+    const EmitTmp t = emit_tmp_layout(ne);
+    int rc;
+    if ((rc = c->d_dec_tmp.reserve(t.total))) return rc;
+    if ((rc = c->d_hist.reserve(sizeof(BlkUnits) * (size_t)ne + 64))) return rc;
+    if ((rc = c->d_codes.reserve(4 * std::max<uint64_t>(total_codes, 1)))) return rc;
+    uint8_t *tmp = (uint8_t *)c->d_dec_tmp.p;
+    uint32_t *d_flags = (uint32_t *)(tmp + t.flags), *d_jf = (uint32_t *)(tmp + t.job_flags);
+    BlkEmit *d_emit = (BlkEmit *)(tmp + t.jobs);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, 64 + 4ull * ne, st));
+    HIP_TRY(hipMemcpyAsync(d_emit, emit.data(), sizeof(BlkEmit) * ne, hipMemcpyHostToDevice, st));
+    LAUNCH_TRY(launch_blk_emit(st, d_in, n, d_emit, ne, (const BlkLanes *)c->d_dec_cand.p, (uint32_t *)c->d_codes.p, d_flags,
+                               (BlkUnits *)c->d_hist.p, emit_unit_target(total_codes, c->n_cu), d_jf, c->d_dec_tabs.p, 17, false, small));
+    if (stamp) c->phase("blk_emit");
+    LAUNCH_TRY(launch_blk_materialize(st, d_in, d_emit, ne, (const BlkLanes *)c->d_dec_cand.p, (const BlkUnits *)c->d_hist.p,
+                                      (const uint32_t *)c->d_codes.p, d_out, nullptr));
+    if (stamp) c->phase("lz77_copy");
+    jf.resize(ne);
+    HIP_TRY(hipMemcpyAsync(jf.data(), d_jf, 4ull * ne, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LFX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // the member decode
 

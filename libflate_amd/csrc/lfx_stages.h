@@ -83,6 +83,19 @@ inline std::vector<int32_t> add_alt_jobs(std::vector<BlkJob> &bj, const std::vec
     return alt;
 }
 
+// ---- block rounds (scan_round / emit_round: one block per live stream and round)
+constexpr uint32_t BLOCK_ROUNDS = 4;                 // blocks of a stream the batch's fast path decodes and a members walk follows ...
+constexpr uint64_t MEMBER_WALK_BYTES = 4ull << 20;   // ... and input bytes that walk covers; a member beyond either is "long"
+// The byte the blocks of the member at candidate cand[k], whose DEFLATE data starts at `data`, must end in front of: the next
+// candidate behind `data` (a member's trailer lies in front of the next member's header), at most MEMBER_WALK_BYTES from the
+// member's start, inside d_in[0, n).  A limit <= data: nothing to walk.
+inline uint64_t member_walk_limit(const std::vector<uint64_t> &cand, size_t k, uint64_t data, uint64_t n) {
+    uint64_t lim = std::min<uint64_t>(n, cand[k] + MEMBER_WALK_BYTES);
+    const auto nx = std::upper_bound(cand.begin(), cand.end(), data);
+    if (nx != cand.end() && *nx < lim) lim = *nx;
+    return lim;
+}
+
 // ---- the storing scan's lane regions
 // Every lane of job j stores its code words at temp + temp_off + lane * cap (dwords): cap = half a code per bit of the slice +
 // a head's worth + slack (a slice whose codes average less than two bits overflows, is flagged, and takes the emit kernel);
@@ -118,6 +131,13 @@ inline BlkEmit blk_emit_of(const BlkInfo &r, uint64_t start_bit, uint32_t slot, 
 inline uint32_t emit_unit_target(uint64_t total_codes, int n_cu) {
     const uint64_t slots = 4ull * (uint64_t)std::max(n_cu, 1);
     return (uint32_t)std::min<uint64_t>((total_codes + slots - 1) / slots + 1, 0x7FFFFFFFu);
+}
+// emit_round's d_dec_tmp for `ne` emit jobs: 64 flag bytes, a flag per job, padding to 8, the jobs (byte offsets)
+struct EmitTmp { uint64_t flags, job_flags, jobs, total; };
+inline EmitTmp emit_tmp_layout(uint32_t ne) {
+    EmitTmp t{0, 64, (64 + 4ull * ne + 7) & ~7ull, 0};
+    t.total = t.jobs + sizeof(BlkEmit) * (uint64_t)ne;
+    return t;
 }
 // marker units (used only when blocks read earlier blocks): two symbol units are resident per CU and the
 // symbol kernel's time does not depend on the unit size as long as every slot has a unit, while every

@@ -1,7 +1,8 @@
 // CPU: the host arithmetic of the member decode's stages (libflate_amd/csrc/lfx_stages.h) over seeded random ranges —
 // the pieces of a range tile it exactly (no gap, no overlap, interior cuts a multiple of 64 bits behind the range's start,
 // warm-ups that never reach in front of it), their number is the one the split formula gives, and the storing scan's lane
-// regions never overlap.
+// regions never overlap; the range a member's walk may end in equals a plain re-statement over random candidate lists; and
+// the parts of emit_round's d_dec_tmp never overlap, for every job count up to 5000.
 #include <cstdio>
 #include <random>
 
@@ -29,9 +30,19 @@ static int check_tiling(const std::vector<BlkJob> &jobs, size_t from, uint64_t s
     return (int)(jobs.size() - from);
 }
 
+// member_walk_limit, re-stated: the first candidate behind `data`, the walk's byte budget from the member's start, the input's end
+static uint64_t plain_walk_limit(const std::vector<uint64_t> &cand, size_t k, uint64_t data, uint64_t n) {
+    uint64_t lim = n;
+    if (cand[k] + MEMBER_WALK_BYTES < lim) lim = cand[k] + MEMBER_WALK_BYTES;
+    for (uint64_t x : cand)
+        if (x > data) { if (x < lim) lim = x; break; }
+    return lim;
+}
+
 int main() {
-    std::mt19937_64 rng(11);
+    std::mt19937_64 rng(11), rng2(12);      // (rng2: the checks added later draw from a stream of their own)
     int cases = 0;
+    int seen_eq = 0, seen_last = 0, seen_near_end = 0, seen_nothing = 0, seen_next = 0, seen_budget = 0;
     for (int it = 0; it < 20000; it++) {
         // a stream of `span` bits for `n_cu` CUs, a candidate range inside it
         const int n_cu = (int)(1 + rng() % 320);
@@ -84,8 +95,47 @@ int main() {
         if (at != dwords) { printf("case %d: regions take %llu dwords, reported %llu\n", it, (unsigned long long)at, (unsigned long long)dwords); return 1; }
         clear_store_regions(bj.data(), (uint32_t)bj.size());
         for (const BlkJob &j : bj) if (j.temp_off || j.cap) { printf("case %d: region not cleared\n", it); return 1; }
+        // ---- the range a member's walk may end in: sorted candidates (gaps from a few bytes to several walk budgets), a
+        // header of 0 bytes up to more than the budget, an input that ends anywhere from inside the header on
+        {
+            std::vector<uint64_t> cand;
+            uint64_t at = rng2() % 4096;
+            const size_t ncand = 1 + rng2() % 40;
+            for (size_t i = 0; i < ncand; i++) { cand.push_back(at); at += 1 + rng2() % (1ull << (2 + rng2() % 23)); }
+            const size_t k = rng2() % 4 == 0 ? ncand - 1 : rng2() % ncand;
+            uint64_t hdr = rng2() % 4 == 0 ? 0 : 10 + rng2() % (1ull << (4 + rng2() % 20));
+            if (k + 1 < ncand && rng2() % 8 == 0) hdr = cand[k + 1] - cand[k];         // (the data starts AT a later candidate)
+            const uint64_t data = cand[k] + hdr;
+            const uint64_t n = rng2() % 4 == 0 ? cand[k] + 1 + rng2() % (hdr + 4096) : cand.back() + 1 + rng2() % (16ull << 20);
+            const uint64_t lim = member_walk_limit(cand, k, data, n), want_lim = plain_walk_limit(cand, k, data, n);
+            if (lim != want_lim) { printf("case %d: walk limit %llu, re-stated %llu\n", it, (unsigned long long)lim, (unsigned long long)want_lim); return 1; }
+            if (lim > n || lim > cand[k] + MEMBER_WALK_BYTES) { printf("case %d: walk limit out of range\n", it); return 1; }
+            seen_eq += std::binary_search(cand.begin(), cand.end(), data);
+            seen_last += k + 1 == ncand;
+            seen_near_end += n < cand[k] + MEMBER_WALK_BYTES && lim == n;
+            seen_nothing += lim <= data;
+            seen_next += lim < n && lim < cand[k] + MEMBER_WALK_BYTES;
+            seen_budget += lim == cand[k] + MEMBER_WALK_BYTES && lim < n;
+        }
         cases++;
     }
-    printf("plan_stages ok: %d cases\n", cases);
+    if (!seen_eq || !seen_last || !seen_near_end || !seen_nothing || !seen_next || !seen_budget) {
+        printf("walk limit: a kind of case never came up (%d %d %d %d %d %d)\n", seen_eq, seen_last, seen_near_end, seen_nothing, seen_next, seen_budget);
+        return 1;
+    }
+    // ---- emit_round's d_dec_tmp: 64 flag bytes, the job flags, the jobs — disjoint, the jobs 8-byte aligned, and no larger
+    // than sizeof(BlkEmit) * ne + 4 * ne + 128 (what the callers of the round reserved before the layout had a home)
+    int layouts = 0;
+    for (uint32_t ne = 1; ne <= 5000; ne++) {
+        const EmitTmp t = emit_tmp_layout(ne);
+        const bool disjoint = t.flags + 64 <= t.job_flags && t.job_flags + 4ull * ne <= t.jobs && t.jobs + sizeof(BlkEmit) * (uint64_t)ne <= t.total;
+        if (!disjoint || t.flags % 4 || t.job_flags % 4 || t.jobs % 8 || t.total > sizeof(BlkEmit) * (uint64_t)ne + 4ull * ne + 128) {
+            printf("layout of %u emit jobs: flags %llu, job flags %llu, jobs %llu, total %llu\n", ne, (unsigned long long)t.flags,
+                   (unsigned long long)t.job_flags, (unsigned long long)t.jobs, (unsigned long long)t.total);
+            return 1;
+        }
+        layouts++;
+    }
+    printf("plan_stages ok: %d cases, %d layouts\n", cases, layouts);
     return 0;
 }

@@ -550,7 +550,8 @@ def test_decode_stage_arithmetic_tiles_ranges_and_regions(tmp_path):
     """The member decode's host arithmetic (libflate_amd/csrc/lfx_stages.h: no HIP call, a plain host compiler builds it).
     tests/c/plan_stages.cpp, over 20000 seeded random ranges: the pieces of a range tile it exactly — no gap, no overlap,
     interior cuts a multiple of 64 bits behind its start — their number is what the split formula gives, alternative scan
-    jobs widen their candidate's range, and the storing scan's lane regions never overlap."""
+    jobs widen their candidate's range, and the storing scan's lane regions never overlap.  Per case also the byte range a
+    member's walk may end in, against a plain re-statement; and for 1...5000 emit jobs the layout of a block round's scratch."""
     import shutil
     import subprocess
     gxx = shutil.which("g++")
@@ -559,4 +560,4 @@ def test_decode_stage_arithmetic_tiles_ranges_and_regions(tmp_path):
     exe = str(tmp_path / "plan_stages")
     subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "c", "plan_stages.cpp")], check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "plan_stages ok: 20000 cases" in out.stdout, out.stdout[-400:]
+    assert out.returncode == 0 and "plan_stages ok: 20000 cases, 5000 layouts" in out.stdout, out.stdout[-400:]
