@@ -16,6 +16,7 @@
 
 #include "lfx_ctx.h"
 #include "lfx_device.h"
+#include "lfx_encode_int.h"
 #include "lfx_huff.h"
 #include "lfx_index.h"
 #include "lfx_plan.h"
@@ -199,15 +200,6 @@ extern "C" uint64_t lfx_encode_bound(uint64_t n, const lfx_encode_opts *o, const
 // context
 namespace lfx {
 
-#define HIP_TRY(expr)                                                                 \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess) {                                                       \
-            c->set_error(std::string(#expr) + ": " + hipGetErrorString(e_));          \
-            return LFX_E_DEVICE;                                                      \
-        }                                                                             \
-    } while (0)
-
 int DevBuf::reserve(size_t bytes) {
     if (bytes <= cap) return 0;
     if (p) (void)hipFree(p);
@@ -359,396 +351,7 @@ extern "C" int lfx_ctx_last_timing(lfx_ctx *cc, lfx_timing *t) try {
 } LFX_ABI_CATCH
 
 // ------------------------------------------------------------------------------------------------
-// encode core
-namespace lfx {
-
-// Stage A: plan upload → match → parse → histogram → Huffman (+ checksum).  Leaves everything the
-// emit stage needs in the context.
-int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *d_in, uint64_t n,
-                   int ck_mode, const HostCodes *hc) {
-    const bool want_checksum = ck_mode != 0;   // 1: CRC-32 (gzip), 2: Adler-32 (zlib), 3: both (a shard: the caller folds either)
-    (void)hipSetDevice(c->device);
-    hipStream_t st = c->stream;
-    c->n_ev = 0;
-    c->phase("start");
-    for (const ChunkDesc &ch : plan.chunks)
-        if (ch.len >= (1ull << 32) - 4) {
-            c->set_error("an LZ77 chunk of 4 GiB or more is outside the reference's domain (u32 positions, default.rs:78)");
-            return LFX_E_ARG;
-        }
-    const uint32_t nchunks = (uint32_t)plan.chunks.size(), nblocks = (uint32_t)plan.blocks.size();
-    // ---- which candidate stage: lfx_match3.hip unless it once reported a lane-order violation (or LFX_MATCH_V1 is set)
-    const bool match_v1 = c->force_match_v1 || c->diag.match_v1;
-    if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)
-    // A segment is one workgroup's serial walk (plus a 32 KiB warm-up when it does not start a chunk).  Small
-    // inputs are cut finer so that the GPU still fills: halve the segment length until there are >= 512 of them
-    // (never below 32 Ki positions: the warm-up would dominate).
-    std::vector<SegDesc> segs;
-    if (!hc) {
-        uint64_t seg_len = SEG_POSITIONS;
-        for (;;) {
-            uint64_t cnt = 0;
-            for (const ChunkDesc &ch : plan.chunks)
-                if (!(ch.flags & CH_LITERALS) && ch.len > 3) cnt += div_up(ch.len - 3, seg_len);
-            if (cnt >= 512 || seg_len <= 32768) break;
-            seg_len /= 2;
-        }
-        for (uint32_t ci = 0; ci < nchunks; ci++) {
-            const ChunkDesc &ch = plan.chunks[ci];
-            if (ch.flags & CH_LITERALS) continue;
-            for (uint64_t s = 0; s + 3 < ch.len; s += seg_len)
-                segs.push_back(SegDesc{ci, (uint32_t)s, (uint32_t)std::min<uint64_t>(seg_len, ch.len - s), 0});
-        }
-    }
-    // lfx_match5: every segment keeps the final links of its positions — its warm-up included — in a region of its own
-    uint64_t lnk_units = 0;
-    for (SegDesc &sg : segs) {
-        if (lnk_units > 0xFFFFFFFFull) { c->set_error("input too large for the link scratch"); return LFX_E_ARG; }
-        sg.lnk_base = (uint32_t)lnk_units;
-        lnk_units += div_up((uint64_t)sg.len + std::min<uint64_t>(sg.start, MAX_WINDOW) + 4, 64);
-        lnk_units = (lnk_units + 1) & ~1ull;   // (even: lfx_match7 stores two ballot words, one per unit, as 16 bytes)
-    }
-    // workgroups of the parse walk: PARSE_WG_SEGS consecutive segments of one chunk each
-    std::vector<ParseWg> pwgs;
-    for (uint32_t ci = 0; ci < nchunks && !hc; ci++) {
-        const ChunkDesc &ch = plan.chunks[ci];
-        if (ch.flags & CH_LITERALS) continue;
-        for (uint32_t s = 0; s < ch.n_seg; s += PARSE_WG_SEGS) pwgs.push_back(ParseWg{ci, s});
-    }
-    // XCD-aware launch order: workgroup i runs on XCD i mod 8, and every XCD has an L2 of its own.  A workgroup stages the
-    // 32 KiB window in front of its 13 KiB of positions — the positions of its two or three left neighbours — so each XCD
-    // takes one contiguous eighth of the list and finds those bytes (and its own `cd` lines) in ITS L2 instead of
-    // fetching them over the fabric again (slots behind the end of an eighth are marked empty).
-    if (pwgs.size() > 8) {
-        const size_t nl = pwgs.size(), per = (nl + 7) / 8;
-        std::vector<ParseWg> phys(per * 8);
-        for (size_t i = 0; i < phys.size(); i++) {
-            const size_t l = (i % 8) * per + i / 8;
-            phys[i] = (i / 8 < per && l < nl && l / per == i % 8) ? pwgs[l] : ParseWg{0xFFFFFFFFu, 0u};
-        }
-        pwgs.swap(phys);
-    }
-    c->cur_nchunks = nchunks;
-    c->cur_nblocks = nblocks;
-    c->cur_ntiles = plan.n_tiles;
-    c->cur_n = n;
-    c->cur_in = d_in;
-    int rc;
-    if ((rc = c->d_chunks.reserve(sizeof(ChunkDesc) * std::max<size_t>(nchunks, 1)))) return rc;
-    if ((rc = c->d_blocks.reserve(sizeof(BlockDesc) * std::max<size_t>(nblocks, 1)))) return rc;
-    if ((rc = c->d_segs.reserve(sizeof(SegDesc) * std::max<size_t>(segs.size(), 1)))) return rc;
-    if ((rc = c->d_pwgs.reserve(sizeof(ParseWg) * std::max<size_t>(pwgs.size(), 1)))) return rc;
-    if (!hc && (rc = c->d_cd.reserve(2 * n + 64))) return rc;                   // candidate distances, 16 bits per position
-    if (!hc && !match_v1 && (rc = c->d_glnk.reserve(264 * std::max<uint64_t>(lnk_units, 1)))) return rc;   // lfx_match7: link records (4 bytes) + ballot words (8 bytes per 64); lfx_match5: links (2 bytes)
-    if (!hc && !match_v1 && (rc = c->d_ucount.reserve(4 * std::max<size_t>(segs.size(), 1)))) return rc;   // lfx_match7: unresolved positions per segment
-    if (!hc && match_v1 && (rc = c->d_md.reserve(4 * std::max<uint64_t>(n, 1)))) return rc;   // first-generation kernel: (length, distance) words
-    if ((rc = c->d_codes.reserve(4 * std::max<uint64_t>(plan.n_codes_cap, 1)))) return rc;
-    if ((rc = c->d_ncodes.reserve(4 * std::max<size_t>(nchunks, 1)))) return rc;
-    if ((rc = c->d_vis.reserve(8 * std::max<uint64_t>(plan.n_vis, 1)))) return rc;
-    if ((rc = c->d_segtmp.reserve(24ull * std::max<uint32_t>(plan.n_segs, 1)))) return rc;
-    if (!hc && (rc = c->d_stage.reserve(4ull * (n + 64)))) return rc;   // code words staged by the speculative parse walk
-    if ((rc = c->d_chunkmap.reserve(4ull * (plan.n_tiles + plan.n_segs + 2)))) return rc;   // tile → chunk, segment → chunk
-    if ((rc = c->d_hist.reserve(4ull * 320 * std::max<size_t>(nblocks, 1)))) return rc;
-    if ((rc = c->d_bc.reserve(sizeof(BlockCodes) * std::max<size_t>(nblocks, 1)))) return rc;
-    if ((rc = c->d_block_start.reserve(8 * std::max<size_t>(nblocks, 1)))) return rc;
-    if ((rc = c->d_tile_bits.reserve(4 * std::max<uint64_t>(plan.n_tiles, 1)))) return rc;
-    if ((rc = c->d_tile_start.reserve(8 * std::max<uint64_t>(plan.n_tiles, 1)))) return rc;
-    const uint64_t nspans = ck_nspans(n);   // partial results of the checksum kernels
-    if ((rc = c->d_ck.reserve(12 * nspans))) return rc;
-    if ((rc = c->d_res.reserve(256))) return rc;
-    if ((rc = c->d_small.reserve(70000))) return rc;
-
-    // plan tables: uploaded from shadows kept on the context (they outlive the asynchronous copies: no synchronisation),
-    // and not at all when the same table already sits in the same device buffer (an encode loop over equal-sized inputs)
-    auto upload = [&](int slot, DevBuf &b, const void *src, size_t bytes) -> hipError_t {
-        std::vector<uint8_t> &sh = c->up_shadow[slot];
-        const uint64_t tag = (uint64_t)(uintptr_t)b.p ^ ((uint64_t)b.gen << 48) ^ (1ull << 63);
-        if (c->up_dev[slot] == tag && sh.size() == bytes && (bytes == 0 || memcmp(sh.data(), src, bytes) == 0)) return hipSuccess;
-        sh.assign((const uint8_t *)src, (const uint8_t *)src + bytes);
-        c->up_dev[slot] = tag;
-        return bytes ? hipMemcpyAsync(b.p, sh.data(), bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-    };
-    HIP_TRY(upload(0, c->d_chunks, plan.chunks.data(), sizeof(ChunkDesc) * nchunks));
-    HIP_TRY(upload(1, c->d_blocks, plan.blocks.data(), sizeof(BlockDesc) * nblocks));
-    HIP_TRY(upload(2, c->d_segs, segs.data(), sizeof(SegDesc) * segs.size()));
-    HIP_TRY(upload(3, c->d_pwgs, pwgs.data(), sizeof(ParseWg) * pwgs.size()));
-    // the blocks' symbol counters, the result record and the match stage's per-segment counts are cleared by the call's first
-    // kernel (three fill operations in front of the match kernel before: 22 us of a 4.6 ms step)
-    const bool ucount_here = !hc && !match_v1 && !c->diag.match_v5;
-    const ZeroSpan z_hist{(uint32_t *)c->d_hist.p, (uint32_t)(320 * std::max<size_t>(nblocks, 1))}, z_res{(uint32_t *)c->d_res.p, 64u},
-        z_ucount{ucount_here ? (uint32_t *)c->d_ucount.p : nullptr, ucount_here ? (uint32_t)std::max<size_t>(segs.size(), 1) : 0u};
-    c->phase("upload");
-    uint32_t *tile_map = (uint32_t *)c->d_chunkmap.p, *seg_map = tile_map + plan.n_tiles;
-    c->cur_tile_map = tile_map;
-    if (int e_ = launch_chunk_maps(st, (const ChunkDesc *)c->d_chunks.p, nchunks, plan.n_tiles, plan.n_segs, tile_map, seg_map, z_hist,
-                                   z_res, z_ucount)) {
-        c->set_error(hipGetErrorString((hipError_t)e_));
-        return LFX_E_DEVICE;
-    }
-
-#define LAUNCH_TRY(call)                                                              \
-    do {                                                                              \
-        int e_ = (call);                                                              \
-        if (e_) {                                                                     \
-            c->set_error(std::string(#call) + ": " + hipGetErrorString((hipError_t)e_)); \
-            return LFX_E_DEVICE;                                                      \
-        }                                                                             \
-    } while (0)
-
-    uint64_t *mdbg = nullptr;
-    if (c->diag.debug) mdbg = (uint64_t *)((uint8_t *)c->d_small.p + 32768);   // per-wavefront cycle counters of workgroup 0
-    bool fused_hist = false;      // the parse counted the blocks' symbols (no histogram_kernel)
-    bool forked = false;          // the first half of the checksum's sweep is on the side stream already
-    uint32_t emit_per = 0, emit_parts = 0;
-    if (hc) {
-        // the caller's own Lz77Encode produced the code words (EncodeOptions::with_lz77(E), encode.rs:59-65): they take the
-        // place of the match + parse stages' output — one chunk per block, EndOfBlock included; everything from the
-        // histogram on (CompressBuf::flush, encode.rs:416-425) runs as for the built-in encoders
-        if (hc->n_codes) HIP_TRY(hipMemcpyAsync(c->d_codes.p, hc->codes, 4ull * hc->n_codes, hipMemcpyHostToDevice, st));
-        if (nchunks) HIP_TRY(hipMemcpyAsync(c->d_ncodes.p, hc->chunk_codes, 4ull * nchunks, hipMemcpyHostToDevice, st));
-        c->phase("codes_upload");
-    } else {
-    uint32_t *d_match_flags = (uint32_t *)((uint8_t *)c->d_res.p + offsetof(EncodeResult, match_flags));
-    uint16_t *d_cd = (uint16_t *)c->d_cd.p;
-    if (match_v1) {
-        LAUNCH_TRY(launch_match(st, d_in, n, (const ChunkDesc *)c->d_chunks.p, (const SegDesc *)c->d_segs.p,
-                                (uint32_t)segs.size(), po.window_size, po.max_length, (uint32_t *)c->d_md.p, mdbg));
-        LAUNCH_TRY(launch_md_to_cd(st, (const uint32_t *)c->d_md.p, n, d_cd));
-    } else {
-        if (!c->diag.match_v5) {
-            // lfx_match7: the candidate kernel, then the positions it leaves open (0.5 % of a text): ballot words → lists → walks.
-            // (Measured, round 5: the segments in four parts, the resolver of a part on the side stream beside the next part's
-            //  kernel — `LFX_MATCH_PARTS=4` — 1.10 ms against 1.15 in one piece at 256 MiB: a part of 256 workgroups ends with
-            //  its slowest segment, and the compaction waits for slots behind the kernel.  The resolver with four walks in
-            //  flight per lane made the overlap pointless.)
-            const uint32_t ns = (uint32_t)segs.size();
-            const uint32_t ncu = (uint32_t)std::max(c->n_cu, 1);
-            const uint32_t want_parts = (uint32_t)std::max(c->diag.match_parts, 1);
-            const uint32_t parts = ns >= 2 * ncu ? std::min<uint32_t>(std::min<uint32_t>(4, want_parts), ns / ncu) : 1;
-            const SegDesc *dsegs = (const SegDesc *)c->d_segs.p;
-            uint32_t *d_glnk = (uint32_t *)c->d_glnk.p;
-            uint64_t *d_umask = (uint64_t *)((uint8_t *)c->d_glnk.p + 256 * std::max<uint64_t>(lnk_units, 1));
-            uint32_t *d_ucount = (uint32_t *)c->d_ucount.p;
-            // (d_ucount: cleared by the call's first kernel, launch_chunk_maps above)
-            for (uint32_t k = 0; k < parts; k++) {
-                const uint32_t s0 = (uint32_t)((uint64_t)ns * k / parts), s1 = (uint32_t)((uint64_t)ns * (k + 1) / parts);
-                LAUNCH_TRY(launch_match7(st, d_in, n, (const ChunkDesc *)c->d_chunks.p, dsegs + s0, s1 - s0, po.window_size, d_cd,
-                                         d_glnk, d_umask, d_match_flags, k == 0 ? mdbg : nullptr));
-                if (parts == 1 && c->timing_fine()) c->phase("lz77_cand");
-                hipStream_t rs = parts > 1 ? c->side_stream : st;
-                if (parts > 1) {
-                    HIP_TRY(hipEventRecord(c->ev_part[k], st));
-                    HIP_TRY(hipStreamWaitEvent(rs, c->ev_part[k], 0));
-                }
-                LAUNCH_TRY(launch_resolve7(rs, (const ChunkDesc *)c->d_chunks.p, dsegs + s0, s1 - s0, po.window_size, d_cd,
-                                           d_glnk, d_umask, (uint32_t *)c->d_stage.p, d_ucount + s0, (uint32_t)std::max(c->diag.r7_cap, 0)));
-            }
-            if (parts > 1) {
-                HIP_TRY(hipEventRecord(c->ev_res, c->side_stream));
-                HIP_TRY(hipStreamWaitEvent(st, c->ev_res, 0));
-            }
-        }
-        else
-            LAUNCH_TRY(launch_match5(st, d_in, n, (const ChunkDesc *)c->d_chunks.p, (const SegDesc *)c->d_segs.p,
-                                     (uint32_t)segs.size(), po.window_size, d_cd, (uint16_t *)c->d_glnk.p, d_match_flags, mdbg));
-    }
-    if (mdbg) {
-        uint64_t hv[256];
-        (void)hipMemcpy(hv, mdbg, sizeof hv, hipMemcpyDeviceToHost);
-        const bool v5 = !match_v1 && c->diag.match_v5, v7 = !match_v1 && !c->diag.match_v5;
-        if (v7) {
-            // lfx_match7: wave 0 = exchange on head, wave 1 = exchange on second, waves 2..15 = helpers
-            for (int w = 0; w < 16; w++)
-                fprintf(stderr, "[lfx] match7 wave%d: work=%llu barrier-wait=%llu tiles=%llu\n", w, (unsigned long long)hv[w * 8],
-                        (unsigned long long)hv[w * 8 + 1], (unsigned long long)hv[w * 8 + 5]);
-        } else {
-            for (int w = 0; w < 16; w++)
-                fprintf(stderr, "[lfx] match%s wave%d: %s=%llu %s=%llu wait=%llu tiles=%llu\n", match_v1 ? "1" : "5", w,
-                        match_v1 ? "load" : "phaseA", (unsigned long long)hv[w * 8], match_v1 ? "work" : "phaseB",
-                        (unsigned long long)hv[w * 8 + 1], (unsigned long long)hv[w * 8 + 2], (unsigned long long)hv[w * 8 + 5]);
-        }
-        if (v5) {
-            uint64_t handed = 0;
-            for (int w = 1; w < 16; w++) handed += hv[128 + w * 8 + 5];
-            fprintf(stderr, "[lfx] match5 workgroup 0: %llu walks handed over to wave 0 of %llu positions; wave 0 waited %llu cycles for their loads\n",
-                    (unsigned long long)handed, (unsigned long long)hv[5] * 960ull, (unsigned long long)hv[6]);
-            for (int w = 1; w < 16; w++)
-                fprintf(stderr, "[lfx] match5 wave%d loop trips: sum=%u max=%u tiles>4=%u tiles>8=%u\n", w, (unsigned)hv[w * 8 + 3],
-                        (unsigned)(hv[w * 8 + 3] >> 32), (unsigned)hv[w * 8 + 4], (unsigned)(hv[w * 8 + 4] >> 32));
-        }
-    }
-    c->phase(c->timing_fine() ? "lz77_resolve" : "lz77_match");
-    if (c->diag.debug && getenv("LFX_DUMP_SEG")) {
-        // diagnostics: the parse state of one segment behind the walk, behind fixseg and at the end
-        const uint32_t sg = (uint32_t)atoi(getenv("LFX_DUMP_SEG"));
-        for (int stage_no = 1; stage_no <= 3 && sg < plan.n_segs; stage_no++) {
-            LAUNCH_TRY(launch_parse(st, d_in, n, (const ChunkDesc *)c->d_chunks.p, nchunks, plan.n_segs, (const ParseWg *)c->d_pwgs.p,
-                                    (uint32_t)pwgs.size(), d_cd, po.max_length, (uint64_t *)c->d_vis.p, (uint32_t *)c->d_segtmp.p,
-                                    (uint32_t *)c->d_codes.p, (uint32_t *)c->d_ncodes.p, (uint32_t *)c->d_stage.p, seg_map, stage_no % 3));
-            (void)hipStreamSynchronize(st);
-            uint64_t v[4];
-            uint32_t t[6];
-            uint16_t cdv[64];
-            (void)hipMemcpy(v, (uint64_t *)c->d_vis.p + (uint64_t)sg * 64, sizeof v, hipMemcpyDeviceToHost);
-            for (int q = 0; q < 6; q++) (void)hipMemcpy(&t[q], (uint32_t *)c->d_segtmp.p + (size_t)q * plan.n_segs + sg, 4, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(cdv, d_cd + (uint64_t)sg * PARSE_SEG, sizeof cdv, hipMemcpyDeviceToHost);
-            fprintf(stderr, "[lfx] seg %u stage %d: vis %016llx %016llx %016llx %016llx exit=%u count=%u off=%u exit2=%u mpos=%u kspec=%u\n", sg,
-                    stage_no, (unsigned long long)v[0], (unsigned long long)v[1], (unsigned long long)v[2], (unsigned long long)v[3], t[0],
-                    t[1], t[2], t[3], t[4], t[5]);
-            if (stage_no == 1) { fprintf(stderr, "[lfx]  cd:"); for (int q = 0; q < 64; q++) fprintf(stderr, " %u", cdv[q]); fprintf(stderr, "\n"); }
-        }
-    }
-    // The blocks' symbol counts are taken by the kernel that writes the code words (parse_emit_hist_kernel): a grid of
-    // nchunks x (workgroups of the longest chunk), about eight workgroups per CU in all.  A chunk list of very unequal chunks
-    // (a few huge ones among thousands of small ones) would launch mostly empty workgroups: histogram_kernel counts then.
-    {
-        const uint32_t target = PARSE_EMIT_WG_PER_CU * (uint32_t)std::max(c->n_cu, 1);
-        uint32_t per = (uint32_t)div_up(std::max<uint32_t>(plan.n_segs, 1), target);
-        per = (per + PARSE_EMIT_WAVES - 1) / PARSE_EMIT_WAVES * PARSE_EMIT_WAVES;
-        uint32_t max_segs = 0;
-        uint64_t useful = 0;
-        for (uint32_t ci = 0; ci < nchunks; ci++) {
-            max_segs = std::max(max_segs, plan.chunks[ci].n_seg);
-            useful += div_up(plan.chunks[ci].n_seg, per);
-        }
-        const uint64_t parts = div_up(max_segs, per);
-        fused_hist = !c->diag.hist_separate && parts <= 65535 && (uint64_t)nchunks * parts <= 4 * useful + 4096;
-        emit_per = per;
-        emit_parts = (uint32_t)parts;
-    }
-    // (fine timing: the walk kernel in a bracket of its own — the same launches in two calls)
-    for (int part = c->timing_fine() ? 1 : 0; part <= (c->timing_fine() ? 2 : 0); part++) {
-        LAUNCH_TRY(launch_parse(st, d_in, n, (const ChunkDesc *)c->d_chunks.p, nchunks, plan.n_segs, (const ParseWg *)c->d_pwgs.p,
-                                (uint32_t)pwgs.size(), d_cd, po.max_length, (uint64_t *)c->d_vis.p, (uint32_t *)c->d_segtmp.p,
-                                (uint32_t *)c->d_codes.p, (uint32_t *)c->d_ncodes.p, (uint32_t *)c->d_stage.p, seg_map, part == 1 ? 1 : 0,
-                                mdbg ? mdbg + 256 : nullptr, fused_hist ? (uint32_t *)c->d_hist.p : nullptr, emit_per, emit_parts,
-                                want_checksum ? c->ev_fork : nullptr, d_match_flags, part == 2 ? 1 : 0));
-        if (part == 1) c->phase("lz77_walk");
-    }
-    if (want_checksum) {
-        // the first half of the container checksum's sweep: on the side stream from behind the walk kernel on, beside the
-        // chaining kernels (one wavefront per segment and a handful of steps each: they leave most of the GPU idle); the
-        // second half beside the Huffman kernel, below.  (Measured, round 6: all of it here ran into parse_emit — both
-        // want the memory system — parse + Huffman 1.13 ms; all of it behind the parse no longer fits under the Huffman
-        // kernel now that the histogram kernel is gone.)
-        uint32_t *ck = (uint32_t *)c->d_ck.p;
-        HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
-        LAUNCH_TRY(launch_checksum_part(c->side_stream, d_in, n, ck, ck + nspans, ck + 2 * nspans, (EncodeResult *)c->d_res.p, ck_mode, 0, 2));
-        forked = true;
-    }
-    if (mdbg) {
-        uint64_t hv[32];
-        (void)hipMemcpy(hv, mdbg + 256, sizeof hv, hipMemcpyDeviceToHost);
-        for (int w = 0; w < 4; w++)
-            fprintf(stderr, "[lfx] walk wave%d: fill=%llu spec=%llu resolve+chain=%llu emit=%llu cycles\n", w, (unsigned long long)hv[w * 8],
-                    (unsigned long long)hv[w * 8 + 1], (unsigned long long)hv[w * 8 + 2], (unsigned long long)hv[w * 8 + 3]);
-    }
-    c->phase(c->timing_fine() ? "lz77_chain" : "lz77_parse");
-    }   // !hc
-    if (want_checksum) {
-        // the container checksum reads only the input: it runs on the side stream, beside the parse's chaining kernels
-        // (one wavefront per segment, a handful of steps each) and the one-workgroup-per-block Huffman kernel, which leave
-        // most of the GPU idle (the fork: behind the walk kernel, launch_parse)
-        uint32_t *ck = (uint32_t *)c->d_ck.p;
-        HIP_TRY(hipEventRecord(c->ev_fork, st));
-        HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
-        if (forked) LAUNCH_TRY(launch_checksum_part(c->side_stream, d_in, n, ck, ck + nspans, ck + 2 * nspans, (EncodeResult *)c->d_res.p, ck_mode, 1, 2));
-        else LAUNCH_TRY(launch_checksum(c->side_stream, d_in, n, ck, ck + nspans, ck + 2 * nspans, (EncodeResult *)c->d_res.p, ck_mode));
-        HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
-    }
-    // enough workgroups to fill the GPU even when there are few chunks (schedule S1: one)
-    // (more workgroups per chunk were measured slower at 1024 chunks: 8 per chunk 0.23 ms against 0.20 ms for one —
-    //  every workgroup ends with a global atomic per non-zero counter)
-    uint32_t split = nchunks && nchunks < 1024 ? std::min<uint32_t>(1024, 2048 / nchunks + 1) : 1;
-    if (!fused_hist)       // (a caller's own code words, LFX_HIST_SEPARATE, very unequal chunks)
-        LAUNCH_TRY(launch_histogram(st, (const ChunkDesc *)c->d_chunks.p, nchunks, split, (const uint32_t *)c->d_codes.p,
-                                    (const uint32_t *)c->d_ncodes.p, (uint32_t *)c->d_hist.p));
-    c->phase("histogram");
-    LAUNCH_TRY(launch_huffman(st, (const BlockDesc *)c->d_blocks.p, nblocks, (const uint32_t *)c->d_hist.p,
-                              (BlockCodes *)c->d_bc.p, mdbg ? mdbg + 512 : nullptr));
-    c->phase("huffman");
-    if (mdbg) {
-        uint64_t hv[24];
-        (void)hipMemcpy(hv, mdbg + 512, sizeof hv, hipMemcpyDeviceToHost);
-        static const char *nm[10] = {"lit: rank sort", "lit: depth", "lit: package-merge", "lit: widths", "lit: codes", "dist tree", "run lengths",
-                                     "code-length tree", "header bits", "body size"};
-        fprintf(stderr, "[lfx] huffman block 0 (cycles):");
-        for (int k = 0; k < 10; k++) fprintf(stderr, " %s=%llu", nm[k], (unsigned long long)(hv[k + 1] - hv[k]));
-        fprintf(stderr, "\n");
-    }
-    if (want_checksum) {
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
-        c->phase("checksum");
-    }
-    return LFX_OK;
-}
-
-int encode_emit(Ctx *c, int format, bool with_trailer, uint32_t trailer_check, bool use_device_check, uint64_t total_n,
-                const uint8_t *prefix, uint32_t prefix_len, uint64_t start_bit, uint8_t *d_out, uint64_t cap,
-                EncodeResult *host_res, EncodeResult *async_slot = nullptr);
-// Stage B: offsets → pack → framing.  `prefix` bytes are placed at the start of d_out; the DEFLATE
-// bits start at bit `start_bit` of d_out (prefix may end with a partial byte).
-int encode_emit(Ctx *c, int format, bool with_trailer, uint32_t trailer_check, bool use_device_check,
-                uint64_t total_n, const uint8_t *prefix, uint32_t prefix_len, uint64_t start_bit,
-                uint8_t *d_out, uint64_t cap, EncodeResult *host_res, EncodeResult *async_slot) {
-    // async_slot (page-locked, the caller's own): the result is copied there and the call returns WITHOUT waiting — the
-    // stream encoder's batch in flight; the caller synchronises and reads the slot itself.  host_res is not touched then.
-    (void)hipSetDevice(c->device);
-    hipStream_t st = c->stream;
-    if (((uintptr_t)d_out & 3) != 0) { c->set_error("output buffer must be 4-byte aligned"); return LFX_E_ARG; }
-    const uint64_t trailer = with_trailer ? (format == LFX_GZIP ? 8 : format == LFX_ZLIB ? 4 : 0) : 0;
-    if (cap < prefix_len + trailer + 8) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
-    const uint64_t cap_words = cap / 4;  // whole dwords only (kernels write dwords)
-    const uint64_t cap_bits = (cap_words * 4 - trailer) * 8;
-    if (c->prezero_ptr == d_out && c->prezero_bytes == cap_words * 4) {
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_zero, 0));      // zero-filled on the side stream, under the match kernel
-    } else {
-        HIP_TRY(hipMemsetAsync(d_out, 0, cap_words * 4, st));
-    }
-    c->prezero_ptr = nullptr;
-    c->phase("memset_out");
-    EncodeResult *dres = (EncodeResult *)c->d_res.p;
-    LAUNCH_TRY(launch_offsets(st, (const BlockDesc *)c->d_blocks.p, c->cur_nblocks, (const BlockCodes *)c->d_bc.p,
-                              start_bit, cap_bits, (uint64_t *)c->d_block_start.p, dres));
-    LAUNCH_TRY(launch_pack(st, c->cur_in, c->cur_n, (const ChunkDesc *)c->d_chunks.p, c->cur_nchunks,
-                           (const BlockDesc *)c->d_blocks.p, c->cur_nblocks, c->cur_ntiles,
-                           (const uint32_t *)c->d_codes.p, (const uint32_t *)c->d_ncodes.p,
-                           (const BlockCodes *)c->d_bc.p, (const uint64_t *)c->d_block_start.p,
-                           (uint32_t *)c->d_tile_bits.p, (uint64_t *)c->d_tile_start.p, dres, 0,
-                           (uint32_t *)d_out, c->cur_tile_map));
-    c->phase("pack");
-    if (prefix_len) {
-        // (a gzip header holds an unbounded file name / comment: its own buffer, sized to fit)
-        int rcp = c->d_hdr.reserve(prefix_len);
-        if (rcp) return rcp;
-        HIP_TRY(hipMemcpyAsync(c->d_hdr.p, prefix, prefix_len, hipMemcpyHostToDevice, st));
-        LAUNCH_TRY(launch_put_bytes(st, (const uint8_t *)c->d_hdr.p, prefix_len, 0, (uint32_t *)d_out));
-    }
-    if (!use_device_check) {
-        // combined checksum supplied by the caller (sharded encode): patch the device result
-        HIP_TRY(hipMemcpyAsync((uint8_t *)dres + offsetof(EncodeResult, crc32), &trailer_check, 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync((uint8_t *)dres + offsetof(EncodeResult, adler32), &trailer_check, 4, hipMemcpyHostToDevice, st));
-    }
-    LAUNCH_TRY(launch_trailer(st, with_trailer ? format : LFX_DEFLATE, (uint32_t)total_n, 0, dres, (uint32_t *)d_out));
-    HIP_TRY(hipMemcpyAsync(async_slot ? (void *)async_slot : c->h_res, dres, sizeof(EncodeResult), hipMemcpyDeviceToHost, st));
-    c->phase("frame");
-    if (async_slot) return LFX_OK;
-    HIP_TRY(hipStreamSynchronize(st));
-    *host_res = *(EncodeResult *)c->h_res;
-    if (host_res->status != 0) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
-    return LFX_OK;
-}
-
-}  // namespace lfx
-
-// The second-generation match kernel proves its one hardware assumption at run time; a violation voids the results
-// and makes the context fall back to the first-generation kernel for good.
-static bool match_violation(Ctx *c, const EncodeResult &res) {
-    if (!(res.match_flags & 1) || c->force_match_v1) return false;
-    c->force_match_v1 = true;
-    return true;
-}
-
+// encode entry points: argument checks, the plan, then the encode core (lfx_encode.cpp)
 extern "C" int lfx_encode_device(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s,
                                  const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len) try {
     if (!cc) return LFX_E_DEVICE;
@@ -764,34 +367,15 @@ extern "C" int lfx_encode_device(lfx_ctx *cc, int format, const lfx_encode_opts 
     apply_schedule(pl, s, n);
     Plan &plan = pl.finish();
     EncodeResult res{};
-    // the pack kernels OR into a zero-filled output: fill it now, on the side stream, instead of between the Huffman
-    // and the pack kernels (every entry point is synchronous, so nothing else is using the buffer)
-    c->prezero_ptr = nullptr;
-    if (((uintptr_t)d_out & 3) == 0 && cap >= 16) {
-        (void)hipSetDevice(c->device);
-        const uint64_t bytes = cap / 4 * 4;
-        // ordered behind whatever the caller's stream still has queued on d_out (a consumer of the previous encode, an
-        // allocator-reused block): fork from c->stream exactly as the checksum does
-        if (hipEventRecord(c->ev_fork, c->stream) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess &&
-            hipMemsetAsync(d_out, 0, bytes, c->side_stream) == hipSuccess && hipEventRecord(c->ev_zero, c->side_stream) == hipSuccess) {
-            c->prezero_ptr = d_out;
-            c->prezero_bytes = bytes;
-        }
-    }
-    for (;;) {
-        if ((rc = encode_prepare(c, plan, po, (const uint8_t *)d_in, n, format == LFX_GZIP ? 1 : format == LFX_ZLIB ? 2 : 0))) {
-            // the fill may still be running on the caller's buffer: do not return before it has finished
-            if (c->prezero_ptr) (void)hipEventSynchronize(c->ev_zero);
-            c->prezero_ptr = nullptr;
-            return rc;
-        }
-        rc = encode_emit(c, format, true, 0, true, n, hdr.data(), (uint32_t)hdr.size(), 8 * (uint64_t)hdr.size(),
-                         (uint8_t *)d_out, cap, &res);
-        if (match_violation(c, res)) continue;   // (never observed: see lfx_match2.hip) redo with the first-generation kernel
-        break;
-    }
-    if (c->prezero_ptr) (void)hipEventSynchronize(c->ev_zero);   // (emit failed before it waited for the fill)
-    c->prezero_ptr = nullptr;
+    const bool fill_ok = ((uintptr_t)d_out & 3) == 0 && cap >= 16;
+    if (fill_ok) (void)hipSetDevice(c->device);
+    c->prezero.start(d_out, fill_ok ? cap / 4 * 4 : 0);
+    rc = with_match_fallback(c, res, [&]() -> int {
+        if (int rc2 = encode_prepare(c, plan, po, (const uint8_t *)d_in, n, ck_mode_of(format))) return rc2;
+        return encode_emit(c, format, true, 0, true, n, hdr.data(), (uint32_t)hdr.size(), 8 * (uint64_t)hdr.size(),
+                           (uint8_t *)d_out, cap, &res);
+    });
+    c->prezero.settle();     // (prepare or emit failed before the stream waited for the fill: it is on the caller's buffer)
     if (rc) return rc;
     if (out_len) *out_len = res.out_bytes;
     // (an index build, lfx_encode_index_device: the candidates of the stream the last emit wrote, while its buffers hold it)
@@ -816,10 +400,7 @@ extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode
     std::vector<uint8_t> hdr;
     if ((rc = container_header(format, d, hdr))) { c->set_error("bad container options"); return rc; }
     if (!count) return LFX_OK;
-    (void)hipSetDevice(c->device);
-    hipStream_t st = c->stream;
     const PlanOpts po = plan_opts(format, d);
-    const uint32_t trailer = format == LFX_GZIP ? 8 : format == LFX_ZLIB ? 4 : 0;
     // ---- the merged plan: every stream planned alone, its descriptors shifted into the shared index spaces
     Plan plan;
     std::vector<BatchStream> streams(count);
@@ -829,15 +410,8 @@ extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode
         Planner pl(po);
         apply_schedule(pl, s, in_len[i]);
         Plan &p = pl.finish();
-        const uint32_t c0 = (uint32_t)plan.chunks.size(), b0 = (uint32_t)plan.blocks.size();
-        for (ChunkDesc ch : p.chunks) {
-            ch.in_off += in_off[i]; ch.code_off += plan.n_codes_cap; ch.block += b0; ch.tile_base += plan.n_tiles;
-            ch.vis_base += plan.n_vis; ch.seg_base += plan.n_segs;
-            plan.chunks.push_back(ch);
-        }
-        for (BlockDesc b : p.blocks) { b.in_off += in_off[i]; b.first_chunk += c0; plan.blocks.push_back(b); }
-        plan.n_codes_cap += p.n_codes_cap; plan.n_tiles += p.n_tiles; plan.n_vis += p.n_vis; plan.n_segs += p.n_segs;
-        streams[i] = BatchStream{in_off[i], in_len[i], out_off[i], out_cap[i], b0, (uint32_t)p.blocks.size()};
+        streams[i] = BatchStream{in_off[i], in_len[i], out_off[i], out_cap[i], (uint32_t)plan.blocks.size(), (uint32_t)p.blocks.size()};
+        plan.append(p, in_off[i]);
         in_extent = std::max(in_extent, in_off[i] + in_len[i]);
         out_lo = std::min(out_lo, out_off[i]);
         out_hi = std::max(out_hi, out_off[i] + out_cap[i]);
@@ -853,48 +427,11 @@ extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode
                 return LFX_E_ARG;
             }
     }
-    const uint32_t nblocks = (uint32_t)plan.blocks.size();
-    // per-stream scratch: descriptors, checksums, end bits, status, lengths (+ the header bytes)
-    const size_t sz_streams = sizeof(BatchStream) * count;
-    DevBuf &sb = c->d_dec_streams;     // (decode scratch: free during an encode)
-    if ((rc = sb.reserve(sz_streams + (4 + 4 + 8 + 4 + 8) * (size_t)count + hdr.size() + 64))) return rc;
-    BatchStream *d_streams = (BatchStream *)sb.p;
-    uint64_t *d_end = (uint64_t *)((uint8_t *)sb.p + sz_streams);
-    uint64_t *d_len = d_end + count;
-    uint32_t *d_crc = (uint32_t *)(d_len + count), *d_adler = d_crc + count;
-    int32_t *d_status = (int32_t *)(d_adler + count);
-    uint8_t *d_hdr = (uint8_t *)(d_status + count);
-    std::vector<uint64_t> h_len(count);
-    std::vector<int32_t> h_status(count);
+    std::vector<uint64_t> h_len;
+    std::vector<int32_t> h_status;
     EncodeResult res{};
-    for (;;) {
-        if ((rc = encode_prepare(c, plan, po, (const uint8_t *)d_in, in_extent, 0))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_streams, streams.data(), sz_streams, hipMemcpyHostToDevice, st));
-        if (!hdr.empty()) HIP_TRY(hipMemcpyAsync(d_hdr, hdr.data(), hdr.size(), hipMemcpyHostToDevice, st));
-        if (trailer)
-            LAUNCH_TRY(launch_checksum_ranges(st, (const uint8_t *)d_in, count, (const uint64_t *)d_streams, sizeof(BatchStream) / 8,
-                                              (const uint64_t *)d_streams + 1, sizeof(BatchStream) / 8, d_crc, d_adler));
-        c->phase("checksum");
-        HIP_TRY(hipMemsetAsync((uint8_t *)d_out + out_lo, 0, out_hi - out_lo, st));
-        EncodeResult *dres = (EncodeResult *)c->d_res.p;
-        LAUNCH_TRY(launch_offsets_batch(st, d_streams, count, (const BlockDesc *)c->d_blocks.p, (const BlockCodes *)c->d_bc.p,
-                                        (uint32_t)hdr.size(), trailer, (uint64_t *)c->d_block_start.p, d_end, d_status, dres));
-        LAUNCH_TRY(launch_pack(st, (const uint8_t *)d_in, in_extent, (const ChunkDesc *)c->d_chunks.p, c->cur_nchunks,
-                               (const BlockDesc *)c->d_blocks.p, nblocks, c->cur_ntiles, (const uint32_t *)c->d_codes.p,
-                               (const uint32_t *)c->d_ncodes.p, (const BlockCodes *)c->d_bc.p, (const uint64_t *)c->d_block_start.p,
-                               (uint32_t *)c->d_tile_bits.p, (uint64_t *)c->d_tile_start.p, dres, 0, (uint32_t *)d_out, c->cur_tile_map));
-        c->phase("pack");
-        LAUNCH_TRY(launch_frame_batch(st, format, d_streams, count, d_hdr, (uint32_t)hdr.size(), d_end, d_crc, d_adler, dres,
-                                      (uint32_t *)d_out, d_len));
-        HIP_TRY(hipMemcpyAsync(c->h_res, dres, sizeof(EncodeResult), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_len.data(), d_len, 8ull * count, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_status.data(), d_status, 4ull * count, hipMemcpyDeviceToHost, st));
-        c->phase("frame");
-        HIP_TRY(hipStreamSynchronize(st));
-        res = *(EncodeResult *)c->h_res;
-        if (match_violation(c, res)) continue;
-        break;
-    }
+    const BatchCall call{format, streams, hdr, (const uint8_t *)d_in, in_extent, (uint8_t *)d_out, out_lo, out_hi};
+    if ((rc = encode_batch(c, plan, po, call, h_len, h_status, res))) return rc;
     for (uint32_t i = 0; i < count; i++) {
         if (status) status[i] = res.status ? h_status[i] : LFX_OK;     // (a voided call: non-zero for exactly the streams that were too small)
         if (out_len) out_len[i] = res.status ? 0 : h_len[i];
@@ -906,6 +443,24 @@ extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode
     return LFX_OK;
 } LFX_ABI_CATCH
 
+// A host variant: `in` staged into d_io_in, run(len) — the device entry point on d_io_in / d_io_out — and len bytes back.
+template <class Run>
+static int encode_staged(Ctx *c, const void *in, uint64_t n, uint64_t out_bytes, void *out, uint64_t cap, uint64_t *out_len, Run run) {
+    int rc;
+    if ((rc = c->d_io_out.reserve(out_bytes))) return rc;
+    // H2D / D2H at link rate (lfx_hostio.h): page-locked buffers (lfx_host_alloc) go to the DMA engine as they are, pageable
+    // ones through page-locked slabs filled by a few threads
+    if ((rc = stage_in(c, in, n))) return rc;
+    uint64_t len = 0;
+    rc = run(len);
+    // (a page-locked `in` was only queued for DMA: no return before the stream has passed the copy, on any path)
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (len > cap) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
+    if ((rc = device_to_host(c, out, c->d_io_out.p, len, c->stream))) { c->set_error("device to host copy failed"); return rc; }
+    if (out_len) *out_len = len;
+    return LFX_OK;
+}
+
 extern "C" int lfx_encode_host(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s,
                                const void *in, uint64_t n, void *out, uint64_t cap, uint64_t *out_len) try {
     if (!cc) return LFX_E_DEVICE;
@@ -914,20 +469,9 @@ extern "C" int lfx_encode_host(lfx_ctx *cc, int format, const lfx_encode_opts *o
     (void)hipSetDevice(c->device);
     uint64_t bound = lfx_encode_bound(n, o, s);
     if (bound == 0) { c->set_error("option outside the reference's domain"); return LFX_E_ARG; }
-    int rc;
-    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
-    if ((rc = c->d_io_out.reserve(bound))) return rc;
-    // H2D / D2H at link rate (lfx_hostio.h): page-locked buffers (lfx_host_alloc) go to the DMA engine as they are, pageable
-    // ones through page-locked slabs filled by a few threads
-    if ((rc = host_to_device(c, c->d_io_in.p, in, n, c->stream))) { c->set_error("host to device copy failed"); return rc; }
-    uint64_t len = 0;
-    rc = lfx_encode_device(cc, format, o, s, c->d_io_in.p, n, c->d_io_out.p, bound & ~3ull, &len);
-    // (a page-locked `in` was only queued for DMA: no return before the stream has passed the copy, on any path)
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (len > cap) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
-    if ((rc = device_to_host(c, out, c->d_io_out.p, len, c->stream))) { c->set_error("device to host copy failed"); return rc; }
-    if (out_len) *out_len = len;
-    return LFX_OK;
+    return encode_staged(c, in, n, bound, out, cap, out_len, [&](uint64_t &len) {
+        return lfx_encode_device(cc, format, o, s, c->d_io_in.p, n, c->d_io_out.p, bound & ~3ull, &len);
+    });
 } LFX_ABI_CATCH
 
 // ---- members encode: one buffer as back-to-back gzip members / BGZF, packed at their final offsets ----------
@@ -977,6 +521,48 @@ extern "C" uint64_t lfx_encode_members_bound(uint64_t n, uint64_t member_size, u
     return (ms.full ? ms.full * term(member_size) : 0) + (ms.have_last ? term(ms.last) : 0) + (bgzf ? BGZF_EOF_LEN : 0);
 } catch (...) { return 0; }
 
+// The merged plan of a members call: a full slice and the last slice are planned once each (the schedule applies to a slice
+// alone), the full slice's descriptors are repeated, shifted into the shared index spaces.  bpm[2]: blocks of a full and of
+// the last member.  *why names what is out of the domain.
+static int members_plan(const PlanOpts &po, const lfx_schedule *s, const MemberSlices &ms, uint64_t member_size, bool bgzf, Plan &plan,
+                        uint32_t bpm[2], const char **why) {
+    Plan pfull, plast;
+    if (ms.full) { Planner pl(po); apply_schedule(pl, s, member_size); pfull = std::move(pl.finish()); }
+    if (ms.have_last) { Planner pl(po); apply_schedule(pl, s, ms.last); plast = std::move(pl.finish()); }
+    if (bgzf) {
+        // the stored form of a member (no_compression = 1) must have the compressed form's blocks, byte for byte the same
+        // ranges: the device turns one into the other by the blocks' type alone.  (One write of at most 65505 bytes: a block
+        // holding all of it, and an empty final one behind it when block_size <= the slice — in both forms.)
+        PlanOpts ps = po;
+        ps.no_compression = true;
+        for (int k = 0; k < 2; k++) {
+            if (k == 0 ? !ms.full : !ms.have_last) continue;
+            const Plan &pc = k == 0 ? pfull : plast;
+            Planner pl(ps);
+            apply_schedule(pl, s, k == 0 ? member_size : ms.last);
+            const Plan &pr = pl.finish();
+            bool same = pr.blocks.size() == pc.blocks.size();
+            for (size_t b = 0; same && b < pr.blocks.size(); b++)
+                same = pr.blocks[b].in_off == pc.blocks[b].in_off && pr.blocks[b].in_len == pc.blocks[b].in_len &&
+                       pr.blocks[b].final == pc.blocks[b].final && pr.blocks[b].align_after == pc.blocks[b].align_after;
+            if (!same) { *why = "block_size: the stored form of a member has other blocks than the compressed form"; return LFX_E_UNSUPPORTED; }
+        }
+    }
+    if ((uint64_t)ms.full * pfull.chunks.size() + plast.chunks.size() > 0xFFFFFFF0ull ||
+        (uint64_t)ms.full * pfull.blocks.size() + plast.blocks.size() > 0xFFFFFFF0ull ||
+        (uint64_t)ms.full * pfull.n_segs + plast.n_segs > 0xFFFFFFF0ull) {
+        *why = "member_size: too many blocks for one call";
+        return LFX_E_ARG;
+    }
+    plan.chunks.reserve(ms.full * pfull.chunks.size() + plast.chunks.size());
+    plan.blocks.reserve(ms.full * pfull.blocks.size() + plast.blocks.size());
+    for (uint64_t m = 0; m < ms.full; m++) plan.append(pfull, m * member_size);
+    if (ms.have_last) plan.append(plast, ms.full * member_size);
+    bpm[0] = (uint32_t)(ms.full ? pfull.blocks.size() : plast.blocks.size());
+    bpm[1] = (uint32_t)(ms.have_last ? plast.blocks.size() : pfull.blocks.size());
+    return LFX_OK;
+}
+
 extern "C" int lfx_encode_members_device(lfx_ctx *cc, const lfx_encode_opts *o, const lfx_schedule *s, uint64_t member_size,
                                          uint32_t flags, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len,
                                          lfx_member *members, uint32_t max_members, uint32_t *n_members) try {
@@ -1009,109 +595,18 @@ extern "C" int lfx_encode_members_device(lfx_ctx *cc, const lfx_encode_opts *o, 
         return LFX_OK;
     }
     const PlanOpts po = plan_opts(LFX_GZIP, d);
-    // ---- the merged plan: a full slice and the last slice are planned once each (the schedule applies to a slice alone), the
-    // full slice's descriptors are repeated, shifted into the shared index spaces
-    Plan pfull, plast;
-    if (ms.full) { Planner pl(po); apply_schedule(pl, s, member_size); pfull = std::move(pl.finish()); }
-    if (ms.have_last) { Planner pl(po); apply_schedule(pl, s, ms.last); plast = std::move(pl.finish()); }
-    if (bgzf) {
-        // the stored form of a member (no_compression = 1) must have the compressed form's blocks, byte for byte the same
-        // ranges: the device turns one into the other by the blocks' type alone.  (One write of at most 65505 bytes: a block
-        // holding all of it, and an empty final one behind it when block_size <= the slice — in both forms.)
-        PlanOpts ps = po;
-        ps.no_compression = true;
-        for (int k = 0; k < 2; k++) {
-            if (k == 0 ? !ms.full : !ms.have_last) continue;
-            const Plan &pc = k == 0 ? pfull : plast;
-            Planner pl(ps);
-            apply_schedule(pl, s, k == 0 ? member_size : ms.last);
-            const Plan &pr = pl.finish();
-            bool same = pr.blocks.size() == pc.blocks.size();
-            for (size_t b = 0; same && b < pr.blocks.size(); b++)
-                same = pr.blocks[b].in_off == pc.blocks[b].in_off && pr.blocks[b].in_len == pc.blocks[b].in_len &&
-                       pr.blocks[b].final == pc.blocks[b].final && pr.blocks[b].align_after == pc.blocks[b].align_after;
-            if (!same) { c->set_error("block_size: the stored form of a member has other blocks than the compressed form"); return LFX_E_UNSUPPORTED; }
-        }
-    }
-    if ((uint64_t)ms.full * pfull.chunks.size() + plast.chunks.size() > 0xFFFFFFF0ull ||
-        (uint64_t)ms.full * pfull.blocks.size() + plast.blocks.size() > 0xFFFFFFF0ull ||
-        (uint64_t)ms.full * pfull.n_segs + plast.n_segs > 0xFFFFFFF0ull) {
-        c->set_error("member_size: too many blocks for one call");
-        return LFX_E_ARG;
-    }
     Plan plan;
-    plan.chunks.reserve(ms.full * pfull.chunks.size() + plast.chunks.size());
-    plan.blocks.reserve(ms.full * pfull.blocks.size() + plast.blocks.size());
-    auto append = [&](const Plan &p, uint64_t in_off) {
-        const uint32_t c0 = (uint32_t)plan.chunks.size(), b0 = (uint32_t)plan.blocks.size();
-        for (ChunkDesc ch : p.chunks) {
-            ch.in_off += in_off; ch.code_off += plan.n_codes_cap; ch.block += b0; ch.tile_base += plan.n_tiles;
-            ch.vis_base += plan.n_vis; ch.seg_base += plan.n_segs;
-            plan.chunks.push_back(ch);
-        }
-        for (BlockDesc b : p.blocks) { b.in_off += in_off; b.first_chunk += c0; plan.blocks.push_back(b); }
-        plan.n_codes_cap += p.n_codes_cap; plan.n_tiles += p.n_tiles; plan.n_vis += p.n_vis; plan.n_segs += p.n_segs;
-    };
-    for (uint64_t m = 0; m < ms.full; m++) append(pfull, m * member_size);
-    if (ms.have_last) append(plast, ms.full * member_size);
+    uint32_t bpm[2];
+    if ((rc = members_plan(po, s, ms, member_size, bgzf, plan, bpm, &why))) { c->set_error(why); return rc; }
     MembersGeom g{};
     g.n = n; g.member_size = member_size; g.count = count;
-    g.bpm = (uint32_t)(ms.full ? pfull.blocks.size() : plast.blocks.size());
-    g.bpm_last = (uint32_t)(ms.have_last ? plast.blocks.size() : pfull.blocks.size());
+    g.bpm = bpm[0]; g.bpm_last = bpm[1];
     g.hdr_len = (uint32_t)hdr.size(); g.bgzf = bgzf ? 1u : 0u;
-    const uint32_t nblocks = (uint32_t)plan.blocks.size();
-    // per-member scratch: records, offsets inside the workgroup, lengths, checksums; the workgroup sums; the header
-    const uint32_t nwg = (count + 255) / 256;
-    const size_t cnt = std::max<uint32_t>(count, 1);
-    DevBuf &sb = c->d_dec_streams;     // (decode scratch: free during an encode)
-    if ((rc = sb.reserve((sizeof(lfx_member) + 8 + 8 + 4 + 4) * cnt + 8 * (size_t)std::max<uint32_t>(nwg, 1) + hdr.size() + 64))) return rc;
-    lfx_member *d_members = (lfx_member *)sb.p;
-    uint64_t *d_local = (uint64_t *)(d_members + cnt), *d_mlen = d_local + cnt, *d_wg = d_mlen + cnt;
-    uint32_t *d_crc = (uint32_t *)(d_wg + std::max<uint32_t>(nwg, 1)), *d_adler = d_crc + cnt;
-    uint8_t *d_hdr = (uint8_t *)(d_adler + cnt);
-    // the kernels OR into zeros: [0, min(cap, bound)) is filled once, on the side stream beside the match kernel (as
-    // lfx_encode_device does); no member can end behind the bound, and nothing is written when the total exceeds cap
     const uint64_t bound = lfx_encode_members_bound(n, member_size, flags, o, s);
-    const uint64_t fill = std::min(cap, bound);
-    bool prezero = fill && hipEventRecord(c->ev_fork, st) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess &&
-                   hipMemsetAsync(d_out, 0, fill, c->side_stream) == hipSuccess && hipEventRecord(c->ev_zero, c->side_stream) == hipSuccess;
-    c->prezero_ptr = nullptr;
     EncodeResult res{};
-    const uint32_t n_rec = members ? std::min(count, max_members) : 0;
-    auto body = [&]() -> int {
-        for (;;) {
-            int rc2;
-            if ((rc2 = encode_prepare(c, plan, po, (const uint8_t *)d_in, n, 0))) return rc2;
-            HIP_TRY(hipMemcpyAsync(d_hdr, hdr.data(), hdr.size(), hipMemcpyHostToDevice, st));
-            EncodeResult *dres = (EncodeResult *)c->d_res.p;
-            LAUNCH_TRY(launch_members_layout(st, g, (BlockDesc *)c->d_blocks.p, (const BlockCodes *)c->d_bc.p, d_local, d_mlen, d_wg, cap,
-                                             (uint64_t *)c->d_block_start.p, d_members, dres));
-            if (bgzf) c->up_dev[1] = 0;      // the device's block table no longer equals its shadow: the next prepare uploads it
-            c->phase("members_layout");
-            LAUNCH_TRY(launch_checksum_ranges(st, (const uint8_t *)d_in, count, (const uint64_t *)d_members, sizeof(lfx_member) / 8,
-                                              (const uint64_t *)d_members + 1, sizeof(lfx_member) / 8, d_crc, d_adler));
-            c->phase("checksum");
-            if (prezero) HIP_TRY(hipStreamWaitEvent(st, c->ev_zero, 0));
-            else if (fill) HIP_TRY(hipMemsetAsync(d_out, 0, fill, st));
-            prezero = false;
-            LAUNCH_TRY(launch_pack(st, (const uint8_t *)d_in, n, (const ChunkDesc *)c->d_chunks.p, c->cur_nchunks,
-                                   (const BlockDesc *)c->d_blocks.p, nblocks, c->cur_ntiles, (const uint32_t *)c->d_codes.p,
-                                   (const uint32_t *)c->d_ncodes.p, (const BlockCodes *)c->d_bc.p, (const uint64_t *)c->d_block_start.p,
-                                   (uint32_t *)c->d_tile_bits.p, (uint64_t *)c->d_tile_start.p, dres, 0, (uint32_t *)d_out, c->cur_tile_map));
-            c->phase("pack");
-            LAUNCH_TRY(launch_members_frame(st, g, d_hdr, d_members, d_crc, dres, (uint32_t *)d_out));
-            HIP_TRY(hipMemcpyAsync(c->h_res, dres, sizeof(EncodeResult), hipMemcpyDeviceToHost, st));
-            if (n_rec) HIP_TRY(hipMemcpyAsync(members, d_members, sizeof(lfx_member) * (size_t)n_rec, hipMemcpyDeviceToHost, st));
-            c->phase("frame");
-            HIP_TRY(hipStreamSynchronize(st));
-            res = *(EncodeResult *)c->h_res;
-            if (match_violation(c, res)) continue;
-            return LFX_OK;
-        }
-    };
-    rc = body();
-    if (prezero) (void)hipEventSynchronize(c->ev_zero);     // (failed before the stream waited for the fill: it is on the caller's buffer)
-    if (rc) return rc;
+    const MembersCall call{g, hdr, (const uint8_t *)d_in, (uint8_t *)d_out, cap, std::min(cap, bound), members,
+                           members ? std::min(count, max_members) : 0};
+    if ((rc = encode_members(c, plan, po, call, res))) return rc;
     if (n_members) *n_members = count;
     if (res.status) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
     if (out_len) *out_len = res.out_bytes;
@@ -1132,17 +627,10 @@ extern "C" int lfx_encode_members_host(lfx_ctx *cc, const lfx_encode_opts *o, co
     int rc = members_check(member_size, flags, o, s, &d, &why);
     if (rc) { c->set_error(why); return rc; }
     const uint64_t bound = lfx_encode_members_bound(n, member_size, flags, o, s);
-    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
-    if ((rc = c->d_io_out.reserve(std::max<uint64_t>(bound, 4)))) return rc;
-    if ((rc = host_to_device(c, c->d_io_in.p, in, n, c->stream))) { c->set_error("host to device copy failed"); return rc; }
-    uint64_t len = 0;
-    rc = lfx_encode_members_device(cc, o, s, member_size, flags, c->d_io_in.p, n, c->d_io_out.p, std::min(cap, bound), &len, members,
-                                   max_members, n_members);
-    // (a page-locked `in` was only queued for DMA: no return before the stream has passed the copy, on any path)
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if ((rc = device_to_host(c, out, c->d_io_out.p, len, c->stream))) { c->set_error("device to host copy failed"); return rc; }
-    if (out_len) *out_len = len;
-    return LFX_OK;
+    return encode_staged(c, in, n, std::max<uint64_t>(bound, 4), out, cap, out_len, [&](uint64_t &len) {
+        return lfx_encode_members_device(cc, o, s, member_size, flags, c->d_io_in.p, n, c->d_io_out.p, std::min(cap, bound), &len, members,
+                                         max_members, n_members);
+    });
 } LFX_ABI_CATCH
 
 extern "C" int lfx_members_gzi(const lfx_member *members, uint32_t n_members, void *buf, uint64_t cap, uint64_t *len) {
@@ -1165,17 +653,10 @@ extern "C" int lfx_encode_shard_prezero(lfx_ctx *cc, void *d_out, uint64_t cap) 
     if (!cc) return LFX_E_DEVICE;
     Ctx *c = reinterpret_cast<Ctx *>(cc);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    if (c->prezero_ptr) (void)hipEventSynchronize(c->ev_zero);
-    c->prezero_ptr = nullptr;
+    c->prezero.settle();
     if (!d_out || ((uintptr_t)d_out & 3) != 0 || cap < 16) return LFX_OK;
     (void)hipSetDevice(c->device);
-    const uint64_t bytes = cap / 4 * 4;
-    // (ordered behind whatever the caller's stream still has queued on d_out: forked from c->stream as in lfx_encode_device)
-    if (hipEventRecord(c->ev_fork, c->stream) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess &&
-        hipMemsetAsync(d_out, 0, bytes, c->side_stream) == hipSuccess && hipEventRecord(c->ev_zero, c->side_stream) == hipSuccess) {
-        c->prezero_ptr = d_out;
-        c->prezero_bytes = bytes;
-    }
+    c->prezero.start(d_out, cap / 4 * 4);
     return LFX_OK;
 } LFX_ABI_CATCH
 
@@ -1215,17 +696,17 @@ extern "C" int lfx_encode_shard_prepare(lfx_ctx *cc, int format, const lfx_encod
     c->shard_last = is_last != 0;
     hipStream_t st = c->stream;
     EncodeResult r{};
-    for (;;) {
-        if ((rc = encode_prepare(c, *plan, po, (const uint8_t *)d_in, n, 3))) return rc;
+    rc = with_match_fallback(c, r, [&]() -> int {
+        if (int rc2 = encode_prepare(c, *plan, po, (const uint8_t *)d_in, n, 3)) return rc2;
         // total bits at bit phase 0 (compressed blocks only → independent of the phase)
         LAUNCH_TRY(launch_offsets(st, (const BlockDesc *)c->d_blocks.p, c->cur_nblocks, (const BlockCodes *)c->d_bc.p,
                                   0, ~0ull, (uint64_t *)c->d_block_start.p, (EncodeResult *)c->d_res.p));
         HIP_TRY(hipMemcpyAsync(c->h_res, c->d_res.p, sizeof(EncodeResult), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         r = *(EncodeResult *)c->h_res;
-        if (match_violation(c, r)) continue;
-        break;
-    }
+        return LFX_OK;
+    });
+    if (rc) return rc;
     // For the LAST shard the figure includes the final byte alignment as seen from phase 0; its true value depends on
     // the shard's start phase and is settled by emit().  Layouts only ever sum the bits of the shards in front of a
     // shard, so the last shard's own figure is informative.
@@ -1327,6 +808,31 @@ static int enc_emit_bytes(lfx_encoder *e, const uint8_t *p, size_t n) {
 // order are those of the synchronous form.
 struct EncCollected { uint64_t whole = 0; bool have = false; };
 
+// One batch through the GPU: prepare + emit of `plan` over d_in[0, n) into d_out[0, cap), the bits behind the partial byte the
+// batch before left (`carry`).  The container trailer is written by the host (the checksum spans batches).  async_slot: as
+// encode_emit's — the call returns without waiting.
+static int enc_encode(lfx_encoder *e, const Plan &plan, uint64_t n, uint64_t cap, const HostCodes *hc, EncodeResult *res,
+                      EncodeResult *async_slot) {
+    Ctx *c = e->c;
+    const uint8_t prefix[1] = {e->carry};
+    int rc = encode_prepare(c, plan, e->po, (const uint8_t *)e->d_in.p, n, ck_mode_of(e->format), hc);
+    if (!rc) rc = encode_emit(c, LFX_DEFLATE, false, 0, true, 0, prefix, e->carry_bits ? 1 : 0, e->carry_bits, (uint8_t *)e->d_out.p,
+                              cap & ~3ull, res, async_slot);
+    if (rc) e->err = c->err;
+    return rc;
+}
+// A batch of n input bytes is encoded: its checksum folded into the running one, its bits counted → the bytes of output that
+// are whole (all of them when `final`); the rest stays as `carry_bits` of a byte the caller fetches into `carry`.
+static uint64_t enc_account(lfx_encoder *e, const EncodeResult &res, uint64_t n, bool final) {
+    if (n) {
+        if (e->format == LFX_GZIP) e->crc = e->encoded_in == 0 ? res.crc32 : lfx_crc32_combine(e->crc, res.crc32, n);
+        if (e->format == LFX_ZLIB) e->adler = e->encoded_in == 0 ? res.adler32 : lfx_adler32_combine(e->adler, res.adler32, n);
+        e->encoded_in += n;
+    }
+    e->carry_bits = final ? 0 : (uint32_t)(res.end_bit & 7);
+    return final ? (res.end_bit + 7) / 8 : res.end_bit / 8;
+}
+
 // start the batch; nothing is waited for.  The batch's bytes move to `inflight_buf`, the open block's bytes stay pending.
 static int enc_launch(lfx_encoder *e, Plan &&plan, uint64_t n, bool final) {
     Ctx *c = e->c;
@@ -1339,12 +845,7 @@ static int enc_launch(lfx_encoder *e, Plan &&plan, uint64_t n, bool final) {
     e->inflight_buf.assign(e->pending.begin() + (std::ptrdiff_t)n, e->pending.end());
     e->inflight_buf.swap(e->pending);              // pending = the open block's bytes, inflight_buf = the batch (its first n bytes)
     if (n && hipMemcpyAsync(e->d_in.p, e->inflight_buf.data(), n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LFX_E_DEVICE;
-    const uint8_t prefix[1] = {e->carry};
-    if ((rc = encode_prepare(c, plan, e->po, (const uint8_t *)e->d_in.p, n, e->format == LFX_GZIP ? 1 : e->format == LFX_ZLIB ? 2 : 0))) { e->err = c->err; return rc; }
-    // the container trailer is written by the host (the checksum spans batches)
-    rc = encode_emit(c, LFX_DEFLATE, false, 0, true, 0, prefix, e->carry_bits ? 1 : 0, e->carry_bits, (uint8_t *)e->d_out.p,
-                     bound & ~3ull, nullptr, (EncodeResult *)e->h_res.data());
-    if (rc) { e->err = c->err; return rc; }
+    if ((rc = enc_encode(e, plan, n, bound, nullptr, nullptr, (EncodeResult *)e->h_res.data()))) return rc;
     e->inflight = true;
     e->inflight_final = final;
     e->inflight_n = n;
@@ -1361,22 +862,18 @@ static int enc_collect(lfx_encoder *e, EncCollected *out) {
     if (!e->inflight) return LFX_OK;
     e->inflight = false;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return LFX_E_DEVICE;
-    EncodeResult res = *(const EncodeResult *)e->h_res.data();
+    EncodeResult res{};
     const uint64_t n = e->inflight_n;
-    int rc = LFX_OK;
-    if (match_violation(c, res)) {
-        // (never observed) the batch's bytes are still in d_in: once more, on the fallback kernel, synchronously
-        const uint8_t prefix[1] = {e->carry};
-        if ((rc = encode_prepare(c, e->inflight_plan, e->po, (const uint8_t *)e->d_in.p, n, e->format == LFX_GZIP ? 1 : e->format == LFX_ZLIB ? 2 : 0))) { e->err = c->err; return rc; }
-        rc = encode_emit(c, LFX_DEFLATE, false, 0, true, 0, prefix, e->carry_bits ? 1 : 0, e->carry_bits, (uint8_t *)e->d_out.p,
-                         e->inflight_bound & ~3ull, &res);
-        if (rc) { e->err = c->err; return rc; }
-    }
+    // the first pass is the batch in flight, its result in the slot; (never observed) a violation: the batch's bytes are still
+    // in d_in — once more, on the fallback kernel, synchronously
+    bool in_flight = true;
+    int rc = with_match_fallback(c, res, [&]() -> int {
+        if (in_flight) { in_flight = false; res = *(const EncodeResult *)e->h_res.data(); return LFX_OK; }
+        return enc_encode(e, e->inflight_plan, n, e->inflight_bound, nullptr, &res, nullptr);
+    });
+    if (rc) return rc;
     if (res.status != 0) { c->set_error("output capacity too small"); e->err = c->err; return LFX_E_NOSPACE; }
-    if (e->format == LFX_GZIP) e->crc = e->encoded_in == 0 ? res.crc32 : lfx_crc32_combine(e->crc, res.crc32, n);
-    if (e->format == LFX_ZLIB) e->adler = e->encoded_in == 0 ? res.adler32 : lfx_adler32_combine(e->adler, res.adler32, n);
-    e->encoded_in += n;
-    const uint64_t whole = e->inflight_final ? (res.end_bit + 7) / 8 : res.end_bit / 8;
+    const uint64_t whole = enc_account(e, res, n, e->inflight_final);
     e->h_out.resize(whole + 1);
     // the shared byte first (the next batch's launch needs it), then the bulk — which travels while that launch is prepared
     uint8_t *slot = e->h_res.data() + 128;
@@ -1384,7 +881,6 @@ static int enc_collect(lfx_encoder *e, EncCollected *out) {
         hipEventRecord(e->ev_small, c->stream) != hipSuccess ||
         (whole && hipMemcpyAsync(e->h_out.data(), e->d_out.p, whole, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
         hipEventRecord(e->ev_out, c->stream) != hipSuccess || hipEventSynchronize(e->ev_small) != hipSuccess) return LFX_E_DEVICE;
-    e->carry_bits = e->inflight_final ? 0 : (uint32_t)(res.end_bit & 7);
     e->carry = e->carry_bits ? *slot : 0;
     out->whole = whole;
     out->have = true;
@@ -1463,21 +959,12 @@ static int enc_run_codes(lfx_encoder *e) {
     if ((rc = e->d_out.reserve(bound))) return rc;
     if (n && hipMemcpyAsync(e->d_in.p, e->pending.data(), n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LFX_E_DEVICE;
     EncodeResult res{};
-    uint8_t prefix[1] = {e->carry};
     const HostCodes hc{e->codes.data(), code_cursor, chunk_codes.data()};
-    if ((rc = encode_prepare(c, plan, e->po, (const uint8_t *)e->d_in.p, n, e->format == LFX_GZIP ? 1 : e->format == LFX_ZLIB ? 2 : 0, &hc))) { e->err = c->err; return rc; }
-    rc = encode_emit(c, LFX_DEFLATE, false, 0, true, 0, prefix, e->carry_bits ? 1 : 0, e->carry_bits, (uint8_t *)e->d_out.p, bound & ~3ull, &res);
-    if (rc) { e->err = c->err; return rc; }
-    if (n) {
-        if (e->format == LFX_GZIP) e->crc = e->encoded_in == 0 ? res.crc32 : lfx_crc32_combine(e->crc, res.crc32, n);
-        if (e->format == LFX_ZLIB) e->adler = e->encoded_in == 0 ? res.adler32 : lfx_adler32_combine(e->adler, res.adler32, n);
-        e->encoded_in += n;
-    }
-    const uint64_t whole = e->final_closed ? (res.end_bit + 7) / 8 : res.end_bit / 8;
+    if ((rc = enc_encode(e, plan, n, bound, &hc, &res, nullptr))) return rc;
+    const uint64_t whole = enc_account(e, res, n, e->final_closed);
     e->h_out.resize(whole + 1);
     if (hipMemcpyAsync(e->h_out.data(), e->d_out.p, whole + 1, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) return LFX_E_DEVICE;
-    e->carry_bits = e->final_closed ? 0 : (uint32_t)(res.end_bit & 7);
     e->carry = e->carry_bits ? e->h_out[whole] : 0;
     e->pending.clear();
     e->codes.erase(e->codes.begin(), e->codes.begin() + (std::ptrdiff_t)e->closed_codes);
@@ -1685,15 +1172,15 @@ extern "C" int lfx_lz77_flush(lfx_lz77 *z, lfx_sink_cb sink, void *user) try {
     int rc;
     if ((rc = z->d_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
     HIP_TRY(hipMemcpyAsync(z->d_in.p, z->buf.data(), n, hipMemcpyHostToDevice, c->stream));
-    uint32_t nc = 0;
-    for (;;) {
-        if ((rc = encode_prepare(c, plan, po, (const uint8_t *)z->d_in.p, n, 0))) return rc;
-        EncodeResult r{};
+    EncodeResult r{};
+    rc = with_match_fallback(c, r, [&]() -> int {
+        if (int rc2 = encode_prepare(c, plan, po, (const uint8_t *)z->d_in.p, n, 0)) return rc2;
         HIP_TRY(hipMemcpy(&r, c->d_res.p, sizeof r, hipMemcpyDeviceToHost));
-        if (match_violation(c, r)) continue;
-        HIP_TRY(hipMemcpy(&nc, c->d_ncodes.p, 4, hipMemcpyDeviceToHost));
-        break;
-    }
+        return LFX_OK;
+    });
+    if (rc) return rc;
+    uint32_t nc = 0;
+    HIP_TRY(hipMemcpy(&nc, c->d_ncodes.p, 4, hipMemcpyDeviceToHost));
     z->host_codes.resize(nc);
     if (nc) HIP_TRY(hipMemcpy(z->host_codes.data(), c->d_codes.p, 4ull * nc, hipMemcpyDeviceToHost));
     z->buf.clear();  // default.rs:108
@@ -1760,15 +1247,11 @@ extern "C" int lfx_debug_plan_incremental(int format, const lfx_encode_opts *o, 
     lfx_encode_opts d = norm_opts(o);
     if (check_opts(d) || !s || s->kind != LFX_SCHED_LIST) return LFX_E_ARG;
     Planner pl(plan_opts(format, d));
-    std::vector<ChunkDesc> chunks;
-    std::vector<BlockDesc> blocks;
+    Plan all;
     uint64_t byte0 = 0;
-    auto stitch = [&](Plan &p, uint64_t bytes) {
-        const uint32_t b0 = (uint32_t)blocks.size(), c0 = (uint32_t)chunks.size();
-        for (ChunkDesc c : p.chunks) { c.in_off += byte0; c.block += b0; chunks.push_back(c); }
-        for (BlockDesc b : p.blocks) { b.in_off += byte0; b.first_chunk += c0; blocks.push_back(b); }
-        byte0 += bytes;
-    };
+    auto stitch = [&](Plan &p, uint64_t bytes) { all.append(p, byte0); byte0 += bytes; };
+    const std::vector<ChunkDesc> &chunks = all.chunks;
+    const std::vector<BlockDesc> &blocks = all.blocks;
     uint64_t used = 0;
     for (size_t i = 0; i < s->n_writes; i++) {
         if (s->writes[i] == LFX_SCHED_FLUSH) pl.flush();

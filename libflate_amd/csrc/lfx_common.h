@@ -81,6 +81,22 @@ constexpr uint32_t PARSE_WG_SEGS = LFX_PARSE_WG_SEGS;
 #endif
 constexpr uint32_t PARSE_EMIT_WAVES = LFX_EMIT_WAVES, PARSE_EMIT_WG_PER_CU = LFX_EMIT_WG_PER_CU;
 
+// ---- descriptors the encode's host geometry makes (lfx_encode_stages.h) and the match / parse kernels read
+// one workgroup's share of the match search: positions [start, start+len) of a chunk
+struct SegDesc {
+    uint32_t chunk;
+    uint32_t start;
+    uint32_t len;
+    uint32_t lnk_base;   // lfx_match7 / lfx_match5: first entry of the segment's private link region, in units of 64 entries (128 bytes)
+};
+constexpr uint32_t SEG_POSITIONS = 256 * 1024;
+
+// one workgroup of the parse walk: PARSE_WG_SEGS consecutive parse segments of one chunk, from segment seg0 on
+struct ParseWg {
+    uint32_t chunk;
+    uint32_t seg0;
+};
+
 #ifdef __HIPCC__
 // pointers that are known to address global memory (HBM): keeps loads on the global_load path —
 // a pointer rebuilt from an integer becomes `flat`, and flat loads also tick lgkmcnt, which makes

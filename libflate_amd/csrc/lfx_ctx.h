@@ -67,9 +67,21 @@ struct Ctx {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_zero = nullptr;
     hipEvent_t ev_part[4] = {}, ev_res = nullptr;   // lfx_match7: the resolver of one part of the segments runs beside the next part's kernel
-    // one-shot encode: the output buffer is zero-filled on the side stream while the match kernel runs
-    const void *prezero_ptr = nullptr;
-    uint64_t prezero_bytes = 0;
+    // The pack kernels OR into a zero-filled output: the fill runs on the side stream, beside the match kernel, instead of
+    // between the Huffman and the pack kernels (every entry point is synchronous, so nothing else is using the buffer).  While
+    // `ptr` is set a fill may still be running on the caller's buffer: no entry point returns before join() or settle().
+    struct Prezero {
+        Ctx *c;
+        const void *ptr = nullptr;
+        uint64_t bytes = 0;
+        // forget what was noted; bytes != 0: fork from c->stream (behind whatever the caller's stream still has queued on d_out: a
+        // consumer of the previous encode, an allocator-reused block), fill on the side stream, record ev_zero → whether it took
+        bool start(void *d_out, uint64_t bytes);
+        // `st` waits for the fill of exactly d_out[0, bytes) — or fills it itself when no such fill is in flight
+        hipError_t join(hipStream_t st, void *d_out, uint64_t bytes);
+        // the host waits for a fill in flight and forgets it
+        void settle();
+    } prezero{this};
     // Every entry point that touches the context's scratch holds this lock: handles (encoders, decoders, LZ77 plug-ins)
     // of one context may live on different threads, they simply take turns on the GPU (SURVEY §8b threading row).
     std::recursive_mutex mu;
@@ -140,7 +152,7 @@ struct Ctx {
         return e;
     }
 
-    // state between encode_prepare and encode_emit
+    // state between encode_prepare and encode_emit (lfx_encode.cpp)
     uint32_t cur_nchunks = 0, cur_nblocks = 0;
     uint64_t cur_ntiles = 0, cur_n = 0;
     const uint32_t *cur_tile_map = nullptr;   // tile → chunk table of the prepared encode (lives in d_chunkmap)
@@ -198,14 +210,5 @@ struct Ctx {
     int n_ev = 0;
     void phase(const char *name);
 };
-
-// code words made on the host by a caller-supplied Lz77Encode (lfx_encoder_write_codes): contiguous, chunk after chunk
-struct HostCodes {
-    const uint32_t *codes;        // n_codes words, (val << 16) | dist, every block's EndOfBlock included
-    uint64_t n_codes;
-    const uint32_t *chunk_codes;  // codes per chunk of the plan
-};
-int encode_prepare(Ctx *c, const struct Plan &plan, const struct PlanOpts &po, const uint8_t *d_in,
-                   uint64_t n, int ck_mode, const HostCodes *hc = nullptr);
 
 }  // namespace lfx

@@ -118,7 +118,7 @@ int member_loop(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_
         MemberResult mr;
         if (sizes_only) rc = size_member(c, d_in + base, n - base, off0, mr);
         else {
-            mr.ck_mode = format == LFX_GZIP ? 1 : format == LFX_ZLIB ? 2 : 0;
+            mr.ck_mode = ck_mode_of(format);
             mr.trailer_len = format == LFX_GZIP ? 8 : format == LFX_ZLIB ? 4 : 0;
             rc = inflate_member(c, d_in + base, n - base, off0, d_out + out_at, cap - out_at, mr);
         }
@@ -183,14 +183,6 @@ int parse_headers(Ctx *c, int format, const uint8_t *d_in, const std::vector<Dec
     }
     if (d_streams) *d_streams = ds;
     if (d_hdrs) *d_hdrs = dh;
-    return LFX_OK;
-}
-
-// the input of a host variant, staged like lfx_decode_host's
-int stage_in(Ctx *c, const void *in, uint64_t n) {
-    int rc;
-    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
-    if (int hr = host_to_device(c, c->d_io_in.p, in, n, c->stream)) { c->set_error("host to device copy failed"); return hr; }
     return LFX_OK;
 }
 

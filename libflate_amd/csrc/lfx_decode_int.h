@@ -10,23 +10,7 @@
 #include "lfx_ctx.h"
 #include "lfx_decode.h"
 #include "lfx_stages.h"
-
-#define HIP_TRY(expr)                                                                 \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess) {                                                       \
-            c->set_error(std::string(#expr) + ": " + hipGetErrorString(e_));          \
-            return LFX_E_DEVICE;                                                      \
-        }                                                                             \
-    } while (0)
-#define LAUNCH_TRY(call)                                                              \
-    do {                                                                              \
-        int e_ = (call);                                                              \
-        if (e_) {                                                                     \
-            c->set_error(std::string(#call) + ": " + hipGetErrorString((hipError_t)e_)); \
-            return LFX_E_DEVICE;                                                      \
-        }                                                                             \
-    } while (0)
+#include "lfx_try.h"
 
 namespace lfx {
 

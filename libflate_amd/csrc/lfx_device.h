@@ -9,15 +9,6 @@
 
 namespace lfx {
 
-// one workgroup's share of the match search: positions [start, start+len) of a chunk
-struct SegDesc {
-    uint32_t chunk;
-    uint32_t start;
-    uint32_t len;
-    uint32_t lnk_base;   // lfx_match7 / lfx_match5: first entry of the segment's private link region, in units of 64 entries (128 bytes)
-};
-constexpr uint32_t SEG_POSITIONS = 256 * 1024;
-
 struct EncodeResult {
     uint64_t end_bit;    // bit after the last DEFLATE bit (absolute, container header included)
     uint64_t out_bytes;  // bytes of output relative to the output base
@@ -33,12 +24,6 @@ struct BatchStream {
     uint64_t in_off, in_len;
     uint64_t out_off, out_cap;
     uint32_t first_block, n_blocks;
-};
-
-// one workgroup of the parse walk: PARSE_WG_SEGS consecutive parse segments of one chunk, from segment seg0 on
-struct ParseWg {
-    uint32_t chunk;
-    uint32_t seg0;
 };
 
 int launch_match(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks,
@@ -120,6 +105,8 @@ int launch_pack(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Chun
 // sixteen 64 KiB spans — sixteen wavefronts on the whole GPU, each walking sixteen dependent pieces: 0.12 ms; 16 MiB are 256)
 inline uint32_t ck_span(uint64_t n) { return n <= (64ull << 20) ? 8192u : 65536u; }
 inline uint64_t ck_nspans(uint64_t n) { return div_up(n ? n : 1, ck_span(n)); }   // partials needed: 3 x 4 bytes each
+// the checksum a container's trailer holds, as launch_checksum's mode (raw DEFLATE: none)
+inline int ck_mode_of(int format) { return format == LFX_GZIP ? 1 : format == LFX_ZLIB ? 2 : 0; }
 int launch_checksum(hipStream_t st, const uint8_t *in, uint64_t n, uint32_t *crc_part,
                     uint32_t *a_part, uint32_t *b_part, EncodeResult *res,
                     int mode = 3)   /* bit 0: CRC-32, bit 1: Adler-32 (the other result is then 0) */;

@@ -1,0 +1,499 @@
+// lfx_encode.cpp — the encode core behind every encode entry point of lfx_api.cpp: encode_prepare as a sequence of stages,
+// encode_emit, and the steps the entry points share.  Every byte of compression work runs on the GPU.
+#include "lfx_encode_int.h"
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "lfx_encode_stages.h"
+
+namespace lfx {
+
+// ------------------------------------------------------------------------------------------------
+// the side-stream zero fill of an output buffer
+bool Ctx::Prezero::start(void *d_out, uint64_t n) {
+    ptr = nullptr;
+    if (!n) return false;
+    if (hipEventRecord(c->ev_fork, c->stream) != hipSuccess || hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) != hipSuccess ||
+        hipMemsetAsync(d_out, 0, n, c->side_stream) != hipSuccess || hipEventRecord(c->ev_zero, c->side_stream) != hipSuccess)
+        return false;
+    ptr = d_out;
+    bytes = n;
+    return true;
+}
+hipError_t Ctx::Prezero::join(hipStream_t st, void *d_out, uint64_t n) {
+    hipError_t e = hipSuccess;
+    if (ptr && ptr == d_out && bytes == n) e = hipStreamWaitEvent(st, c->ev_zero, 0);
+    else if (n) e = hipMemsetAsync(d_out, 0, n, st);
+    if (e == hipSuccess) ptr = nullptr;      // (a failure leaves the fill to settle())
+    return e;
+}
+void Ctx::Prezero::settle() {
+    if (ptr) (void)hipEventSynchronize(c->ev_zero);
+    ptr = nullptr;
+}
+
+namespace {
+
+// typed views of the context's buffers for one encode_prepare call (valid behind reserve_scratch)
+struct EncView {
+    const ChunkDesc *chunks;
+    const BlockDesc *blocks;
+    const SegDesc *segs;
+    const ParseWg *pwgs;
+    uint16_t *cd;
+    uint32_t *codes, *ncodes, *stage, *segtmp, *hist, *ck;
+    uint64_t *vis;
+    EncodeResult *res;
+    uint32_t *tile_map, *seg_map, *d_match_flags;
+    uint64_t *mdbg;               // LFX_DEBUG: per-wavefront cycle counters of workgroup 0
+};
+// one encode_prepare call: its arguments, its geometry and what the stages hand on
+struct EncCall {
+    const Plan &plan;
+    const PlanOpts &po;
+    const uint8_t *d_in;
+    uint64_t n;
+    int ck_mode;
+    const HostCodes *hc;
+    bool match_v1;                // the first-generation match kernel: it once saw a lane-order violation (or LFX_MATCH_V1 is set)
+    EncodeGeom g;
+    uint64_t nspans = 0;          // partial results of the checksum kernels
+    bool forked = false;          // the first half of the checksum's sweep is on the side stream already
+    EncView v{};
+};
+
+// ---- LFX_DEBUG dumps (each behind a synchronous copy, where the stage that calls it stands in the stream)
+void dbg_match(Ctx *c, const EncCall &k) {
+    uint64_t hv[256];
+    (void)hipMemcpy(hv, k.v.mdbg, sizeof hv, hipMemcpyDeviceToHost);
+    const bool match_v1 = k.match_v1, v5 = !match_v1 && c->diag.match_v5, v7 = !match_v1 && !c->diag.match_v5;
+    if (v7) {
+        // lfx_match7: wave 0 = exchange on head, wave 1 = exchange on second, waves 2..15 = helpers
+        for (int w = 0; w < 16; w++)
+            fprintf(stderr, "[lfx] match7 wave%d: work=%llu barrier-wait=%llu tiles=%llu\n", w, (unsigned long long)hv[w * 8],
+                    (unsigned long long)hv[w * 8 + 1], (unsigned long long)hv[w * 8 + 5]);
+    } else {
+        for (int w = 0; w < 16; w++)
+            fprintf(stderr, "[lfx] match%s wave%d: %s=%llu %s=%llu wait=%llu tiles=%llu\n", match_v1 ? "1" : "5", w,
+                    match_v1 ? "load" : "phaseA", (unsigned long long)hv[w * 8], match_v1 ? "work" : "phaseB",
+                    (unsigned long long)hv[w * 8 + 1], (unsigned long long)hv[w * 8 + 2], (unsigned long long)hv[w * 8 + 5]);
+    }
+    if (v5) {
+        uint64_t handed = 0;
+        for (int w = 1; w < 16; w++) handed += hv[128 + w * 8 + 5];
+        fprintf(stderr, "[lfx] match5 workgroup 0: %llu walks handed over to wave 0 of %llu positions; wave 0 waited %llu cycles for their loads\n",
+                (unsigned long long)handed, (unsigned long long)hv[5] * 960ull, (unsigned long long)hv[6]);
+        for (int w = 1; w < 16; w++)
+            fprintf(stderr, "[lfx] match5 wave%d loop trips: sum=%u max=%u tiles>4=%u tiles>8=%u\n", w, (unsigned)hv[w * 8 + 3],
+                    (unsigned)(hv[w * 8 + 3] >> 32), (unsigned)hv[w * 8 + 4], (unsigned)(hv[w * 8 + 4] >> 32));
+    }
+}
+// LFX_DUMP_SEG: the parse state of one segment behind the walk, behind fixseg and at the end
+int dbg_dump_seg(Ctx *c, const EncCall &k) {
+    const EncView &v = k.v;
+    hipStream_t st = c->stream;
+    const uint32_t sg = (uint32_t)atoi(getenv("LFX_DUMP_SEG"));
+    for (int stage_no = 1; stage_no <= 3 && sg < k.plan.n_segs; stage_no++) {
+        LAUNCH_TRY(launch_parse(st, k.d_in, k.n, v.chunks, c->cur_nchunks, k.plan.n_segs, v.pwgs, (uint32_t)k.g.pwgs.size(), v.cd,
+                                k.po.max_length, v.vis, v.segtmp, v.codes, v.ncodes, v.stage, v.seg_map, stage_no % 3));
+        (void)hipStreamSynchronize(st);
+        uint64_t vw[4];
+        uint32_t t[6];
+        uint16_t cdv[64];
+        (void)hipMemcpy(vw, v.vis + (uint64_t)sg * 64, sizeof vw, hipMemcpyDeviceToHost);
+        for (int q = 0; q < 6; q++) (void)hipMemcpy(&t[q], v.segtmp + (size_t)q * k.plan.n_segs + sg, 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(cdv, v.cd + (uint64_t)sg * PARSE_SEG, sizeof cdv, hipMemcpyDeviceToHost);
+        fprintf(stderr, "[lfx] seg %u stage %d: vis %016llx %016llx %016llx %016llx exit=%u count=%u off=%u exit2=%u mpos=%u kspec=%u\n", sg,
+                stage_no, (unsigned long long)vw[0], (unsigned long long)vw[1], (unsigned long long)vw[2], (unsigned long long)vw[3], t[0],
+                t[1], t[2], t[3], t[4], t[5]);
+        if (stage_no == 1) { fprintf(stderr, "[lfx]  cd:"); for (int q = 0; q < 64; q++) fprintf(stderr, " %u", cdv[q]); fprintf(stderr, "\n"); }
+    }
+    return LFX_OK;
+}
+void dbg_walk(const EncCall &k) {
+    uint64_t hv[32];
+    (void)hipMemcpy(hv, k.v.mdbg + 256, sizeof hv, hipMemcpyDeviceToHost);
+    for (int w = 0; w < 4; w++)
+        fprintf(stderr, "[lfx] walk wave%d: fill=%llu spec=%llu resolve+chain=%llu emit=%llu cycles\n", w, (unsigned long long)hv[w * 8],
+                (unsigned long long)hv[w * 8 + 1], (unsigned long long)hv[w * 8 + 2], (unsigned long long)hv[w * 8 + 3]);
+}
+void dbg_huffman(const EncCall &k) {
+    uint64_t hv[24];
+    (void)hipMemcpy(hv, k.v.mdbg + 512, sizeof hv, hipMemcpyDeviceToHost);
+    static const char *nm[10] = {"lit: rank sort", "lit: depth", "lit: package-merge", "lit: widths", "lit: codes", "dist tree", "run lengths",
+                                 "code-length tree", "header bits", "body size"};
+    fprintf(stderr, "[lfx] huffman block 0 (cycles):");
+    for (int q = 0; q < 10; q++) fprintf(stderr, " %s=%llu", nm[q], (unsigned long long)(hv[q + 1] - hv[q]));
+    fprintf(stderr, "\n");
+}
+
+// ---- the stages of encode_prepare
+int reserve_scratch(Ctx *c, EncCall &k) {
+    const Plan &plan = k.plan;
+    const bool hc = k.hc != nullptr, match_v1 = k.match_v1;
+    const uint32_t nchunks = c->cur_nchunks, nblocks = c->cur_nblocks;
+    const uint64_t n = k.n, lnk_units = k.g.lnk_units;
+    const size_t nsegs = k.g.segs.size();
+    int rc;
+    if ((rc = c->d_chunks.reserve(sizeof(ChunkDesc) * std::max<size_t>(nchunks, 1)))) return rc;
+    if ((rc = c->d_blocks.reserve(sizeof(BlockDesc) * std::max<size_t>(nblocks, 1)))) return rc;
+    if ((rc = c->d_segs.reserve(sizeof(SegDesc) * std::max<size_t>(nsegs, 1)))) return rc;
+    if ((rc = c->d_pwgs.reserve(sizeof(ParseWg) * std::max<size_t>(k.g.pwgs.size(), 1)))) return rc;
+    if (!hc && (rc = c->d_cd.reserve(2 * n + 64))) return rc;                   // candidate distances, 16 bits per position
+    if (!hc && !match_v1 && (rc = c->d_glnk.reserve(264 * std::max<uint64_t>(lnk_units, 1)))) return rc;   // lfx_match7: link records (4 bytes) + ballot words (8 bytes per 64); lfx_match5: links (2 bytes)
+    if (!hc && !match_v1 && (rc = c->d_ucount.reserve(4 * std::max<size_t>(nsegs, 1)))) return rc;   // lfx_match7: unresolved positions per segment
+    if (!hc && match_v1 && (rc = c->d_md.reserve(4 * std::max<uint64_t>(n, 1)))) return rc;   // first-generation kernel: (length, distance) words
+    if ((rc = c->d_codes.reserve(4 * std::max<uint64_t>(plan.n_codes_cap, 1)))) return rc;
+    if ((rc = c->d_ncodes.reserve(4 * std::max<size_t>(nchunks, 1)))) return rc;
+    if ((rc = c->d_vis.reserve(8 * std::max<uint64_t>(plan.n_vis, 1)))) return rc;
+    if ((rc = c->d_segtmp.reserve(24ull * std::max<uint32_t>(plan.n_segs, 1)))) return rc;
+    if (!hc && (rc = c->d_stage.reserve(4ull * (n + 64)))) return rc;   // code words staged by the speculative parse walk
+    if ((rc = c->d_chunkmap.reserve(4ull * (plan.n_tiles + plan.n_segs + 2)))) return rc;   // tile → chunk, segment → chunk
+    if ((rc = c->d_hist.reserve(4ull * 320 * std::max<size_t>(nblocks, 1)))) return rc;
+    if ((rc = c->d_bc.reserve(sizeof(BlockCodes) * std::max<size_t>(nblocks, 1)))) return rc;
+    if ((rc = c->d_block_start.reserve(8 * std::max<size_t>(nblocks, 1)))) return rc;
+    if ((rc = c->d_tile_bits.reserve(4 * std::max<uint64_t>(plan.n_tiles, 1)))) return rc;
+    if ((rc = c->d_tile_start.reserve(8 * std::max<uint64_t>(plan.n_tiles, 1)))) return rc;
+    k.nspans = ck_nspans(n);
+    if ((rc = c->d_ck.reserve(12 * k.nspans))) return rc;
+    if ((rc = c->d_res.reserve(256))) return rc;
+    if ((rc = c->d_small.reserve(70000))) return rc;
+    EncView &v = k.v;
+    v.chunks = (const ChunkDesc *)c->d_chunks.p; v.blocks = (const BlockDesc *)c->d_blocks.p;
+    v.segs = (const SegDesc *)c->d_segs.p; v.pwgs = (const ParseWg *)c->d_pwgs.p;
+    v.cd = (uint16_t *)c->d_cd.p; v.codes = (uint32_t *)c->d_codes.p; v.ncodes = (uint32_t *)c->d_ncodes.p;
+    v.stage = (uint32_t *)c->d_stage.p; v.segtmp = (uint32_t *)c->d_segtmp.p; v.hist = (uint32_t *)c->d_hist.p;
+    v.ck = (uint32_t *)c->d_ck.p; v.vis = (uint64_t *)c->d_vis.p; v.res = (EncodeResult *)c->d_res.p;
+    v.tile_map = (uint32_t *)c->d_chunkmap.p; v.seg_map = v.tile_map + plan.n_tiles;
+    v.d_match_flags = (uint32_t *)((uint8_t *)c->d_res.p + offsetof(EncodeResult, match_flags));
+    v.mdbg = c->diag.debug ? (uint64_t *)((uint8_t *)c->d_small.p + 32768) : nullptr;
+    return LFX_OK;
+}
+
+// A plan table: uploaded from a shadow kept on the context (it outlives the asynchronous copy: no synchronisation), and not
+// at all when the same table already sits in the same device buffer (an encode loop over equal-sized inputs)
+hipError_t upload_table(Ctx *c, int slot, DevBuf &b, const void *src, size_t bytes) {
+    std::vector<uint8_t> &sh = c->up_shadow[slot];
+    const uint64_t tag = (uint64_t)(uintptr_t)b.p ^ ((uint64_t)b.gen << 48) ^ (1ull << 63);
+    if (c->up_dev[slot] == tag && sh.size() == bytes && (bytes == 0 || memcmp(sh.data(), src, bytes) == 0)) return hipSuccess;
+    sh.assign((const uint8_t *)src, (const uint8_t *)src + bytes);
+    c->up_dev[slot] = tag;
+    return bytes ? hipMemcpyAsync(b.p, sh.data(), bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+}
+int upload_tables(Ctx *c, const EncCall &k) {
+    HIP_TRY(upload_table(c, 0, c->d_chunks, k.plan.chunks.data(), sizeof(ChunkDesc) * k.plan.chunks.size()));
+    HIP_TRY(upload_table(c, 1, c->d_blocks, k.plan.blocks.data(), sizeof(BlockDesc) * k.plan.blocks.size()));
+    HIP_TRY(upload_table(c, 2, c->d_segs, k.g.segs.data(), sizeof(SegDesc) * k.g.segs.size()));
+    HIP_TRY(upload_table(c, 3, c->d_pwgs, k.g.pwgs.data(), sizeof(ParseWg) * k.g.pwgs.size()));
+    c->phase("upload");
+    return LFX_OK;
+}
+
+// tile → chunk and segment → chunk.  The call's first kernel also clears the blocks' symbol counters, the result record and the
+// match stage's per-segment counts (three fill operations in front of the match kernel before: 22 us of a 4.6 ms step)
+int chunk_maps(Ctx *c, const EncCall &k) {
+    const bool ucount_here = !k.hc && !k.match_v1 && !c->diag.match_v5;
+    const ZeroSpan z_hist{k.v.hist, (uint32_t)(320 * std::max<size_t>(c->cur_nblocks, 1))}, z_res{(uint32_t *)c->d_res.p, 64u},
+        z_ucount{ucount_here ? (uint32_t *)c->d_ucount.p : nullptr, ucount_here ? (uint32_t)std::max<size_t>(k.g.segs.size(), 1) : 0u};
+    c->cur_tile_map = k.v.tile_map;
+    if (int e_ = launch_chunk_maps(c->stream, k.v.chunks, c->cur_nchunks, k.plan.n_tiles, k.plan.n_segs, k.v.tile_map, k.v.seg_map, z_hist,
+                                   z_res, z_ucount)) {
+        c->set_error(hipGetErrorString((hipError_t)e_));
+        return LFX_E_DEVICE;
+    }
+    return LFX_OK;
+}
+
+// the caller's own Lz77Encode produced the code words (EncodeOptions::with_lz77(E), encode.rs:59-65): they take the place of
+// the match + parse stages' output — one chunk per block, EndOfBlock included; everything from the histogram on
+// (CompressBuf::flush, encode.rs:416-425) runs as for the built-in encoders
+int upload_codes(Ctx *c, const EncCall &k) {
+    hipStream_t st = c->stream;
+    if (k.hc->n_codes) HIP_TRY(hipMemcpyAsync(c->d_codes.p, k.hc->codes, 4ull * k.hc->n_codes, hipMemcpyHostToDevice, st));
+    if (c->cur_nchunks) HIP_TRY(hipMemcpyAsync(c->d_ncodes.p, k.hc->chunk_codes, 4ull * c->cur_nchunks, hipMemcpyHostToDevice, st));
+    c->phase("codes_upload");
+    return LFX_OK;
+}
+
+// lfx_match7: the candidate kernel, then the positions it leaves open (0.5 % of a text): ballot words → lists → walks.
+// (Measured, round 5: the segments in four parts, the resolver of a part on the side stream beside the next part's
+//  kernel — `LFX_MATCH_PARTS=4` — 1.10 ms against 1.15 in one piece at 256 MiB: a part of 256 workgroups ends with
+//  its slowest segment, and the compaction waits for slots behind the kernel.  The resolver with four walks in
+//  flight per lane made the overlap pointless.)
+int match7(Ctx *c, const EncCall &k) {
+    const EncView &v = k.v;
+    hipStream_t st = c->stream;
+    const uint32_t ns = (uint32_t)k.g.segs.size();
+    const uint32_t parts = match7_parts(ns, (uint32_t)std::max(c->n_cu, 1), c->diag.match_parts);
+    uint32_t *d_glnk = (uint32_t *)c->d_glnk.p;
+    uint64_t *d_umask = (uint64_t *)((uint8_t *)c->d_glnk.p + 256 * std::max<uint64_t>(k.g.lnk_units, 1));
+    uint32_t *d_ucount = (uint32_t *)c->d_ucount.p;     // (cleared by the call's first kernel, launch_chunk_maps)
+    for (uint32_t q = 0; q < parts; q++) {
+        const uint32_t s0 = (uint32_t)((uint64_t)ns * q / parts), s1 = (uint32_t)((uint64_t)ns * (q + 1) / parts);
+        LAUNCH_TRY(launch_match7(st, k.d_in, k.n, v.chunks, v.segs + s0, s1 - s0, k.po.window_size, v.cd, d_glnk, d_umask,
+                                 v.d_match_flags, q == 0 ? v.mdbg : nullptr));
+        if (parts == 1 && c->timing_fine()) c->phase("lz77_cand");
+        hipStream_t rs = parts > 1 ? c->side_stream : st;
+        if (parts > 1) {
+            HIP_TRY(hipEventRecord(c->ev_part[q], st));
+            HIP_TRY(hipStreamWaitEvent(rs, c->ev_part[q], 0));
+        }
+        LAUNCH_TRY(launch_resolve7(rs, v.chunks, v.segs + s0, s1 - s0, k.po.window_size, v.cd, d_glnk, d_umask, v.stage, d_ucount + s0,
+                                   (uint32_t)std::max(c->diag.r7_cap, 0)));
+    }
+    if (parts > 1) {
+        HIP_TRY(hipEventRecord(c->ev_res, c->side_stream));
+        HIP_TRY(hipStreamWaitEvent(st, c->ev_res, 0));
+    }
+    return LFX_OK;
+}
+
+// candidate distances for every position: lfx_match7 unless the context fell back to (or LFX_MATCH_V1 asks for) the
+// first-generation kernel, or LFX_MATCH_V5 asks for lfx_match5
+int stage_match(Ctx *c, const EncCall &k) {
+    const EncView &v = k.v;
+    hipStream_t st = c->stream;
+    const uint32_t ns = (uint32_t)k.g.segs.size();
+    if (k.match_v1) {
+        LAUNCH_TRY(launch_match(st, k.d_in, k.n, v.chunks, v.segs, ns, k.po.window_size, k.po.max_length, (uint32_t *)c->d_md.p, v.mdbg));
+        LAUNCH_TRY(launch_md_to_cd(st, (const uint32_t *)c->d_md.p, k.n, v.cd));
+    } else if (!c->diag.match_v5) {
+        if (int rc = match7(c, k)) return rc;
+    } else {
+        LAUNCH_TRY(launch_match5(st, k.d_in, k.n, v.chunks, v.segs, ns, k.po.window_size, v.cd, (uint16_t *)c->d_glnk.p, v.d_match_flags,
+                                 v.mdbg));
+    }
+    if (v.mdbg) dbg_match(c, k);
+    c->phase(c->timing_fine() ? "lz77_resolve" : "lz77_match");
+    return LFX_OK;
+}
+
+// the greedy walk → code words per chunk (and, fused_hist, the blocks' symbol counts); with a checksum the first half of its
+// sweep goes to the side stream from behind the walk kernel on
+int stage_parse(Ctx *c, EncCall &k) {
+    const EncView &v = k.v;
+    hipStream_t st = c->stream;
+    const bool want_checksum = k.ck_mode != 0;
+    if (c->diag.debug && getenv("LFX_DUMP_SEG"))
+        if (int rc = dbg_dump_seg(c, k)) return rc;
+    // (fine timing: the walk kernel in a bracket of its own — the same launches in two calls)
+    for (int part = c->timing_fine() ? 1 : 0; part <= (c->timing_fine() ? 2 : 0); part++) {
+        LAUNCH_TRY(launch_parse(st, k.d_in, k.n, v.chunks, c->cur_nchunks, k.plan.n_segs, v.pwgs, (uint32_t)k.g.pwgs.size(), v.cd,
+                                k.po.max_length, v.vis, v.segtmp, v.codes, v.ncodes, v.stage, v.seg_map, part == 1 ? 1 : 0,
+                                v.mdbg ? v.mdbg + 256 : nullptr, k.g.fused_hist ? v.hist : nullptr, k.g.emit_per, k.g.emit_parts,
+                                want_checksum ? c->ev_fork : nullptr, v.d_match_flags, part == 2 ? 1 : 0));
+        if (part == 1) c->phase("lz77_walk");
+    }
+    if (want_checksum) {
+        // the first half of the container checksum's sweep: on the side stream from behind the walk kernel on, beside the
+        // chaining kernels (one wavefront per segment and a handful of steps each: they leave most of the GPU idle); the
+        // second half beside the Huffman kernel (checksum_fork).  (Measured, round 6: all of it here ran into parse_emit — both
+        // want the memory system — parse + Huffman 1.13 ms; all of it behind the parse no longer fits under the Huffman
+        // kernel now that the histogram kernel is gone.)
+        HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
+        LAUNCH_TRY(launch_checksum_part(c->side_stream, k.d_in, k.n, v.ck, v.ck + k.nspans, v.ck + 2 * k.nspans, v.res, k.ck_mode, 0, 2));
+        k.forked = true;
+    }
+    if (v.mdbg) dbg_walk(k);
+    c->phase(c->timing_fine() ? "lz77_chain" : "lz77_parse");
+    return LFX_OK;
+}
+
+// the container checksum reads only the input: it runs on the side stream, beside the parse's chaining kernels (one wavefront
+// per segment, a handful of steps each) and the one-workgroup-per-block Huffman kernel, which leave most of the GPU idle
+// (forked: its first half went there behind the walk kernel, stage_parse).  The join: ev_join, waited for behind the Huffman kernel.
+int checksum_fork(Ctx *c, const EncCall &k) {
+    const EncView &v = k.v;
+    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
+    if (k.forked) LAUNCH_TRY(launch_checksum_part(c->side_stream, k.d_in, k.n, v.ck, v.ck + k.nspans, v.ck + 2 * k.nspans, v.res, k.ck_mode, 1, 2));
+    else LAUNCH_TRY(launch_checksum(c->side_stream, k.d_in, k.n, v.ck, v.ck + k.nspans, v.ck + 2 * k.nspans, v.res, k.ck_mode));
+    HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
+    return LFX_OK;
+}
+
+// the blocks' symbol counts where the parse did not take them (a caller's own code words, LFX_HIST_SEPARATE, very unequal
+// chunks), then one workgroup per block builds its codes
+int stage_huffman(Ctx *c, const EncCall &k) {
+    const EncView &v = k.v;
+    hipStream_t st = c->stream;
+    if (!k.g.fused_hist) LAUNCH_TRY(launch_histogram(st, v.chunks, c->cur_nchunks, k.g.split, v.codes, v.ncodes, v.hist));
+    c->phase("histogram");
+    LAUNCH_TRY(launch_huffman(st, v.blocks, c->cur_nblocks, v.hist, (BlockCodes *)c->d_bc.p, v.mdbg ? v.mdbg + 512 : nullptr));
+    c->phase("huffman");
+    if (v.mdbg) dbg_huffman(k);
+    return LFX_OK;
+}
+
+}  // namespace
+
+int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *d_in, uint64_t n, int ck_mode, const HostCodes *hc) {
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    EncCall k{plan, po, d_in, n, ck_mode, hc, c->force_match_v1 || c->diag.match_v1,
+              encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate)};
+    if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
+    if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)
+    c->cur_nchunks = (uint32_t)plan.chunks.size();
+    c->cur_nblocks = (uint32_t)plan.blocks.size();
+    c->cur_ntiles = plan.n_tiles;
+    c->cur_n = n;
+    c->cur_in = d_in;
+    int rc;
+    if ((rc = reserve_scratch(c, k))) return rc;
+    if ((rc = upload_tables(c, k))) return rc;
+    if ((rc = chunk_maps(c, k))) return rc;
+    if (hc) rc = upload_codes(c, k);
+    else if (!(rc = stage_match(c, k))) rc = stage_parse(c, k);
+    if (rc) return rc;
+    if (ck_mode && (rc = checksum_fork(c, k))) return rc;
+    if ((rc = stage_huffman(c, k))) return rc;
+    if (ck_mode) {
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+        c->phase("checksum");
+    }
+    return LFX_OK;
+}
+
+int pack_blocks(Ctx *c, void *d_out) {
+    LAUNCH_TRY(launch_pack(c->stream, c->cur_in, c->cur_n, (const ChunkDesc *)c->d_chunks.p, c->cur_nchunks,
+                           (const BlockDesc *)c->d_blocks.p, c->cur_nblocks, c->cur_ntiles,
+                           (const uint32_t *)c->d_codes.p, (const uint32_t *)c->d_ncodes.p,
+                           (const BlockCodes *)c->d_bc.p, (const uint64_t *)c->d_block_start.p,
+                           (uint32_t *)c->d_tile_bits.p, (uint64_t *)c->d_tile_start.p, (const EncodeResult *)c->d_res.p, 0,
+                           (uint32_t *)d_out, c->cur_tile_map));
+    return LFX_OK;
+}
+
+int encode_emit(Ctx *c, int format, bool with_trailer, uint32_t trailer_check, bool use_device_check,
+                uint64_t total_n, const uint8_t *prefix, uint32_t prefix_len, uint64_t start_bit,
+                uint8_t *d_out, uint64_t cap, EncodeResult *host_res, EncodeResult *async_slot) {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    if (((uintptr_t)d_out & 3) != 0) { c->set_error("output buffer must be 4-byte aligned"); return LFX_E_ARG; }
+    const uint64_t trailer = with_trailer ? (format == LFX_GZIP ? 8 : format == LFX_ZLIB ? 4 : 0) : 0;
+    if (cap < prefix_len + trailer + 8) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
+    const uint64_t cap_words = cap / 4;  // whole dwords only (kernels write dwords)
+    const uint64_t cap_bits = (cap_words * 4 - trailer) * 8;
+    HIP_TRY(c->prezero.join(st, d_out, cap_words * 4));
+    c->phase("memset_out");
+    EncodeResult *dres = (EncodeResult *)c->d_res.p;
+    LAUNCH_TRY(launch_offsets(st, (const BlockDesc *)c->d_blocks.p, c->cur_nblocks, (const BlockCodes *)c->d_bc.p,
+                              start_bit, cap_bits, (uint64_t *)c->d_block_start.p, dres));
+    if (int rc = pack_blocks(c, d_out)) return rc;
+    c->phase("pack");
+    if (prefix_len) {
+        // (a gzip header holds an unbounded file name / comment: its own buffer, sized to fit)
+        int rcp = c->d_hdr.reserve(prefix_len);
+        if (rcp) return rcp;
+        HIP_TRY(hipMemcpyAsync(c->d_hdr.p, prefix, prefix_len, hipMemcpyHostToDevice, st));
+        LAUNCH_TRY(launch_put_bytes(st, (const uint8_t *)c->d_hdr.p, prefix_len, 0, (uint32_t *)d_out));
+    }
+    if (!use_device_check) {
+        // combined checksum supplied by the caller (sharded encode): patch the device result
+        HIP_TRY(hipMemcpyAsync((uint8_t *)dres + offsetof(EncodeResult, crc32), &trailer_check, 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync((uint8_t *)dres + offsetof(EncodeResult, adler32), &trailer_check, 4, hipMemcpyHostToDevice, st));
+    }
+    LAUNCH_TRY(launch_trailer(st, with_trailer ? format : LFX_DEFLATE, (uint32_t)total_n, 0, dres, (uint32_t *)d_out));
+    HIP_TRY(hipMemcpyAsync(async_slot ? (void *)async_slot : c->h_res, dres, sizeof(EncodeResult), hipMemcpyDeviceToHost, st));
+    c->phase("frame");
+    if (async_slot) return LFX_OK;
+    HIP_TRY(hipStreamSynchronize(st));
+    *host_res = *(EncodeResult *)c->h_res;
+    if (host_res->status != 0) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
+    return LFX_OK;
+}
+
+int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &b, std::vector<uint64_t> &h_len,
+                 std::vector<int32_t> &h_status, EncodeResult &res) {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    const uint32_t count = (uint32_t)b.streams.size();
+    const uint32_t trailer = b.format == LFX_GZIP ? 8 : b.format == LFX_ZLIB ? 4 : 0;
+    // per-stream scratch: descriptors, checksums, end bits, status, lengths (+ the header bytes)
+    const size_t sz_streams = sizeof(BatchStream) * count;
+    DevBuf &sb = c->d_dec_streams;     // (decode scratch: free during an encode)
+    if (int rc = sb.reserve(sz_streams + (4 + 4 + 8 + 4 + 8) * (size_t)count + b.hdr.size() + 64)) return rc;
+    BatchStream *d_streams = (BatchStream *)sb.p;
+    uint64_t *d_end = (uint64_t *)((uint8_t *)sb.p + sz_streams);
+    uint64_t *d_len = d_end + count;
+    uint32_t *d_crc = (uint32_t *)(d_len + count), *d_adler = d_crc + count;
+    int32_t *d_status = (int32_t *)(d_adler + count);
+    uint8_t *d_hdr = (uint8_t *)(d_status + count);
+    h_len.resize(count);
+    h_status.resize(count);
+    return with_match_fallback(c, res, [&]() -> int {
+        if (int rc = encode_prepare(c, plan, po, b.d_in, b.in_extent, 0)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_streams, b.streams.data(), sz_streams, hipMemcpyHostToDevice, st));
+        if (!b.hdr.empty()) HIP_TRY(hipMemcpyAsync(d_hdr, b.hdr.data(), b.hdr.size(), hipMemcpyHostToDevice, st));
+        if (trailer)
+            LAUNCH_TRY(launch_checksum_ranges(st, b.d_in, count, (const uint64_t *)d_streams, sizeof(BatchStream) / 8,
+                                              (const uint64_t *)d_streams + 1, sizeof(BatchStream) / 8, d_crc, d_adler));
+        c->phase("checksum");
+        // (the span of all streams' ranges, on the main stream: the one fill that does not go through Prezero)
+        HIP_TRY(hipMemsetAsync(b.d_out + b.out_lo, 0, b.out_hi - b.out_lo, st));
+        EncodeResult *dres = (EncodeResult *)c->d_res.p;
+        LAUNCH_TRY(launch_offsets_batch(st, d_streams, count, (const BlockDesc *)c->d_blocks.p, (const BlockCodes *)c->d_bc.p,
+                                        (uint32_t)b.hdr.size(), trailer, (uint64_t *)c->d_block_start.p, d_end, d_status, dres));
+        if (int rc = pack_blocks(c, b.d_out)) return rc;
+        c->phase("pack");
+        LAUNCH_TRY(launch_frame_batch(st, b.format, d_streams, count, d_hdr, (uint32_t)b.hdr.size(), d_end, d_crc, d_adler, dres,
+                                      (uint32_t *)b.d_out, d_len));
+        HIP_TRY(hipMemcpyAsync(c->h_res, dres, sizeof(EncodeResult), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_len.data(), d_len, 8ull * count, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_status.data(), d_status, 4ull * count, hipMemcpyDeviceToHost, st));
+        c->phase("frame");
+        HIP_TRY(hipStreamSynchronize(st));
+        res = *(EncodeResult *)c->h_res;
+        return LFX_OK;
+    });
+}
+
+int encode_members(Ctx *c, const Plan &plan, const PlanOpts &po, const MembersCall &m, EncodeResult &res) {
+    hipStream_t st = c->stream;
+    const MembersGeom &g = m.g;
+    const uint32_t count = g.count;
+    // per-member scratch: records, offsets inside the workgroup, lengths, checksums; the workgroup sums; the header
+    const uint32_t nwg = (count + 255) / 256;
+    const size_t cnt = std::max<uint32_t>(count, 1);
+    DevBuf &sb = c->d_dec_streams;     // (decode scratch: free during an encode)
+    if (int rc = sb.reserve((sizeof(lfx_member) + 8 + 8 + 4 + 4) * cnt + 8 * (size_t)std::max<uint32_t>(nwg, 1) + m.hdr.size() + 64)) return rc;
+    lfx_member *d_members = (lfx_member *)sb.p;
+    uint64_t *d_local = (uint64_t *)(d_members + cnt), *d_mlen = d_local + cnt, *d_wg = d_mlen + cnt;
+    uint32_t *d_crc = (uint32_t *)(d_wg + std::max<uint32_t>(nwg, 1)), *d_adler = d_crc + cnt;
+    uint8_t *d_hdr = (uint8_t *)(d_adler + cnt);
+    // the kernels OR into zeros: [0, min(cap, bound)) is filled once, beside the match kernel; no member can end behind the
+    // bound, and nothing is written when the total exceeds cap
+    c->prezero.start(m.d_out, m.fill);
+    const int rc = with_match_fallback(c, res, [&]() -> int {
+        if (int rc2 = encode_prepare(c, plan, po, m.d_in, g.n, 0)) return rc2;
+        HIP_TRY(hipMemcpyAsync(d_hdr, m.hdr.data(), m.hdr.size(), hipMemcpyHostToDevice, st));
+        EncodeResult *dres = (EncodeResult *)c->d_res.p;
+        LAUNCH_TRY(launch_members_layout(st, g, (BlockDesc *)c->d_blocks.p, (const BlockCodes *)c->d_bc.p, d_local, d_mlen, d_wg, m.cap,
+                                         (uint64_t *)c->d_block_start.p, d_members, dres));
+        if (g.bgzf) c->up_dev[1] = 0;      // the device's block table no longer equals its shadow: the next prepare uploads it
+        c->phase("members_layout");
+        LAUNCH_TRY(launch_checksum_ranges(st, m.d_in, count, (const uint64_t *)d_members, sizeof(lfx_member) / 8,
+                                          (const uint64_t *)d_members + 1, sizeof(lfx_member) / 8, d_crc, d_adler));
+        c->phase("checksum");
+        HIP_TRY(c->prezero.join(st, m.d_out, m.fill));
+        if (int rc2 = pack_blocks(c, m.d_out)) return rc2;
+        c->phase("pack");
+        LAUNCH_TRY(launch_members_frame(st, g, d_hdr, d_members, d_crc, dres, (uint32_t *)m.d_out));
+        HIP_TRY(hipMemcpyAsync(c->h_res, dres, sizeof(EncodeResult), hipMemcpyDeviceToHost, st));
+        if (m.n_rec) HIP_TRY(hipMemcpyAsync(m.members, d_members, sizeof(lfx_member) * (size_t)m.n_rec, hipMemcpyDeviceToHost, st));
+        c->phase("frame");
+        HIP_TRY(hipStreamSynchronize(st));
+        res = *(EncodeResult *)c->h_res;
+        return LFX_OK;
+    });
+    c->prezero.settle();     // (failed before the stream waited for the fill: it is on the caller's buffer)
+    return rc;
+}
+
+}  // namespace lfx

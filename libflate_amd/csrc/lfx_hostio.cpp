@@ -120,6 +120,13 @@ int host_to_device(Ctx *c, void *d_dst, const void *h_src, uint64_t n, hipStream
     return LFX_OK;
 }
 
+int stage_in(Ctx *c, const void *in, uint64_t n) {
+    int rc;
+    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
+    if (int hr = host_to_device(c, c->d_io_in.p, in, n, c->stream)) { c->set_error("host to device copy failed"); return hr; }
+    return LFX_OK;
+}
+
 int device_to_host(Ctx *c, void *h_dst, const void *d_src, uint64_t n, hipStream_t st) {
     if (!n) return hipStreamSynchronize(st) == hipSuccess ? LFX_OK : LFX_E_DEVICE;
     if (n < HOSTIO_DIRECT_BELOW || is_pinned(h_dst, n) || c->hostio.init() != LFX_OK) {

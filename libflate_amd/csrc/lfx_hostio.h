@@ -68,6 +68,8 @@ struct HostIo {
 // h_src until `st` has passed the copy, so the caller's buffer must stay untouched until then (lfx_encode_host /
 // lfx_decode_host synchronise `st` before they return: their callers never see the difference).  → LFX status
 int host_to_device(Ctx *c, void *d_dst, const void *h_src, uint64_t n, hipStream_t st);
+// the input of a host variant: c->d_io_in[0, n) <- in[0, n) on c->stream (error text on the context)
+int stage_in(Ctx *c, const void *in, uint64_t n);
 // h_dst[0, n) <- d_src[0, n), after everything queued on `st` so far.  Complete on return.
 int device_to_host(Ctx *c, void *h_dst, const void *d_src, uint64_t n, hipStream_t st);
 

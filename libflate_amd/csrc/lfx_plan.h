@@ -33,6 +33,18 @@ struct Plan {
     uint64_t n_tiles = 0;      // pack tiles (upper bound)
     uint64_t n_vis = 0;        // visited-mask words
     uint32_t n_segs = 0;       // parse segments
+    // p, planned alone for bytes that lie at in_off, behind what is here: its descriptors shifted into the shared index spaces
+    // (batch and members encode: the kernels see one plan).  The 32-bit spaces are the caller's to guard.
+    void append(const Plan &p, uint64_t in_off) {
+        const uint32_t c0 = (uint32_t)chunks.size(), b0 = (uint32_t)blocks.size();
+        for (ChunkDesc ch : p.chunks) {
+            ch.in_off += in_off; ch.code_off += n_codes_cap; ch.block += b0; ch.tile_base += n_tiles;
+            ch.vis_base += n_vis; ch.seg_base += n_segs;
+            chunks.push_back(ch);
+        }
+        for (BlockDesc b : p.blocks) { b.in_off += in_off; b.first_chunk += c0; blocks.push_back(b); }
+        n_codes_cap += p.n_codes_cap; n_tiles += p.n_tiles; n_vis += p.n_vis; n_segs += p.n_segs;
+    }
 };
 
 class Planner {

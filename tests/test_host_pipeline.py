@@ -561,3 +561,22 @@ def test_decode_stage_arithmetic_tiles_ranges_and_regions(tmp_path):
     subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "c", "plan_stages.cpp")], check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "plan_stages ok: 20000 cases, 5000 layouts" in out.stdout, out.stdout[-400:]
+
+
+def test_encode_stage_arithmetic_segments_links_workgroups_and_append(tmp_path):
+    """The encode's host arithmetic (libflate_amd/csrc/lfx_encode_stages.h: no HIP call, a plain host compiler builds it) and
+    Plan::append (lfx_plan.h).  tests/c/encode_geom.cpp, over 4000 seeded plans of the real Planner and ten synthetic chunk
+    lists of many GiB, for 1, 64 and 256 compute units: the match segments tile their chunks at the one segment length the
+    halving rule gives, the link regions are even, ordered and disjoint and the refusal fires exactly when a base leaves 32
+    bits, the parse workgroups in launch order are the logical list dealt out in contiguous eighths with {0xFFFFFFFF, 0} for
+    the empty slots, the emit grid and the fused-histogram decision follow their formulas, and k appended copies of a plan are
+    shifted copies that keep the planner's own invariants."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "encode_geom")
+    subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "c", "encode_geom.cpp")], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "encode_geom ok: 4000 plans, 10 synthetic lists" in out.stdout, out.stdout[-400:]
