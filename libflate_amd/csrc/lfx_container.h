@@ -1,5 +1,6 @@
 // lfx_container.h — gzip / zlib container header parse, ONE source for the device kernel (batch and one-shot
-// decodes: one lane per stream) and for the host stream decoder (header-first construction, header getters).
+// decodes: one lane per stream) and for the host stream decoder (header-first construction, header getters).  No HIP
+// include: a plain host compiler builds it too.
 //
 // Reference behaviour reproduced (sile/libflate v2.3.0):
 //   src/zlib.rs:221-266   Header::read_from: (CMF*256 + FLG) % 31, CM = 8, CINFO <= 7, FDICT rejected
@@ -11,7 +12,7 @@
 #include <stdint.h>
 
 #include "lfx_common.h"
-#include "lfx_decode.h"
+#include "lfx_blk.h"
 
 namespace lfx {
 

@@ -1,4 +1,4 @@
-// lfx_decode.cpp — host orchestration of the inflate path (C ABI: lfx_decode_*, lfx_decoder_*).
+// lfx_decode.cpp — host orchestration of the inflate path (C ABI: lfx_decode_*; the stream decoder: lfx_stream_dec.cpp).
 // Every compressed bit is decoded on the GPU; the host only sequences kernels, chains block
 // boundaries and formats error messages.
 #include "../../include/lfx.h"
@@ -18,8 +18,6 @@
 #include "lfx_container.h"
 #include "lfx_index.h"
 #include "lfx_bgzf.h"
-#include <thread>
-#include <chrono>
 
 static_assert(offsetof(lfx::DecStream, out_off) == 16 && sizeof(lfx::DecStream) % 8 == 0, "checksum_ranges stride");
 static_assert(offsetof(lfx::InflateResult, out_len) == 8 && sizeof(lfx::InflateResult) % 8 == 0, "checksum_ranges stride");
@@ -54,19 +52,7 @@ int verify_trailer(Ctx *c, int format, const uint8_t *d_in, uint64_t tpos, uint6
         c->phase("checksum");
         er = *(EncodeResult *)c->h_res;
     }
-    if (format == LFX_GZIP) {
-        const uint32_t crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
-        if (crc != er.crc32) {  // gzip.rs:1035-1040 (ISIZE is read but never verified)
-            oc.status = LFX_E_INVALID_DATA;
-            oc.msg = format_error(ERR_CRC32, er.crc32, crc);
-        }
-    } else {
-        const uint32_t ad = (uint32_t)t[0] << 24 | (uint32_t)t[1] << 16 | (uint32_t)t[2] << 8 | t[3];
-        if (ad != er.adler32) {
-            oc.status = LFX_E_INVALID_DATA;
-            oc.msg = format_error(ERR_ADLER32, er.adler32, ad);
-        }
-    }
+    if (const int bad = check_trailer(format, t, er.crc32, er.adler32, oc.msg)) oc.status = bad;
     return LFX_OK;
 }
 
@@ -119,7 +105,7 @@ int member_loop(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_
         if (sizes_only) rc = size_member(c, d_in + base, n - base, off0, mr);
         else {
             mr.ck_mode = ck_mode_of(format);
-            mr.trailer_len = format == LFX_GZIP ? 8 : format == LFX_ZLIB ? 4 : 0;
+            mr.trailer_len = trailer_len(format);
             rc = inflate_member(c, d_in + base, n - base, off0, d_out + out_at, cap - out_at, mr);
         }
         if (rc) return rc;
@@ -129,7 +115,7 @@ int member_loop(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_
         if (mr.status != LFX_OK) { oc.status = mr.status; oc.msg = mr.msg; return LFX_OK; }
         // ---- trailer
         if (format != LFX_DEFLATE) {
-            const uint64_t need = format == LFX_GZIP ? 8 : 4;
+            const uint64_t need = trailer_len(format);
             const uint64_t tpos = base + mr.end_byte;
             if (n - tpos < need) {
                 oc.status = LFX_E_UNEXPECTED_EOF;
@@ -1575,7 +1561,7 @@ extern "C" int lfx_decode_batch_size_device(lfx_ctx *cc, int format, uint32_t co
             used = std::min<uint64_t>((r.end_bit + 7) >> 3, n);
             if (huff_used[i] != ~0ull) used = huff_used[i];
             if (r.status == 0 && format != LFX_DEFLATE) {
-                const uint64_t need = format == LFX_GZIP ? 8 : 4;
+                const uint64_t need = trailer_len(format);
                 if (n - used < need) { r.status = 2; r.err = ERR_EOF; used = n; }
                 else used += need;
             }
@@ -1663,530 +1649,3 @@ extern "C" int lfx_decode_index_device(lfx_ctx *cc, int format, uint32_t flags, 
     c->phase("done");
     return LFX_OK;
 } LFX_ABI_CATCH
-
-// ------------------------------------------------------------------------------------------------
-// stream decoder: io::Read shaped ({deflate,zlib,gzip}::Decoder, gzip::MultiDecoder, src/non_blocking/*).
-//
-// Header first: the constructor pulls only what the container header needs (plus the rest of the chunk the reader
-// handed over) and reports header errors (gzip.rs:941-944, zlib.rs:312-320); the body is decoded by the first
-// read().  The GPU inflates whole members, so input is pulled in growing batches and a decode is ATTEMPTED whenever
-// a batch is complete, the reader ends, hands over a short read, or (non-blocking mode) would block; an attempt
-// that runs out of input (UnexpectedEof while the reader has not ended) simply waits for more.  Bytes pulled
-// beyond the member's trailer are never decoded: they stay in the decoder (lfx_decoder_surplus) for the caller to
-// hand to whatever reads next — what `into_inner()` amounts to for a reader that cannot be rewound
-// (gzip.rs:987,1216-1226) — and MultiDecoder continues with them.
-struct lfx_decoder {
-    Ctx *c;
-    int format;
-    uint32_t flags;
-    lfx_read_cb r;
-    void *user;
-    // (page-locked vectors, lfx_hostio.h: a window's H2D / D2H copies are DMA transfers straight out of / into them, and
-    //  resize() does not zero-fill what a copy overwrites)
-    PinVec in;                      // pulled from the reader and not yet consumed by a decoded window
-    bool reader_eof = false;
-    enum State { ST_HEADER, ST_BODY, ST_SERVE, ST_DONE, ST_FAILED } state = ST_HEADER;
-    bool first_member = true;
-    // current member
-    ContainerFields hf{};
-    std::vector<uint8_t> hdr_bytes;
-    bool have_header = false;
-    PinVec out;
-    uint64_t cursor = 0, serve_limit = 0;
-    int pending_status = LFX_OK;    // reported once the bytes in front of it have been served
-    uint64_t consumed_total = 0;    // reader bytes that belong to finished members
-    uint64_t target = 0;            // input size at which the next attempt is due
-    uint64_t tried_at = 0;          // input size of the last attempt that ran out of input
-    std::string err;
-    // windowed body decode: the member is decoded a window of complete blocks at a time
-    bool body_started = false;      // the header bytes have been dropped from `in`; in[0] holds the next block's first bit
-    uint32_t bit_off = 0;           // ... at this bit of in[0]
-    uint64_t member_out = 0;        // bytes of the member decoded by earlier windows
-    std::vector<uint8_t> hist;      // the last (at most 32 KiB) of them: the LZ77 window the next blocks may reach into
-    uint32_t run_crc = 0, run_adler = 1;   // container checksum over member_out bytes
-    bool member_final = false;      // the BFINAL block has been decoded: the trailer is next
-    bool more_windows = false;      // ST_SERVE: another window follows the bytes being served
-    uint64_t out_cap = 0;           // output capacity of one window
-    // ---- the next window decoded AHEAD (round 6): while the caller copies window k out of `out` (io::copy: 8192 bytes a
-    // read), a worker thread runs window k + 1 on the GPU into `next.out`.  The input was pulled by the CALLER's thread before
-    // the worker started (the read callback never runs on another thread); the worker touches `in` (read only), `hist` (read
-    // only), `next` and the context (under its lock) — nothing the serving path reads.
-    struct Window {
-        PinVec out;
-        MemberResult mr;
-        uint32_t crc = 0, adler = 1;
-        uint64_t n = 0;             // bytes of `in` the window was given
-        int rc = LFX_OK;            // a device-level failure of the attempt
-    } next;
-    std::thread worker;
-    bool ahead = false;             // `worker` is running (or has finished) window k + 1
-};
-
-namespace {
-
-enum { PULL_OK = 0, PULL_EOF = 1, PULL_BLOCK = 2, PULL_ERR = 3 };
-// one read() of up to `want` bytes from the inner reader
-int dec_pull(lfx_decoder *d, size_t want, size_t *got) {
-    *got = 0;
-    if (d->reader_eof) return PULL_EOF;
-    // (straight into the spare room behind `in` — page-locked, no zero fill, no second copy; the vector grows geometrically,
-    //  so a reader that hands over a few bytes at a time does not pay for `want` bytes each time)
-    const size_t old = d->in.size();
-    d->in.resize(old + want);
-    const int64_t k = d->r(d->user, d->in.data() + old, want);
-    d->in.resize(old + (k > 0 ? (size_t)std::min<int64_t>(k, (int64_t)want) : 0));
-    if (k == -(int64_t)LFX_E_WOULD_BLOCK) return PULL_BLOCK;
-    if (k < 0) return PULL_ERR;
-    if (k == 0) { d->reader_eof = true; return PULL_EOF; }
-    *got = (size_t)k;
-    return PULL_OK;
-}
-
-// parse the container header at the front of d->in, pulling what is missing.
-// → LFX_OK (have_header set), LFX_E_WOULD_BLOCK, LFX_E_IO, or the header's own failure (err set)
-int dec_header(lfx_decoder *d) {
-    if (d->format == LFX_DEFLATE) { d->have_header = true; d->hf = ContainerFields{}; d->hdr_bytes.clear(); return LFX_OK; }
-    for (;;) {
-        ContainerFields cf;
-        const DecHeader h = parse_container(d->format, d->in.data(), d->in.size(), &cf);
-        if (h.status == 0) {
-            d->hf = cf;                    // (a header that fails to parse leaves the previous member's in place)
-            d->hdr_bytes.assign(d->in.begin(), d->in.begin() + (size_t)h.deflate_off);
-            d->have_header = true;
-            return LFX_OK;
-        }
-        if (h.status == 2 && !d->reader_eof) {          // the header may simply not be complete yet
-            size_t got;
-            const int pr = dec_pull(d, 1 << 16, &got);
-            if (pr == PULL_BLOCK) return LFX_E_WOULD_BLOCK;
-            if (pr == PULL_ERR) { d->err = "read callback failed"; return LFX_E_IO; }
-            continue;
-        }
-        d->err = format_error(h.err, h.a0, h.a1);
-        d->consumed_total += h.deflate_off;
-        return map_status(h.status);
-    }
-}
-
-// The body is decoded a WINDOW at a time (the reference decodes one block per read, src/deflate/decode.rs:136-164, and keeps
-// 32 KiB of history, libflate_lz77/src/lib.rs:219-231): pull up to WINDOW_IN compressed bytes, decode the blocks that are
-// complete in them and fit WINDOW_OUT (inflate_member, partial), serve those bytes, drop the input they used, keep the
-// last 32 KiB of output as history — what is buffered never exceeds one window of input plus one window of output,
-// whatever the member's size, and the first byte is served as soon as the first window is decoded.  The container
-// checksum is folded window by window (CRC-32 / Adler-32 combine).  A window without one complete block (a block larger
-// than the window: schedule-S1 members) doubles the window.
-// WINDOW_IN_MAX bounds the doubling (a damaged stream whose block never reaches an EndOfBlock, on a reader that
-// never ends, must not pull the rest of the input into memory): at the limit the window is decoded WITHOUT `partial` — the
-// exact walk gives a verdict for a damaged stream; a valid block larger than the limit is refused.
-// Round 6: a window's kernels are bound by per-block latency, not by its size — 33 one-MiB blocks (16 MiB of text stream) take
-// 2.0 ms of kernels where the whole 256-block stream takes 2.6 (LFX_DEBUG window lines) — so after a first window of WINDOW_IN
-// bytes (first bytes early) the later ones take WINDOW_IN_LATER: half as many windows for 16 MiB more of page-locked memory.
-constexpr uint64_t WINDOW_IN = 16ull << 20, WINDOW_IN_LATER = 32ull << 20, WINDOW_OUT = 96ull << 20, WINDOW_IN_MAX = 4ull << 30;
-
-// → LFX_OK when bytes or a verdict are ready (state ST_SERVE), LFX_E_WOULD_BLOCK / LFX_E_IO from the reader, or a device error
-// ---- one window of the member's body in three steps: input (caller's thread) → GPU (caller's thread, or a worker thread
-//      that decodes AHEAD while the caller drains the window before) → state update (dec_body)
-// input up to the window size; a short read or the end of the reader also triggers an attempt.  → LFX_OK: attempt now
-int dec_fill(lfx_decoder *d) {
-    bool attempt = d->reader_eof;
-    while (!attempt) {
-        if (d->in.size() >= d->target) { attempt = true; break; }
-        size_t got;
-        const size_t want = std::min<uint64_t>(d->target - d->in.size(), 4u << 20);
-        const int pr = dec_pull(d, want, &got);
-        if (pr == PULL_ERR) { d->err = "read callback failed"; return LFX_E_IO; }
-        if (pr == PULL_EOF) { attempt = true; break; }
-        if (pr == PULL_BLOCK) {
-            // everything the peer has sent is here: decode it if enough new bytes arrived since an attempt that found
-            // no complete block (an eighth more: the retries of one long block stay linear in its size), else WouldBlock
-            if (d->in.size() > d->tried_at + d->tried_at / 8) { attempt = true; break; }
-            return LFX_E_WOULD_BLOCK;
-        }
-        // a short read hints that the reader has no more right now (pipes, sockets): worth an attempt once the
-        // input has grown by a quarter since the last one (keeps the total work linear)
-        if (got < want && d->in.size() >= d->tried_at + d->tried_at / 4 + 1) { attempt = true; break; }
-    }
-    return LFX_OK;
-}
-
-// one window on the GPU (the context's scratch is shared: one decode at a time per context): in[0, n) from bit bit_off with
-// the history → W.out, W.mr, the window's checksums.  Reads d->in, d->hist, d->bit_off, d->member_out, d->reader_eof,
-// d->out_cap (grows it when the tail of the member does not fit); writes only W and d->out_cap.
-void dec_gpu(lfx_decoder *d, lfx_decoder::Window &W) {
-    Ctx *c = d->c;
-    const uint64_t trailer = d->format == LFX_GZIP ? 8 : d->format == LFX_ZLIB ? 4 : 0;
-    const uint64_t n = d->in.size();
-    W.n = n;
-    W.crc = 0;
-    W.adler = 1;
-    W.rc = LFX_OK;
-    MemberResult &mr = W.mr;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    (void)hipSetDevice(c->device);
-    for (;;) {
-        mr = MemberResult();
-        c->n_ev = 0;
-        c->phase("start");
-        int rc;
-        const uint64_t H = d->hist.size();
-        if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) { W.rc = rc; return; }
-        if ((rc = c->d_io_out.reserve(MAX_WINDOW + d->out_cap))) { W.rc = rc; return; }
-        if ((rc = c->d_res.reserve(256))) { W.rc = rc; return; }
-        uint8_t *d_out = (uint8_t *)c->d_io_out.p + MAX_WINDOW;          // the history lies right in front of it
-        if (n && hipMemcpyAsync(c->d_io_in.p, d->in.data(), n, hipMemcpyHostToDevice, c->stream) != hipSuccess) { W.rc = LFX_E_DEVICE; return; }
-        if (H && hipMemcpyAsync(d_out - H, d->hist.data(), H, hipMemcpyHostToDevice, c->stream) != hipSuccess) { W.rc = LFX_E_DEVICE; return; }
-        // (once the reader has ended nothing more can arrive: the exact walk gives the member's verdict)
-        const bool at_limit = !d->reader_eof && n >= WINDOW_IN_MAX;
-        const bool partial = !d->reader_eof && !at_limit;
-        const auto tw0 = std::chrono::steady_clock::now();
-        rc = inflate_member(c, (const uint8_t *)c->d_io_in.p, n, 0, d_out, d->out_cap, mr, d->bit_off, ~0ull, partial, d->member_out);
-        if (rc) { W.rc = rc; return; }
-        const auto tw1 = std::chrono::steady_clock::now();
-        if (at_limit && mr.status == LFX_E_UNEXPECTED_EOF) {
-            mr.status = LFX_E_UNSUPPORTED;
-            mr.msg = "a DEFLATE block exceeds the stream decoder's window limit (4 GiB of compressed bytes)";
-        }
-        if (mr.status == LFX_E_NOSPACE && !partial) {     // (the tail of the member does not fit one window: grow and retry)
-            d->out_cap *= 2;
-            continue;
-        }
-        const uint64_t keep = mr.out_len;                 // bytes produced (also on failure)
-        if (keep && mr.status == LFX_OK && trailer) {
-            const uint64_t nspans = ck_nspans(keep);
-            if ((rc = c->d_ck.reserve(12 * nspans))) { W.rc = rc; return; }
-            uint32_t *ck = (uint32_t *)c->d_ck.p;
-            if (int e_ = launch_checksum(c->stream, d_out, keep, ck, ck + nspans, ck + 2 * nspans, (EncodeResult *)c->d_res.p,
-                                         d->format == LFX_GZIP ? 1 : 2)) {
-                c->set_error(hipGetErrorString((hipError_t)e_));
-                W.rc = LFX_E_DEVICE;
-                return;
-            }
-            if (hipMemcpyAsync(c->h_res, c->d_res.p, sizeof(EncodeResult), hipMemcpyDeviceToHost, c->stream) != hipSuccess) { W.rc = LFX_E_DEVICE; return; }
-        }
-        W.out.resize(keep);
-        if (keep && hipMemcpyAsync(W.out.data(), d_out, keep, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { W.rc = LFX_E_DEVICE; return; }
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { W.rc = LFX_E_DEVICE; return; }
-        if (keep && mr.status == LFX_OK && trailer) {
-            const EncodeResult er = *(EncodeResult *)c->h_res;
-            W.crc = er.crc32;
-            W.adler = er.adler32;
-        }
-        if (c->diag.debug) {
-            fprintf(stderr, "[lfx] window gpu: in=%llu out=%llu inflate_member %.3f ms, checksum + D2H %.3f ms", (unsigned long long)n,
-                    (unsigned long long)keep, std::chrono::duration<double, std::milli>(tw1 - tw0).count(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw1).count());
-            if (c->timing_on)          // (the kernels' own brackets of this window; the first one holds the H2D copy too)
-                for (int i = 0; i + 1 < c->n_ev; i++) {
-                    float ms = 0;
-                    (void)hipEventSynchronize(c->ev[i + 1]);
-                    if (hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]) == hipSuccess) fprintf(stderr, " %s=%.3f", c->ev_name[i + 1], ms);
-                }
-            fprintf(stderr, "\n");
-        }
-        return;
-    }
-}
-
-// ST_SERVE, first read of a window that is worth the thread (a few MiB to copy out) and has a successor: pull the successor's
-// input NOW, on the caller's thread, and let a worker decode it while the caller drains this window.  Not for non-blocking
-// readers (a WouldBlock in the middle of a drain has no call to come back from).
-void dec_start_ahead(lfx_decoder *d) {
-    if (d->ahead || !d->more_windows || d->member_final || d->pending_status != LFX_OK || (d->flags & LFX_DEC_NONBLOCKING) ||
-        !d->body_started || d->serve_limit < (4u << 20)) return;
-    if (dec_fill(d) != LFX_OK) return;                 // (an I/O error is found again, and reported, by the window's own turn)
-    if (d->in.empty()) return;
-    try {
-        d->worker = std::thread([d] {
-            try { dec_gpu(d, d->next); }
-            catch (const std::bad_alloc &) { d->next.rc = LFX_E_OOM; }
-            catch (...) { d->next.rc = LFX_E_DEVICE; }
-        });
-        d->ahead = true;
-    } catch (...) {
-        d->ahead = false;                              // (no thread to be had: the window is decoded when its turn comes)
-    }
-}
-// accessors and the destructor look at state the worker may be writing: let it finish first
-void dec_settle(lfx_decoder *d) {
-    if (d->ahead && d->worker.joinable()) d->worker.join();
-}
-
-int dec_body(lfx_decoder *d) {
-    Ctx *c = d->c;
-    if (!d->body_started) {
-        // the header has been parsed on the host (dec_header): drop its bytes, the first block starts at bit 0
-        const size_t hl = d->hdr_bytes.size();
-        d->in.erase(d->in.begin(), d->in.begin() + (std::ptrdiff_t)std::min(hl, d->in.size()));
-        d->consumed_total += hl;
-        d->body_started = true;
-        d->bit_off = 0; d->member_out = 0; d->hist.clear(); d->run_crc = 0; d->run_adler = 1; d->member_final = false;
-        d->target = 0; d->tried_at = 0;
-        d->out_cap = WINDOW_OUT;
-    }
-    // (small members: do not wait for a whole window.  1 MiB since round 6 — a reader that has less hands over a short read or
-    //  its end, either of which triggers an attempt; at 64 KiB a member of 1 MiB blocks made three attempts of 0.45 ms each
-    //  before its first block was complete)
-    if (d->target == 0) d->target = 1 << 20;
-    const uint64_t trailer = d->format == LFX_GZIP ? 8 : d->format == LFX_ZLIB ? 4 : 0;
-    for (;;) {
-        // ---- the member's blocks are done: the trailer (gzip.rs:1030-1042, zlib.rs:387-401)
-        if (d->member_final) {
-            const uint64_t tpos = d->bit_off ? 1 : 0;       // (the last block ends inside in[0]: the trailer is byte aligned)
-            while (d->in.size() < tpos + trailer && !d->reader_eof) {
-                size_t got;
-                const int pr = dec_pull(d, (size_t)(tpos + trailer - d->in.size()), &got);
-                if (pr == PULL_ERR) { d->err = "read callback failed"; return LFX_E_IO; }
-                if (pr == PULL_BLOCK) return LFX_E_WOULD_BLOCK;
-            }
-            d->out.clear(); d->cursor = 0; d->serve_limit = 0; d->more_windows = false;
-            d->pending_status = LFX_OK; d->err.clear();
-            if (d->in.size() < tpos + trailer) {
-                d->pending_status = LFX_E_UNEXPECTED_EOF;
-                d->err = "failed to fill whole buffer";
-                d->consumed_total += d->in.size();
-                d->in.clear();
-            } else {
-                const uint8_t *t = d->in.data() + tpos;
-                if (d->format == LFX_GZIP) {
-                    const uint32_t crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
-                    if (crc != d->run_crc) {   // gzip.rs:1035-1040 (ISIZE is read but never verified)
-                        d->pending_status = LFX_E_INVALID_DATA;
-                        d->err = format_error(ERR_CRC32, d->run_crc, crc);
-                    }
-                } else if (d->format == LFX_ZLIB) {
-                    const uint32_t ad = (uint32_t)t[0] << 24 | (uint32_t)t[1] << 16 | (uint32_t)t[2] << 8 | t[3];
-                    if (ad != d->run_adler) {
-                        d->pending_status = LFX_E_INVALID_DATA;
-                        d->err = format_error(ERR_ADLER32, d->run_adler, ad);
-                    }
-                }
-                d->consumed_total += tpos + trailer;
-                d->in.erase(d->in.begin(), d->in.begin() + (std::ptrdiff_t)(tpos + trailer));   // what is left is the surplus
-            }
-            d->body_started = false;
-            d->state = lfx_decoder::ST_SERVE;
-            return LFX_OK;
-        }
-        // ---- input (dec_fill) and one window on the GPU (dec_gpu) — or the window the worker thread decoded ahead while the
-        //      caller was copying the one before out (dec_start_ahead)
-        lfx_decoder::Window &W = d->next;
-        if (d->ahead) {
-            if (d->worker.joinable()) d->worker.join();      // (an accessor may have waited for it already)
-            d->ahead = false;
-        } else {
-            const int fr = dec_fill(d);
-            if (fr != LFX_OK) return fr;
-            dec_gpu(d, W);
-        }
-        if (W.rc) return W.rc;
-        const uint64_t n = W.n;
-        MemberResult &mr = W.mr;
-        const uint32_t w_crc = W.crc, w_adler = W.adler;
-        d->out.swap(W.out);                          // (the window's bytes; W.out keeps the old buffer's room for the next one)
-        bool verdict = false;
-        (void)verdict;
-        if (c->diag.debug)
-            fprintf(stderr, "[lfx] window: n=%llu bit_off=%u eof=%d hist=%llu → status=%d out=%llu blk_out=%llu end_bit=%llu final=%d need_cap=%d target=%llu\n",
-                    (unsigned long long)n, d->bit_off, (int)d->reader_eof, (unsigned long long)d->member_out, mr.status,
-                    (unsigned long long)mr.out_len, (unsigned long long)mr.blk_out_start, (unsigned long long)mr.end_bit,
-                    (int)mr.final_seen, (int)mr.need_cap, (unsigned long long)d->target);
-        if (mr.status == LFX_OK && mr.out_len == 0 && !mr.final_seen) {
-            // no complete block in this window: more input (or, for a block that does not fit, more room)
-            if (mr.need_cap) { d->out_cap *= 2; continue; }
-            if (d->reader_eof || n >= WINDOW_IN_MAX) {
-                // (cannot happen with !partial; kept as the way out of a reader that never ends on a broken stream)
-                d->pending_status = LFX_E_UNEXPECTED_EOF; d->err = "failed to fill whole buffer";
-                d->out.clear(); d->cursor = 0; d->serve_limit = 0; d->more_windows = false;
-                d->state = lfx_decoder::ST_SERVE;
-                return LFX_OK;
-            }
-            d->tried_at = n;
-            d->target = std::max<uint64_t>(d->target, std::max<uint64_t>(2 * n, 1 << 16));   // the next try: twice what did not suffice
-            continue;
-        }
-        // ---- bytes (and maybe a verdict) to serve
-        d->cursor = 0;
-        d->pending_status = LFX_OK;
-        d->err.clear();
-        if (mr.status != LFX_OK) {
-            // the reference hands out what completed blocks produced, then the error (decode.rs:136-164); everything
-            // produced stays available through unread_decoded_data (decode.rs:68-73)
-            d->serve_limit = mr.blk_out_start;
-            d->pending_status = mr.status;
-            d->err = mr.msg;
-            d->more_windows = false;
-            const uint64_t used = std::min<uint64_t>(mr.end_byte, n);
-            d->consumed_total += used;
-            d->in.erase(d->in.begin(), d->in.begin() + (std::ptrdiff_t)used);
-            d->body_started = false;
-            d->state = lfx_decoder::ST_SERVE;
-            (void)verdict;
-            return LFX_OK;
-        }
-        d->serve_limit = mr.out_len;
-        if (trailer && mr.out_len) {
-            d->run_crc = lfx_crc32_combine(d->run_crc, w_crc, mr.out_len);
-            d->run_adler = lfx_adler32_combine(d->run_adler, w_adler, mr.out_len);
-        }
-        d->member_out += mr.out_len;
-        // history: the last 32 KiB of (history ++ this window's output)
-        if (mr.out_len >= MAX_WINDOW) d->hist.assign(d->out.end() - MAX_WINDOW, d->out.end());
-        else {
-            d->hist.insert(d->hist.end(), d->out.begin(), d->out.end());
-            if (d->hist.size() > MAX_WINDOW) d->hist.erase(d->hist.begin(), d->hist.end() - MAX_WINDOW);
-        }
-        // input: everything in front of the byte that holds the next unread bit is done with
-        const uint64_t used = std::min<uint64_t>(mr.end_bit / 8, n);
-        d->consumed_total += used;
-        d->in.erase(d->in.begin(), d->in.begin() + (std::ptrdiff_t)used);
-        d->bit_off = (uint32_t)(mr.end_bit & 7);
-        d->member_final = mr.final_seen;
-        d->more_windows = true;                        // (the trailer check, at least, follows)
-        d->target = std::max<uint64_t>(d->member_out > mr.out_len ? WINDOW_IN_LATER : WINDOW_IN, d->target > (1 << 20) ? d->target : 0);
-        d->tried_at = 0;
-        d->state = lfx_decoder::ST_SERVE;
-        return LFX_OK;
-    }
-}
-
-}  // namespace
-
-extern "C" void lfx_decoder_free(lfx_decoder *d);
-extern "C" lfx_decoder *lfx_decoder_new(lfx_ctx *cc, int format, uint32_t flags, lfx_read_cb r, void *user, int *status) try {
-    if (!cc || !r || format < 0 || format > 2) { if (status) *status = cc ? LFX_E_ARG : LFX_E_DEVICE; return nullptr; }
-    lfx_decoder *d = new lfx_decoder();
-    d->c = reinterpret_cast<Ctx *>(cc);
-    d->out = d->c->take_pin();         // (page-locked buffers of an earlier decoder of this context, when there are any)
-    d->next.out = d->c->take_pin();
-    d->in = d->c->take_pin();
-    d->format = format;
-    d->flags = flags;
-    d->r = r;
-    d->user = user;
-    if (!(flags & LFX_DEC_NONBLOCKING)) {
-        // gzip / zlib constructors read the header and can fail (gzip.rs:941-944, zlib.rs:312-320); the non-blocking
-        // decoders read it lazily (src/non_blocking/gzip.rs:64-88)
-        const int rc = dec_header(d);
-        if (rc) {
-            if (status) *status = rc;
-            d->c->set_error(d->err);
-            lfx_decoder_free(d);
-            return nullptr;
-        }
-        d->state = lfx_decoder::ST_BODY;
-    }
-    if (status) *status = LFX_OK;
-    return d;
-} LFX_ABI_CATCH_NEW
-
-extern "C" int64_t lfx_decoder_read(lfx_decoder *d, uint8_t *out, size_t cap) try {
-    if (!d) return -(int64_t)LFX_E_ARG;
-    if (cap == 0) return 0;  // never latches end-of-stream (gzip.rs:1025-1027, zlib.rs:383-385)
-    for (;;) {
-        switch (d->state) {
-            case lfx_decoder::ST_DONE: return 0;
-            case lfx_decoder::ST_FAILED: return 0;   // (the error was reported once, like a latched io::Error)
-            case lfx_decoder::ST_SERVE: {
-                if (d->cursor < d->serve_limit) {
-                    if (d->cursor == 0) dec_start_ahead(d);       // (the next window on the GPU while this one is copied out)
-                    const uint64_t k = std::min<uint64_t>(cap, d->serve_limit - d->cursor);
-                    memcpy(out, d->out.data() + d->cursor, k);
-                    d->cursor += k;
-                    return (int64_t)k;
-                }
-                if (d->pending_status != LFX_OK) { d->state = lfx_decoder::ST_FAILED; return -(int64_t)d->pending_status; }
-                if (d->more_windows) { d->state = lfx_decoder::ST_BODY; continue; }      // the next window (or the trailer)
-                if (d->format == LFX_GZIP && (d->flags & LFX_DEC_MULTI)) {   // MultiDecoder::read gzip.rs:1142-1166
-                    d->first_member = false;
-                    d->state = lfx_decoder::ST_HEADER;
-                    continue;
-                }
-                d->state = lfx_decoder::ST_DONE;
-                return 0;
-            }
-            case lfx_decoder::ST_HEADER: {
-                const uint64_t before = d->consumed_total;
-                const int rc = dec_header(d);
-                if (rc == LFX_E_WOULD_BLOCK) return -(int64_t)LFX_E_WOULD_BLOCK;
-                if (rc == LFX_E_UNEXPECTED_EOF && !d->first_member) {
-                    // a following member's header that ends early = clean end of the stream (gzip.rs:1150-1156);
-                    // the partial header bytes were read
-                    d->consumed_total = before + d->in.size();
-                    d->in.clear();
-                    d->err.clear();
-                    d->state = lfx_decoder::ST_DONE;
-                    return 0;
-                }
-                if (rc) { d->state = lfx_decoder::ST_FAILED; return -(int64_t)rc; }
-                d->state = lfx_decoder::ST_BODY;
-                continue;
-            }
-            case lfx_decoder::ST_BODY: {
-                const int rc = dec_body(d);
-                if (rc == LFX_E_WOULD_BLOCK) return -(int64_t)LFX_E_WOULD_BLOCK;
-                if (rc) { d->err = d->err.empty() ? d->c->err : d->err; d->state = lfx_decoder::ST_FAILED; return -(int64_t)rc; }
-                continue;
-            }
-        }
-    }
-} LFX_ABI_CATCH_NEG
-extern "C" int lfx_decoder_unread(lfx_decoder *d, const uint8_t **p, size_t *n) try {
-    if (!d) return LFX_E_ARG;
-    // data decoded but not handed out: the rest of completed blocks + the partial block (decode.rs:68-73)
-    const uint64_t start = std::min<uint64_t>(d->cursor, d->out.size());
-    *p = d->out.data() + start;
-    *n = d->out.size() - start;
-    return LFX_OK;
-} LFX_ABI_CATCH
-extern "C" int lfx_decoder_surplus(lfx_decoder *d, const uint8_t **p, size_t *n) try {
-    if (!d) return LFX_E_ARG;
-    // input pulled from the reader that lies behind the last finished member (only meaningful between members /
-    // at the end: while a member is being collected `in` holds that member's bytes)
-    const bool settled = (d->state == lfx_decoder::ST_SERVE && !d->more_windows && !d->body_started) ||
-                         d->state == lfx_decoder::ST_DONE || d->state == lfx_decoder::ST_FAILED;
-    *p = d->in.data();
-    *n = settled ? d->in.size() : 0;
-    return LFX_OK;
-} LFX_ABI_CATCH
-extern "C" int lfx_decoder_header(lfx_decoder *d, lfx_header *h) try {
-    if (!d || !h) return LFX_E_ARG;
-    memset(h, 0, sizeof *h);
-    if (!d->have_header) {
-        if (!(d->flags & LFX_DEC_NONBLOCKING) || d->state != lfx_decoder::ST_HEADER) return LFX_E_ARG;
-        const int rc = dec_header(d);          // non-blocking decoders read the header on demand (non_blocking/gzip.rs:98-113)
-        if (rc) { if (rc != LFX_E_WOULD_BLOCK) d->state = lfx_decoder::ST_FAILED; return rc; }
-        d->state = lfx_decoder::ST_BODY;
-    }
-    const ContainerFields &f = d->hf;
-    const uint8_t *b = d->hdr_bytes.data();
-    h->format = d->format;
-    if (d->format == LFX_GZIP) {
-        h->mtime = f.mtime;
-        h->xfl = f.xfl;
-        h->os = f.os;
-        h->is_text = (f.flg & 1) != 0;
-        h->is_verified = (f.flg & 2) != 0;
-        if (f.flg & 4) { h->extra = b + f.extra_off; h->extra_len = (uint32_t)f.extra_len; h->has_extra = 1; }
-        if (f.name_len) h->filename = (const char *)(b + f.name_off);
-        if (f.comment_len) h->comment = (const char *)(b + f.comment_off);
-    } else if (d->format == LFX_ZLIB) {
-        h->zlib_window_size = 1u << (((uint32_t)f.cmf >> 4) + 8);   // Lz77WindowSize (zlib.rs:99-173)
-        h->zlib_level = (uint32_t)f.flg >> 6;                        // CompressionLevel (zlib.rs:28-58)
-    }
-    return LFX_OK;
-} LFX_ABI_CATCH
-extern "C" uint64_t lfx_decoder_consumed(const lfx_decoder *d) { return d ? d->consumed_total : 0; }
-extern "C" uint64_t lfx_decoder_buffered(const lfx_decoder *d) {
-    if (!d) return 0;
-    dec_settle(const_cast<lfx_decoder *>(d));      // (a window decoded ahead counts, and its buffer is not read while it grows)
-    return (uint64_t)(d->in.size() + d->out.size() + d->hist.size() + d->next.out.size());
-}
-extern "C" const char *lfx_decoder_last_error(const lfx_decoder *d) { return d ? d->err.c_str() : "null"; }
-extern "C" void lfx_decoder_free(lfx_decoder *d) {
-    if (!d) return;
-    dec_settle(d);
-    d->c->give_pin(std::move(d->in));
-    d->c->give_pin(std::move(d->out));
-    d->c->give_pin(std::move(d->next.out));
-    delete d;
-}

@@ -7,18 +7,14 @@
 #include <vector>
 
 #include "../../include/lfx.h"
+#include "lfx_container.h"
+#include "lfx_verdict.h"
 #include "lfx_ctx.h"
 #include "lfx_decode.h"
 #include "lfx_stages.h"
 #include "lfx_try.h"
 
 namespace lfx {
-
-// messages: prefixes match the reference texts quoted in SURVEY.md §4
-std::string format_error(uint32_t err, uint32_t a0, uint32_t a1);
-inline int map_status(uint32_t st) {
-    return st == 0 ? LFX_OK : st == 1 ? LFX_E_INVALID_DATA : st == 2 ? LFX_E_UNEXPECTED_EOF : LFX_E_NOSPACE;
-}
 
 struct MemberResult {
     int status = LFX_OK;

@@ -105,8 +105,6 @@ int launch_pack(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Chun
 // sixteen 64 KiB spans — sixteen wavefronts on the whole GPU, each walking sixteen dependent pieces: 0.12 ms; 16 MiB are 256)
 inline uint32_t ck_span(uint64_t n) { return n <= (64ull << 20) ? 8192u : 65536u; }
 inline uint64_t ck_nspans(uint64_t n) { return div_up(n ? n : 1, ck_span(n)); }   // partials needed: 3 x 4 bytes each
-// the checksum a container's trailer holds, as launch_checksum's mode (raw DEFLATE: none)
-inline int ck_mode_of(int format) { return format == LFX_GZIP ? 1 : format == LFX_ZLIB ? 2 : 0; }
 int launch_checksum(hipStream_t st, const uint8_t *in, uint64_t n, uint32_t *crc_part,
                     uint32_t *a_part, uint32_t *b_part, EncodeResult *res,
                     int mode = 3)   /* bit 0: CRC-32, bit 1: Adler-32 (the other result is then 0) */;

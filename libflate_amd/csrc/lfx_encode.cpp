@@ -376,7 +376,7 @@ int encode_emit(Ctx *c, int format, bool with_trailer, uint32_t trailer_check, b
     (void)hipSetDevice(c->device);
     hipStream_t st = c->stream;
     if (((uintptr_t)d_out & 3) != 0) { c->set_error("output buffer must be 4-byte aligned"); return LFX_E_ARG; }
-    const uint64_t trailer = with_trailer ? (format == LFX_GZIP ? 8 : format == LFX_ZLIB ? 4 : 0) : 0;
+    const uint64_t trailer = with_trailer ? trailer_len(format) : 0;
     if (cap < prefix_len + trailer + 8) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
     const uint64_t cap_words = cap / 4;  // whole dwords only (kernels write dwords)
     const uint64_t cap_bits = (cap_words * 4 - trailer) * 8;
@@ -414,7 +414,7 @@ int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &
     (void)hipSetDevice(c->device);
     hipStream_t st = c->stream;
     const uint32_t count = (uint32_t)b.streams.size();
-    const uint32_t trailer = b.format == LFX_GZIP ? 8 : b.format == LFX_ZLIB ? 4 : 0;
+    const uint32_t trailer = trailer_len(b.format);
     // per-stream scratch: descriptors, checksums, end bits, status, lengths (+ the header bytes)
     const size_t sz_streams = sizeof(BatchStream) * count;
     DevBuf &sb = c->d_dec_streams;     // (decode scratch: free during an encode)

@@ -7,6 +7,7 @@
 #include "lfx_device.h"
 #include "lfx_plan.h"
 #include "lfx_try.h"
+#include "lfx_verdict.h"
 
 namespace lfx {
 

@@ -12,37 +12,6 @@
 
 namespace lfx {
 
-std::string format_error(uint32_t err, uint32_t a0, uint32_t a1) {
-    char m[200];
-    switch (err) {
-        case ERR_EOF: return "failed to fill whole buffer";
-        case ERR_HUFF: return "Invalid huffman coded stream";
-        case ERR_CONFLICT: snprintf(m, sizeof m, "Bit region conflict: symbol=%u", a0); return m;
-        case ERR_HDIST: snprintf(m, sizeof m, "The value of HDIST is too big: max=30, actual=%u", a0); return m;
-        case ERR_NO_PREV: return "No preceding value";
-        case ERR_DIST_LIST:
-            snprintf(m, sizeof m, "The length of `distance_code_bitwidthes` is too large: actual=%u, expected=%u", a0, a1);
-            return m;
-        case ERR_286: snprintf(m, sizeof m, "The value %u must not occur in compressed data", a0); return m;
-        case ERR_BACKREF: snprintf(m, sizeof m, "Too long backword reference: buffer.len=%u, distance=%u", a0, a1); return m;
-        case ERR_BTYPE3: return "btype 0x11 of DEFLATE is reserved(error) value";
-        case ERR_LEN_NLEN: snprintf(m, sizeof m, "LEN=%u is not the one's complement of NLEN=%u", a0, a1); return m;
-        case ERR_STORED_SHORT: snprintf(m, sizeof m, "The reader has incorrect length: expected %u, read %u", a0, a1); return m;
-        case ERR_NOSPACE: return "output capacity too small";
-        case ERR_ZLIB_CHECK:
-            snprintf(m, sizeof m, "Inconsistent ZLIB check bits: `CMF(%u) * 256 + FLG(%u)` must be a multiple of 31", a0, a1);
-            return m;
-        case ERR_METHOD: snprintf(m, sizeof m, "Compression methods other than DEFLATE(8) are unsupported: method=%u", a0); return m;
-        case ERR_CINFO: snprintf(m, sizeof m, "CINFO above 7 are not allowed: value=%u", a0); return m;
-        case ERR_FDICT: snprintf(m, sizeof m, "Preset dictionaries are not supported: dictionary_id=0x%X", a0); return m;
-        case ERR_GZIP_ID: return "Unexpected GZIP ID";
-        case ERR_HCRC: snprintf(m, sizeof m, "CRC16 of GZIP header mismatched: value=%u, expected=%u", a0, a1); return m;
-        case ERR_CRC32: snprintf(m, sizeof m, "CRC32 mismatched: value=%u, expected=%u", a0, a1); return m;
-        case ERR_ADLER32: snprintf(m, sizeof m, "Adler32 checksum mismatched: value=%u, expected=%u", a0, a1); return m;
-        default: return "";
-    }
-}
-
 int run_jobs(Ctx *c, const uint8_t *d_in, uint8_t *d_out, const std::vector<InflateJob> &jobs,
              std::vector<InflateResult> &res) {
     const size_t n = jobs.size();

@@ -580,3 +580,24 @@ def test_encode_stage_arithmetic_segments_links_workgroups_and_append(tmp_path):
     subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "c", "encode_geom.cpp")], check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "encode_geom ok: 4000 plans, 10 synthetic lists" in out.stdout, out.stdout[-400:]
+
+
+def test_stream_decoder_state_machine_over_a_stand_in_backend(tmp_path):
+    """The stream decoder's state machine (libflate_amd/csrc/lfx_stream_dec.h: no HIP, no context, a plain host compiler builds
+    it) with kilobyte-sized windows over a stand-in window backend that answers from the oracle's block list.
+    tests/c/stream_dec.cpp: all three formats, members of 0, 1 and many bytes, readers that hand over everything, 1 byte, 7
+    bytes, random short reads and WouldBlock, reads of 1, 8192 and more bytes — the plain text, `consumed`, reads of capacity 0,
+    reads after the end, the bound on what is buffered; the surplus; MultiDecoder's clean end on a cut header and the failures
+    of a cut FIRST header; truncation in the body and in the trailer; bad CRC-32 / Adler-32 with format_error's text; a
+    damaged block in a later window; the doubling of the window and of the output room, the input limit; the window decoded
+    ahead by a worker thread, and a decoder freed while it is in flight."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "stream_dec")
+    subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-pthread", "-o", exe, os.path.join(root, "tests", "c", "stream_dec.cpp"),
+                    os.path.join(root, "oracle", "lfo_core.c"), os.path.join(root, "oracle", "lfo_deflate.c")], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "stream_dec ok:" in out.stdout, out.stdout[-400:] + out.stderr[-400:]
