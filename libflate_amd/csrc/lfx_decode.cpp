@@ -1321,13 +1321,15 @@ bool walk_settled(const WalkResult &r, uint64_t out_before) {
     return r.status != WALK_STUCK && (r.reach == INT64_MAX || (int64_t)out_before + r.reach >= 0);
 }
 
+}  // namespace
+
+namespace lfx {
 // `consumed` behind an "Invalid huffman coded stream" verdict.  The reference's decoder skips 16 bits it never read when a
 // code is unassigned (huffman.rs:157-179), and inflate_kernel's end_bit counts them as the decode's `consumed` does; what
 // the reference's reader has pulled from its input at that point is the shortest prefix of the stream that still gives the
 // same verdict.  That prefix is found with the exact kernel itself: the failing block again, count-only, on the two or three
 // candidate lengths in ONE launch (only on this rare verdict).  probes[i]: stream base, stream length, the exact path's
 // result → used[i] = bytes of the stream consumed.
-struct HuffProbe { uint64_t in_off, in_len; InflateResult r; };
 int huff_consumed(Ctx *c, const uint8_t *d_in, const std::vector<HuffProbe> &probes, std::vector<uint64_t> &used) {
     used.assign(probes.size(), 0);
     std::vector<InflateJob> jobs;
@@ -1355,7 +1357,9 @@ int huff_consumed(Ctx *c, const uint8_t *d_in, const std::vector<HuffProbe> &pro
     }
     return LFX_OK;
 }
-inline bool huff_verdict(const InflateResult &r) { return r.status == 1 && r.err == ERR_HUFF; }
+}  // namespace lfx
+
+namespace {
 
 // inflate_member for sizes: mr.status / out_len / end_byte / msg of the DEFLATE stream at byte off0 of d_in[0, n)
 int size_member(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t off0, MemberResult &mr) {

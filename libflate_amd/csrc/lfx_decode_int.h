@@ -48,6 +48,12 @@ struct DecodeOutcome {
 // run `njobs` inflate jobs (the exact serial kernel) and fetch their results
 int run_jobs(Ctx *c, const uint8_t *d_in, uint8_t *d_out, const std::vector<InflateJob> &jobs, std::vector<InflateResult> &res);
 
+// `consumed` behind an "Invalid huffman coded stream" verdict of the exact kernel (lfx_decode.cpp): the decode, the size call and
+// the batch decode all report what the reference's reader has pulled from its input at that point
+struct HuffProbe { uint64_t in_off, in_len; InflateResult r; };
+inline bool huff_verdict(const InflateResult &r) { return r.status == 1 && r.err == ERR_HUFF; }
+int huff_consumed(Ctx *c, const uint8_t *d_in, const std::vector<HuffProbe> &probes, std::vector<uint64_t> &used);
+
 // Decode the DEFLATE stream that starts at byte `off0` of d_in[0..n) into d_out[0..cap).
 // hist0 = 0 (a member starts with an empty Lz77Decoder buffer, gzip.rs:1000-1005).
 // stop_bit != ~0: the walk ends cleanly when a block ends exactly at stop_bit (a shard of a member that

@@ -710,6 +710,14 @@ int serial_walk(const Member &m, MemberResult &mr) {
     if ((rc = run_jobs(c, m.d_in, m.d_out, {j}, res))) return rc;
     c->phase("serial");
     InflateResult &r = res[0];
+    // an unassigned code in a whole member: `consumed` is what the reference's reader has pulled by then, as in the size call
+    // (end_bit counts the 16 bits the reference skips without reading them)
+    uint64_t huff_used = ~0ull;
+    if (huff_verdict(r) && m.stop_bit == ~0ull && !m.partial && m.hist == 0) {
+        std::vector<uint64_t> used;
+        if ((rc = huff_consumed(c, m.d_in, {HuffProbe{0, n, r}}, used))) return rc;
+        huff_used = used[0];
+    }
     if (m.stop_bit != ~0ull && r.status == 0 && (r.final_seen || r.end_bit != m.stop_bit)) {
         // a shard without the BFINAL block must end exactly where the next shard starts
         r.status = 1; r.err = ERR_HUFF; r.a0 = r.a1 = 0;
@@ -717,7 +725,7 @@ int serial_walk(const Member &m, MemberResult &mr) {
     mr.status = map_status(r.status);
     mr.out_len = r.out_len;
     mr.blk_out_start = r.status ? r.blk_out_start : r.out_len;
-    mr.end_byte = std::min<uint64_t>((r.end_bit + 7) / 8, n);
+    mr.end_byte = huff_used != ~0ull ? huff_used : std::min<uint64_t>((r.end_bit + 7) / 8, n);
     mr.end_bit = r.end_bit;
     mr.final_seen = r.status == 0 && r.final_seen;
     mr.msg = format_error(r.err, r.a0, r.a1);
