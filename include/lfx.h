@@ -608,6 +608,55 @@ int lfx_decoder_header(lfx_decoder *d, lfx_header *h);
 const char *lfx_decoder_last_error(const lfx_decoder *d);
 void lfx_decoder_free(lfx_decoder *d);
 
+/* ---- preset dictionaries: zlib streams with FDICT, raw DEFLATE that starts with history ------------------
+ * What zlib's inflateSetDictionary / Python's zlib.decompressobj(zdict=...) read.  The reference refuses FDICT, and the
+ * dictionary-less calls above keep doing so; these calls are ours.  Decoding only.
+ *
+ *  1. Dictionary.  The usable history is the LAST min(len, 32768) bytes; lfx_dict_id is the Adler-32 of ALL len bytes (RFC
+ *     1950's DICTID).  len == 0 is allowed (id 1, no history).  lfx_dict_new copies what it needs to the device once and
+ *     computes the id there; later calls do no per-call dictionary work.  bytes[0, len): host memory, or device memory when
+ *     on_device != 0.  A dictionary belongs to its context: use it with that context's calls and decoders only (another
+ *     context's: LFX_E_ARG), free it before the context.  A NULL context gives NULL with *status = LFX_E_DEVICE.
+ *  2. Formats: LFX_ZLIB and LFX_DEFLATE.  LFX_GZIP is LFX_E_ARG (gzip has no preset dictionary), whatever `dict` is.  There
+ *     is no `flags` argument.
+ *  3. dict == NULL: every call behaves exactly as its dictionary-less twin (lfx_decode_device, lfx_decode_host,
+ *     lfx_decode_batch_device with flags 0) — today's FDICT rejection and its message included.
+ *  4. zlib, FDICT set: the header is six bytes; CMF / FLG are checked as ever, DICTID is big-endian.  DICTID != lfx_dict_id(dict)
+ *     is LFX_E_INVALID_DATA with *out_len = 0, *consumed what the FDICT rejection reports for the same bytes, and the message
+ *     "Dictionary mismatch: dictionary_id=0x%X, supplied=0x%X".  Fewer than six bytes: LFX_E_UNEXPECTED_EOF.  On a match the
+ *     body is decoded with the dictionary as history; the Adler-32 trailer covers the output only, never the dictionary.
+ *  5. zlib, FDICT clear: the dictionary is not used (as in zlib's inflate): status, lengths, message and bytes are
+ *     lfx_decode_device's.
+ *  6. Raw DEFLATE: the dictionary is always the history in front of byte 0.  A distance may reach min(len, 32768) + bytes
+ *     produced so far; a longer one is "Too long backword reference: buffer.len=%d, distance=%d" with buffer.len =
+ *     min(len, 32768) + bytes produced.
+ *  7. Everything else — error kinds, partial output on damaged input, LFX_E_NOSPACE, trailing bytes, per-stream status in the
+ *     batch with no effect on neighbours — is what the dictionary-less call does.  Nothing outside d_out[out_off, out_off +
+ *     out_cap) is written for a stream, and for a stream that decodes, is cut short or does not fit, exactly d_out[out_off,
+ *     out_off + out_len).  As in lfx_decode_batch_device, a DAMAGED stream of a batch may leave bytes of a discarded
+ *     block-parallel attempt behind out_len, inside its own out_cap; status, out_len and d_out[out_off, out_off + out_len)
+ *     are the exact decode's.
+ *  8. Stream decoder: lfx_decoder_set_dict makes a zlib / deflate lfx_decoder follow rules 4-6, non-blocking mode included;
+ *     on a gzip decoder it is LFX_E_ARG.  It must come before the container header is read: before the first header() /
+ *     read() of a non-blocking decoder or of one made with LFX_DEC_LAZY_HEADER (a blocking decoder that, like a non-blocking
+ *     one, leaves the header to the first header() / read() instead of reading it in lfx_decoder_new), any time before the
+ *     first read() of a raw DEFLATE decoder; later, or a second time: LFX_E_ARG.  The dictionary must outlive the decoder. */
+typedef struct lfx_dict lfx_dict;
+lfx_dict *lfx_dict_new(lfx_ctx *c, const void *bytes, uint64_t len, int on_device, int *status);
+uint32_t lfx_dict_id(const lfx_dict *d);
+void lfx_dict_free(lfx_dict *d);
+int lfx_decode_dict_device(lfx_ctx *c, int format, const lfx_dict *dict, const void *d_in, uint64_t n,
+                           void *d_out, uint64_t cap, uint64_t *out_len, uint64_t *consumed);
+/* same, host buffers (staged like lfx_decode_host) */
+int lfx_decode_dict_host(lfx_ctx *c, int format, const lfx_dict *dict, const void *in, uint64_t n,
+                         void *out, uint64_t cap, uint64_t *out_len, uint64_t *consumed);
+/* lfx_decode_batch_device with one dictionary for every stream of the batch (it is never copied in front of an output) */
+int lfx_decode_batch_dict_device(lfx_ctx *c, int format, const lfx_dict *dict, uint32_t count, const void *d_in,
+                                 const uint64_t *in_off, const uint64_t *in_len, void *d_out, const uint64_t *out_off,
+                                 const uint64_t *out_cap, uint64_t *out_len, int32_t *status);
+#define LFX_DEC_LAZY_HEADER 4u
+int lfx_decoder_set_dict(lfx_decoder *d, const lfx_dict *dict);
+
 /* ---- plug-in: libflate_lz77::Lz77Encode (libflate_lz77/src/lib.rs:83-107) -----------------
  * Codes are delivered in batches: word = (val << 16) | dist; dist == 0 → Code::Literal(val),
  * else Code::Pointer{length: val, backward_distance: dist} (lib.rs:27-42). */

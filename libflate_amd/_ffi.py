@@ -17,6 +17,7 @@ SCHED_SINGLE, SCHED_FIXED, SCHED_LIST = 0, 1, 2
 SCHED_FLUSH = (1 << 64) - 1
 DEC_MULTI = 1
 DEC_NONBLOCKING = 2
+DEC_LAZY_HEADER = 4     # a blocking decoder that leaves the container header to the first header() / read() (set_dict first)
 MEMBERS_BGZF = 1
 BGZF_MEMBER_SIZE = 65280      # bgzip's own slice; 65505 is the most a BGZF member holds
 VOFF_NONE = 2**64 - 1         # lfx_bgzf_read.end_voff: no such bound
@@ -40,6 +41,8 @@ EXPORTS = [
     "lfx_encode_members_bound", "lfx_encode_members_device", "lfx_encode_members_host", "lfx_members_gzi",
     "lfx_decode_size_device", "lfx_decode_size_host", "lfx_decode_batch_size_device", "lfx_decode_members_size_device",
     "lfx_decode_members_size_host", "lfx_bgzf_read_device", "lfx_bgzf_read_host", "lfx_members_voffset",
+    "lfx_dict_new", "lfx_dict_id", "lfx_dict_free", "lfx_decode_dict_device", "lfx_decode_dict_host",
+    "lfx_decode_batch_dict_device", "lfx_decoder_set_dict",
 ]
 
 
@@ -191,6 +194,16 @@ def lib():
     L.lfx_decode_device.argtypes = [vp, i32, u32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.lfx_decode_host.argtypes = [vp, i32, u32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.lfx_decode_batch_device.argtypes = [vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lfx_dict_new.restype = vp
+    L.lfx_dict_new.argtypes = [vp, vp, u64, i32, C.POINTER(i32)]
+    L.lfx_dict_id.restype = u32
+    L.lfx_dict_id.argtypes = [vp]
+    L.lfx_dict_free.argtypes = [vp]
+    L.lfx_dict_free.restype = None
+    L.lfx_decode_dict_device.argtypes = [vp, i32, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.lfx_decode_dict_host.argtypes = [vp, i32, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.lfx_decode_batch_dict_device.argtypes = [vp, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lfx_decoder_set_dict.argtypes = [vp, vp]
     L.lfx_decode_members_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,
                                             C.POINTER(u32)]
     L.lfx_decode_members_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,

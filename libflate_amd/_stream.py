@@ -131,8 +131,9 @@ class _DecoderBase:
     FORMAT = _ffi.DEFLATE
     FLAGS = 0
 
-    def __init__(self, inner, context=None):
-        """`inner`: bytes-like or an object with read(n) — the reference's `R`."""
+    def __init__(self, inner, context=None, zdict=None):
+        """`inner`: bytes-like or an object with read(n) — the reference's `R`.  zdict (zlib / deflate): a preset dictionary,
+        bytes or a libflate_amd.Dictionary (lfx_decoder_set_dict)."""
         self._ctx = context or default_context()
         if isinstance(inner, (bytes, bytearray, memoryview)):
             import io
@@ -140,11 +141,28 @@ class _DecoderBase:
         self._inner = inner
         self._rcb = _ffi.READ_CB(self._on_read)
         st = C.c_int(0)
-        self._h = _ffi.lib().lfx_decoder_new(self._ctx.handle, self.FORMAT, self.FLAGS, self._rcb, None,
+        # (with a dictionary the header is left to the first header() / read(): set_dict has to come before it)
+        flags = self.FLAGS | (_ffi.DEC_LAZY_HEADER if zdict is not None else 0)
+        self._h = _ffi.lib().lfx_decoder_new(self._ctx.handle, self.FORMAT, flags, self._rcb, None,
                                              C.byref(st))
         if not self._h:
             raise StreamError(st.value, self._ctx.last_error())
         self._ctx._retain()
+        self._zdict = None
+        if zdict is not None:
+            self.set_dict(zdict)
+            if not (self.FLAGS & _ffi.DEC_NONBLOCKING):
+                self.header()            # (a blocking constructor reads the header and reports its failure)
+
+    def set_dict(self, zdict):
+        """lfx_decoder_set_dict: before the header is read; the decoder keeps the Dictionary alive"""
+        if not hasattr(zdict, "handle"):
+            from .context import Dictionary
+            zdict = Dictionary(zdict, self._ctx)
+        rc = _ffi.lib().lfx_decoder_set_dict(self._h, zdict.handle)
+        if rc:
+            raise StreamError(rc, "lfx_decoder_set_dict: too late, a second dictionary, or a gzip decoder")
+        self._zdict = zdict
 
     def _on_read(self, _user, p, cap):
         try:
@@ -227,3 +245,4 @@ class _DecoderBase:
             _ffi.lib().lfx_decoder_free(self._h)
             self._h = None
             self._ctx._release()
+            self._zdict = None       # (only now: the decoder read the dictionary's bytes)

@@ -328,6 +328,91 @@ class Context:
                 continue
             return rc, out.raw[:out_len.value], consumed.value, self.last_error() if rc else ""
 
+    # ---- preset dictionaries (lfx_decode_dict_*) ------------------------------------------
+    @staticmethod
+    def _dict_handle(zdict):
+        return zdict.handle if zdict is not None else None
+
+    def decode_dict_device(self, fmt, zdict, d_in, n, d_out, cap):
+        """lfx_decode_dict_device: zlib / raw DEFLATE with a Dictionary (None: exactly decode_device)
+        → (status, out_len, consumed, message)"""
+        out_len, consumed = C.c_uint64(0), C.c_uint64(0)
+        rc = _ffi.lib().lfx_decode_dict_device(self._h, fmt, self._dict_handle(zdict), d_in, n, d_out, cap, C.byref(out_len),
+                                               C.byref(consumed))
+        if rc in (_ffi.E_DEVICE, _ffi.E_OOM, _ffi.E_ARG):
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return rc, out_len.value, consumed.value, self.last_error() if rc else ""
+
+    def decode_dict_host(self, fmt, zdict, data, cap=None):
+        """lfx_decode_dict_host → (status, output_so_far, consumed, message); a cap left to None grows while the output does
+        not fit, as in decode_host"""
+        data = bytes(data)
+        grow = cap is None
+        cap = cap if cap is not None else max(1 << 16, len(data) * 16)
+        while True:
+            out = C.create_string_buffer(cap)
+            out_len, consumed = C.c_uint64(0), C.c_uint64(0)
+            rc = _ffi.lib().lfx_decode_dict_host(self._h, fmt, self._dict_handle(zdict), data, len(data), out, cap,
+                                                 C.byref(out_len), C.byref(consumed))
+            if rc in (_ffi.E_DEVICE, _ffi.E_OOM, _ffi.E_ARG):
+                raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+            if grow and rc == _ffi.E_NOSPACE and cap < len(data) * 1040 + (1 << 20):
+                cap *= 8
+                continue
+            return rc, out.raw[:out_len.value], consumed.value, self.last_error() if rc else ""
+
+    def decode_batch_dict_device(self, fmt, zdict, d_in, in_offs, in_lens, d_out, out_offs, out_caps):
+        """lfx_decode_batch_dict_device: the streams d_in[in_offs[i], +in_lens[i]) into d_out[out_offs[i], +out_caps[i]), one
+        Dictionary for all of them; the offsets and lengths are host-side lists → [(status, out_len)] per stream"""
+        k = len(in_offs)
+        a = lambda v: (C.c_uint64 * max(k, 1))(*v)
+        io, il, oo, oc = a(in_offs), a(in_lens), a(out_offs), a(out_caps)
+        out_len, st = (C.c_uint64 * max(k, 1))(), (C.c_int32 * max(k, 1))()
+        rc = _ffi.lib().lfx_decode_batch_dict_device(self._h, fmt, self._dict_handle(zdict), k, d_in, io, il, d_out, oo, oc, out_len, st)
+        if rc:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return [(st[i], out_len[i]) for i in range(k)]
+
+
+class Dictionary:
+    """A preset dictionary (lfx_dict): what zlib.compressobj(zdict=...) was given.  The last 32 KiB are the
+    usable history; `id` is the Adler-32 of all bytes (RFC 1950's DICTID).  `data`: bytes-like, or a contiguous CUDA uint8
+    tensor.  Belongs to its Context and counts itself in and out of it like the other native handles."""
+
+    def __init__(self, data, context=None):
+        self._h = None
+        self._ctx = context if context is not None else default_context()
+        st = C.c_int(0)
+        if hasattr(data, "data_ptr"):
+            if not data.is_cuda or data.dtype.itemsize != 1 or not data.is_contiguous():
+                raise TypeError("Dictionary: a tensor must be a contiguous CUDA uint8 tensor")
+            import torch
+            torch.cuda.current_stream(data.device).synchronize()
+            self._h = _ffi.lib().lfx_dict_new(self._ctx.handle, data.data_ptr(), data.numel(), 1, C.byref(st))
+        else:
+            data = bytes(data)
+            self._h = _ffi.lib().lfx_dict_new(self._ctx.handle, data, len(data), 0, C.byref(st))
+        if not self._h:
+            raise (_ffi.DeviceError if st.value == _ffi.E_DEVICE else _ffi.LfxError)(st.value, self._ctx.last_error())
+        self._ctx._retain()
+        self.id = int(_ffi.lib().lfx_dict_id(self._h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _ffi.lib().lfx_dict_free(self._h)
+            self._h = None
+            self._ctx._release()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 _default = {}
 

@@ -24,6 +24,7 @@ enum : uint32_t {
     ERR_ZLIB_CHECK, ERR_METHOD, ERR_CINFO, ERR_FDICT,   // zlib.rs:229-259
     ERR_GZIP_ID, ERR_HCRC,                              // gzip.rs:398-441
     ERR_CRC32, ERR_ADLER32,                             // gzip.rs:1035-1040, zlib.rs:396-401
+    ERR_DICT_MISMATCH, // "Dictionary mismatch: dictionary_id=, supplied=" (ours: the dictionary calls)
 };
 
 // what the container header parse (lfx_container.h: one source for the device kernel and the host stream decoder) reports
@@ -31,9 +32,10 @@ struct DecHeader {
     uint64_t deflate_off;  // first DEFLATE byte relative to the stream start
     uint32_t status;       // 0 ok, 1 InvalidData, 2 UnexpectedEof
     uint32_t err, a0, a1;
-    uint32_t flags;
+    uint32_t flags;        // gzip: FLG; zlib: HDR_DICT when FDICT was set and the caller's dictionary matched its DICTID
     uint32_t _pad;
 };
+constexpr uint32_t HDR_DICT = 0x100;
 
 // ---- lane-parallel single-stream path (lfx_inflate_fast.hip)
 enum : uint32_t { BLK_OK = 0, BLK_BAD = 1, BLK_NO_EOB = 2 };
@@ -90,7 +92,8 @@ struct BlkEmit {
     uint32_t preload;    // materialise: those bytes are already final in `out` — load up to 32 KiB of them as history
     uint32_t placed;     // round 6: 1 = the scan stored this block's codes (blk_place_kernel moves them; blk_emit_kernel skips the block)
     uint64_t temp_off;   // ... at temp + temp_off + lane * cap
-    uint32_t cap, _pad;
+    uint32_t cap;
+    uint32_t dict_len;   // the dictionary instances only: of `hist`, so many bytes are the preset dictionary's tail (not in `out`)
 };
 constexpr uint32_t MAX_FREE_UNITS = 64;  // marker units per block (a schedule-S1 stream is ONE block)
 struct BlkUnits {

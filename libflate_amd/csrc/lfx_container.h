@@ -120,4 +120,15 @@ LFX_HD inline DecHeader parse_container(int format, const uint8_t *p, uint64_t n
     return h;
 }
 
+// The dictionary calls: a zlib header that parse_container refuses for its FDICT bit, judged against the caller's
+// dictionary.  DICTID == dict_id: the header is fine (six bytes, flags = HDR_DICT: the body is decoded with the dictionary as
+// history); otherwise "Dictionary mismatch", consumed as the FDICT rejection.  Every other verdict passes through.
+LFX_HD inline DecHeader resolve_fdict(DecHeader h, uint32_t dict_id) {
+    if (h.status == 1 && h.err == ERR_FDICT) {
+        if (h.a0 == dict_id) { h.status = 0; h.err = 0; h.a0 = 0; h.flags = HDR_DICT; }
+        else { h.err = ERR_DICT_MISMATCH; h.a1 = dict_id; }
+    }
+    return h;
+}
+
 }  // namespace lfx

@@ -18,6 +18,7 @@
 #include "lfx_container.h"
 #include "lfx_index.h"
 #include "lfx_bgzf.h"
+#include "lfx_dict.h"
 
 static_assert(offsetof(lfx::DecStream, out_off) == 16 && sizeof(lfx::DecStream) % 8 == 0, "checksum_ranges stride");
 static_assert(offsetof(lfx::InflateResult, out_len) == 8 && sizeof(lfx::InflateResult) % 8 == 0, "checksum_ranges stride");
@@ -60,8 +61,11 @@ int verify_trailer(Ctx *c, int format, const uint8_t *d_in, uint64_t tpos, uint6
 // into d_out[0, out_at) and verified by the caller; base == 0 is the first member).  one_member: return behind the first
 // member whose trailer was verified (oc.more), without looking at what follows.  members: the verified members are appended.
 // sizes_only: the loop of the size calls — no output and no checksum comparison (a trailer must be THERE); d_out is not used.
+// dict (the dictionary calls, zlib / raw DEFLATE, not with sizes_only): a zlib header's FDICT is judged against it, and a
+// member that uses it is decoded with its tail as detached history.
 int member_loop(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, bool sizes_only,
-                DecodeOutcome &oc, uint64_t base, uint64_t out_at, bool one_member, std::vector<lfx_member> *members) {
+                DecodeOutcome &oc, uint64_t base, uint64_t out_at, bool one_member, std::vector<lfx_member> *members,
+                const lfx_dict *dict = nullptr) {
     (void)hipSetDevice(c->device);
     hipStream_t st = c->stream;
     bool first = base == 0;
@@ -73,11 +77,16 @@ int member_loop(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_
     for (;;) {
         // ---- container header (device parse, one lane)
         uint64_t off0 = 0;
+        uint64_t dict_hist = dict && format == LFX_DEFLATE ? dict->usable : 0;    // (raw DEFLATE: always the history in front of byte 0)
         if (format != LFX_DEFLATE) {
             DecStream ds{base, n - base, 0, 0};
             DecHeader dh{};
             c->pin_reset();       // (page-locked slots for the two small transfers, lfx_ctx.h)
             HIP_TRY(c->small_up(c->d_small.p, &ds, sizeof ds, st));
+            if (dict)
+                LAUNCH_TRY(launch_container_dict(st, 1, d_in, (const DecStream *)c->d_small.p,
+                                                 (DecHeader *)((uint8_t *)c->d_small.p + 256), dict->id));
+            else
             LAUNCH_TRY(launch_container(st, format, 1, d_in, (const DecStream *)c->d_small.p,
                                         (DecHeader *)((uint8_t *)c->d_small.p + 256)));
             HIP_TRY(c->small_down(&dh, (uint8_t *)c->d_small.p + 256, sizeof dh, st));
@@ -95,6 +104,7 @@ int member_loop(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_
                 return LFX_OK;
             }
             off0 = dh.deflate_off;
+            if (dict && (dh.flags & HDR_DICT)) dict_hist = dict->usable;          // (zlib without FDICT: the dictionary is not used)
         }
         if (c->idx && !sizes_only) {   // (an index build: the member's first block is an access point)
             c->idx->bit_base = base * 8;
@@ -106,7 +116,8 @@ int member_loop(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_
         else {
             mr.ck_mode = ck_mode_of(format);
             mr.trailer_len = trailer_len(format);
-            rc = inflate_member(c, d_in + base, n - base, off0, d_out + out_at, cap - out_at, mr);
+            rc = inflate_member(c, d_in + base, n - base, off0, d_out + out_at, cap - out_at, mr, ~0ull, ~0ull, false, dict_hist,
+                                dict_hist ? dict->d_win : nullptr);
         }
         if (rc) return rc;
         oc.out_len = out_at + mr.out_len;
@@ -142,15 +153,15 @@ int member_loop(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_
 
 int decode_stream(Ctx *c, int format, uint32_t flags, const uint8_t *d_in, uint64_t n, uint8_t *d_out,
                   uint64_t cap, DecodeOutcome &oc, uint64_t base = 0, uint64_t out_at = 0, bool one_member = false,
-                  std::vector<lfx_member> *members = nullptr) {
-    return member_loop(c, format, flags, d_in, n, d_out, cap, false, oc, base, out_at, one_member, members);
+                  std::vector<lfx_member> *members = nullptr, const lfx_dict *dict = nullptr) {
+    return member_loop(c, format, flags, d_in, n, d_out, cap, false, oc, base, out_at, one_member, members, dict);
 }
 
 // The container headers of a list of streams in one launch: hdrs[i] = stream i's parse.  The streams and the headers stay in
 // d_dec_blocks (*d_streams, *d_hdrs, with extra_bytes of room behind the headers) for the kernels of a caller that go on from
 // them.  LFX_DEFLATE has no header: all-zero ones, on the device too, without a round trip.
 int parse_headers(Ctx *c, int format, const uint8_t *d_in, const std::vector<DecStream> &streams, std::vector<DecHeader> &hdrs,
-                  size_t extra_bytes = 0, DecStream **d_streams = nullptr, DecHeader **d_hdrs = nullptr) {
+                  size_t extra_bytes = 0, DecStream **d_streams = nullptr, DecHeader **d_hdrs = nullptr, const lfx_dict *dict = nullptr) {
     hipStream_t st = c->stream;
     const uint32_t count = (uint32_t)streams.size();
     const size_t sz_streams = sizeof(DecStream) * count, sz_hdr = sizeof(DecHeader) * count;
@@ -159,7 +170,8 @@ int parse_headers(Ctx *c, int format, const uint8_t *d_in, const std::vector<Dec
     DecStream *ds = (DecStream *)c->d_dec_blocks.p;
     DecHeader *dh = (DecHeader *)((uint8_t *)c->d_dec_blocks.p + sz_streams);
     HIP_TRY(hipMemcpyAsync(ds, streams.data(), sz_streams, hipMemcpyHostToDevice, st));
-    LAUNCH_TRY(launch_container(st, format, count, d_in, ds, dh));
+    if (dict && format == LFX_ZLIB) LAUNCH_TRY(launch_container_dict(st, count, d_in, ds, dh, dict->id));
+    else LAUNCH_TRY(launch_container(st, format, count, d_in, ds, dh));
     hdrs.assign(count, DecHeader{});
     if (format != LFX_DEFLATE) {
         HIP_TRY(hipMemcpyAsync(hdrs.data(), dh, sz_hdr, hipMemcpyDeviceToHost, st));
@@ -193,6 +205,101 @@ extern "C" int lfx_decode_device(lfx_ctx *cc, int format, uint32_t flags, const 
     if (oc.status != LFX_OK) c->set_error(oc.msg);
     return oc.status;
 } LFX_ABI_CATCH
+
+// ---- the dictionary calls: the same loop with the dictionary; without one, the dictionary-less twin itself
+extern "C" int lfx_decode_dict_device(lfx_ctx *cc, int format, const lfx_dict *dict, const void *d_in, uint64_t n, void *d_out,
+                                      uint64_t cap, uint64_t *out_len, uint64_t *consumed) try {
+    if (!cc) return LFX_E_DEVICE;
+    if (format != LFX_ZLIB && format != LFX_DEFLATE) return LFX_E_ARG;      // (gzip has no preset dictionary)
+    if (!dict) return lfx_decode_device(cc, format, 0, d_in, n, d_out, cap, out_len, consumed);
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    if (dict->c != c) return LFX_E_ARG;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    DecodeOutcome oc;
+    int rc = decode_stream(c, format, 0, (const uint8_t *)d_in, n, (uint8_t *)d_out, cap, oc, 0, 0, false, nullptr, dict);
+    if (rc) return rc;
+    if (oc.status == LFX_OK) c->phase("done");
+    if (oc.out_len > cap) oc.out_len = cap;
+    if (out_len) *out_len = oc.out_len;
+    if (consumed) *consumed = oc.consumed;
+    if (oc.status != LFX_OK) c->set_error(oc.msg);
+    return oc.status;
+} LFX_ABI_CATCH
+
+extern "C" int lfx_decode_dict_host(lfx_ctx *cc, int format, const lfx_dict *dict, const void *in, uint64_t n, void *out,
+                                    uint64_t cap, uint64_t *out_len, uint64_t *consumed) try {
+    if (!cc) return LFX_E_DEVICE;
+    if (format != LFX_ZLIB && format != LFX_DEFLATE) return LFX_E_ARG;
+    if (!dict) return lfx_decode_host(cc, format, 0, in, n, out, cap, out_len, consumed);
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    if (dict->c != c) return LFX_E_ARG;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    int rc;       // (staged as lfx_decode_host stages)
+    if ((rc = c->d_io_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
+    if ((rc = c->d_io_out.reserve(std::max<uint64_t>(cap, 4)))) return rc;
+    if (int hr = host_to_device(c, c->d_io_in.p, in, n, c->stream)) { c->set_error("host to device copy failed"); return hr; }
+    uint64_t ol = 0;
+    rc = lfx_decode_dict_device(cc, format, dict, c->d_io_in.p, n, c->d_io_out.p, cap, &ol, consumed);
+    if (rc == LFX_E_DEVICE || rc == LFX_E_OOM || rc == LFX_E_ARG) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (ol) { if (int hr = device_to_host(c, out, c->d_io_out.p, ol, c->stream)) { c->set_error("device to host copy failed"); return hr; } }
+    if (out_len) *out_len = ol;
+    return rc;
+} LFX_ABI_CATCH
+
+// A dictionary belongs to its context.  The id is computed on the device (the checksum kernels of the trailer check) over ALL
+// bytes; the last min(len, 32768) of them are kept: at the end of a 32 KiB device window, and on the host (stream decoders).
+extern "C" void lfx_dict_free(lfx_dict *d);
+extern "C" lfx_dict *lfx_dict_new(lfx_ctx *cc, const void *bytes, uint64_t len, int on_device, int *status) try {
+    if (status) *status = LFX_OK;
+    if (!cc) { if (status) *status = LFX_E_DEVICE; return nullptr; }
+    if (!bytes && len) { if (status) *status = LFX_E_ARG; return nullptr; }
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    lfx_dict *d = new lfx_dict();
+    d->c = c;
+    auto fail = [&](int rc) -> lfx_dict * { if (status) *status = rc; lfx_dict_free(d); return nullptr; };
+    if (hipMalloc((void **)&d->d_win, MAX_WINDOW) != hipSuccess) { d->d_win = nullptr; return fail(LFX_E_OOM); }
+    if (hipMemsetAsync(d->d_win, 0, MAX_WINDOW, st) != hipSuccess) return fail(LFX_E_DEVICE);
+    d->usable = (uint32_t)std::min<uint64_t>(len, MAX_WINDOW);
+    if (len) {
+        const uint8_t *d_bytes = (const uint8_t *)bytes;
+        if (!on_device) {
+            if (int rc = c->d_io_in.reserve(len)) return fail(rc);
+            if (int hr = host_to_device(c, c->d_io_in.p, bytes, len, st)) { c->set_error("host to device copy failed"); return fail(hr); }
+            d_bytes = (const uint8_t *)c->d_io_in.p;
+        }
+        const uint64_t nspans = ck_nspans(len);
+        if (int rc = c->d_ck.reserve(12 * nspans)) return fail(rc);
+        if (int rc = c->d_res.reserve(256)) return fail(rc);
+        uint32_t *ck = (uint32_t *)c->d_ck.p;
+        if (launch_checksum(st, d_bytes, len, ck, ck + nspans, ck + 2 * nspans, (EncodeResult *)c->d_res.p, 2)) return fail(LFX_E_DEVICE);
+        d->tail.resize(d->usable);
+        if (hipMemcpyAsync(c->h_res, c->d_res.p, sizeof(EncodeResult), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(d->d_win + (MAX_WINDOW - d->usable), d_bytes + (len - d->usable), d->usable, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(d->tail.data(), d_bytes + (len - d->usable), d->usable, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return fail(LFX_E_DEVICE);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(LFX_E_DEVICE);
+    if (len) d->id = ((const EncodeResult *)c->h_res)->adler32;
+    return d;
+} LFX_ABI_CATCH_NEW
+extern "C" uint32_t lfx_dict_id(const lfx_dict *d) { return d ? d->id : 1; }
+extern "C" void lfx_dict_free(lfx_dict *d) {
+    if (!d) return;
+    if (d->d_win) {
+        std::lock_guard<std::recursive_mutex> lock(d->c->mu);
+        (void)hipSetDevice(d->c->device);
+        (void)hipStreamSynchronize(d->c->stream);
+        (void)hipFree(d->d_win);
+    }
+    delete d;
+}
 
 extern "C" int lfx_decode_shard_device(lfx_ctx *cc, const void *d_in, uint64_t n, uint64_t start_bit,
                                        uint64_t total_bits, int is_last, void *d_out, uint64_t cap,
@@ -536,8 +643,10 @@ extern "C" int lfx_decode_host(lfx_ctx *cc, int format, uint32_t flags, const vo
 // back-reference that reaches in front of its block, more than BLOCK_ROUNDS blocks.
 // fast[i] = 1: d_out holds the stream's bytes and res[i] is filled in.
 namespace lfx {
+// dict_end (the dictionary batch): a job's hist_avail = dict_len bytes of history lie in front of its first byte, ending there.
 static int batch_fast(Ctx *c, const uint8_t *d_in, uint64_t n_in, uint8_t *d_out, uint32_t count,
-                      const std::vector<InflateJob> &jobs, std::vector<uint8_t> &fast, std::vector<InflateResult> &res) {
+                      const std::vector<InflateJob> &jobs, std::vector<uint8_t> &fast, std::vector<InflateResult> &res,
+                      const uint8_t *dict_end = nullptr) {
     struct Live { uint32_t stream; uint64_t bit, produced; uint32_t nblocks; };
     std::vector<Live> live;
     fast.assign(count, 0);
@@ -568,15 +677,16 @@ static int batch_fast(Ctx *c, const uint8_t *d_in, uint64_t n_in, uint8_t *d_out
             if (r.status != BLK_OK || r.end_bit <= live[k].bit || r.end_bit > (j.in_off + j.in_len) * 8 ||
                 live[k].produced + r.n_out > j.out_cap)
                 continue;
-            BlkEmit e = blk_emit_of(r, live[k].bit, k, j.out_off + live[k].produced, total_codes, live[k].produced);
-            e.preload = live[k].produced != 0;
+            BlkEmit e = blk_emit_of(r, live[k].bit, k, j.out_off + live[k].produced, total_codes, j.hist_avail + live[k].produced);
+            e.preload = e.hist != 0;
+            e.dict_len = j.dict_len;
             emit.push_back(e);
             owner.push_back(k);
             total_codes += r.n_codes;
         }
         const uint32_t ne = (uint32_t)emit.size();
         std::vector<uint32_t> jf;
-        if (ne && (rc = emit_round(c, d_in, n_in, emit, total_codes, small, d_out, jf, stamp))) return rc;
+        if (ne && (rc = emit_round(c, d_in, n_in, emit, total_codes, small, d_out, jf, stamp, dict_end))) return rc;
         if (c->idx && ne) {   // (an index build: the blocks this round proved)
             std::vector<BlkEmit> ok;
             for (uint32_t q = 0; q < ne; q++) if (!jf[q]) ok.push_back(emit[q]);
@@ -617,7 +727,7 @@ namespace {
 // the body of lfx_decode_batch_device: res[i] = stream i's verdict (trailer included), used[i] = its bytes consumed
 int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uint64_t *in_off, const uint64_t *in_len,
                  void *d_out, const uint64_t *out_off, const uint64_t *out_cap, std::vector<InflateResult> &res,
-                 std::vector<uint64_t> *used = nullptr) {
+                 std::vector<uint64_t> *used = nullptr, const lfx_dict *dict = nullptr) {
     hipStream_t st = c->stream;
     std::vector<DecStream> streams(count);
     for (uint32_t i = 0; i < count; i++) streams[i] = DecStream{in_off[i], in_len[i], out_off[i], out_cap[i]};
@@ -625,7 +735,7 @@ int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uin
     std::vector<DecHeader> hdrs;
     DecStream *d_streams;
     DecHeader *d_hdrs;       // (behind the headers: each stream's checksums and its bytes consumed)
-    if ((rc = parse_headers(c, format, (const uint8_t *)d_in, streams, hdrs, 16ull * count + 64, &d_streams, &d_hdrs))) return rc;
+    if ((rc = parse_headers(c, format, (const uint8_t *)d_in, streams, hdrs, 16ull * count + 64, &d_streams, &d_hdrs, dict))) return rc;
     uint32_t *d_crc = (uint32_t *)(d_hdrs + count);
     uint32_t *d_adler = d_crc + count;
     uint64_t *d_consumed = (uint64_t *)(d_adler + count);
@@ -644,6 +754,8 @@ int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uin
         j.out_off = out_off[i];
         j.out_cap = out_cap[i];
         j.flags = 0;
+        // (the dictionary batch: raw DEFLATE always reads it, zlib when FDICT was set and matched)
+        if (dict && (format == LFX_DEFLATE || (hdrs[i].flags & HDR_DICT))) j.hist_avail = j.dict_len = dict->usable;
         jobs[i] = j;
     }
     // ---- lane-parallel path first; whatever it could not take goes through the exact serial kernel
@@ -652,7 +764,7 @@ int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uin
     std::vector<uint8_t> fast;
     std::vector<InflateResult> fres;
     if (c->diag.batch_serial) { fast.assign(count, 0); fres.assign(count, InflateResult{}); }
-    else if ((rc = batch_fast(c, (const uint8_t *)d_in, n_in, (uint8_t *)d_out, count, jobs, fast, fres))) return rc;
+    else if ((rc = batch_fast(c, (const uint8_t *)d_in, n_in, (uint8_t *)d_out, count, jobs, fast, fres, dict ? dict->d_end() : nullptr))) return rc;
     c->phase("fast");
     std::vector<InflateJob> slow_jobs;
     std::vector<uint32_t> slow_idx;
@@ -666,6 +778,10 @@ int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uin
     HIP_TRY(hipMemcpyAsync(d_res, fres.data(), sizeof(InflateResult) * count, hipMemcpyHostToDevice, st));
     if (nslow) {
         HIP_TRY(hipMemcpyAsync(c->d_dec_streams.p, slow_jobs.data(), sizeof(InflateJob) * nslow, hipMemcpyHostToDevice, st));
+        if (dict)
+            LAUNCH_TRY(launch_inflate_dict(st, (const uint8_t *)d_in, (uint8_t *)d_out, (const InflateJob *)c->d_dec_streams.p, d_slow, nslow,
+                                           dict->d_end()));
+        else
         LAUNCH_TRY(launch_inflate(st, (const uint8_t *)d_in, (uint8_t *)d_out, (const InflateJob *)c->d_dec_streams.p, d_slow, nslow));
         if (nslow == count) HIP_TRY(hipMemcpyAsync(d_res, d_slow, sizeof(InflateResult) * count, hipMemcpyDeviceToDevice, st));
         else for (uint32_t q = 0; q < nslow; q++)
@@ -704,6 +820,32 @@ extern "C" int lfx_decode_batch_device(lfx_ctx *cc, int format, uint32_t count, 
     if (!count) return LFX_OK;
     std::vector<InflateResult> res;
     int rc = decode_batch(c, format, count, d_in, in_off, in_len, d_out, out_off, out_cap, res);
+    if (rc) return rc;
+    int worst = LFX_OK;
+    for (uint32_t i = 0; i < count; i++) {
+        if (out_len) out_len[i] = res[i].out_len;
+        const int s = map_status(res[i].status);
+        if (status) status[i] = s;
+        if (s != LFX_OK && worst == LFX_OK) { worst = s; c->set_error(format_error(res[i].err, res[i].a0, res[i].a1)); }
+    }
+    return LFX_OK;  // per-stream results are in status[]
+} LFX_ABI_CATCH
+
+extern "C" int lfx_decode_batch_dict_device(lfx_ctx *cc, int format, const lfx_dict *dict, uint32_t count, const void *d_in,
+                                            const uint64_t *in_off, const uint64_t *in_len, void *d_out, const uint64_t *out_off,
+                                            const uint64_t *out_cap, uint64_t *out_len, int32_t *status) try {
+    if (!cc) return LFX_E_DEVICE;
+    if (format != LFX_ZLIB && format != LFX_DEFLATE) return LFX_E_ARG;
+    if (!dict) return lfx_decode_batch_device(cc, format, count, d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status);
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    if (dict->c != c) return LFX_E_ARG;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    if (!count) return LFX_OK;
+    std::vector<InflateResult> res;
+    int rc = decode_batch(c, format, count, d_in, in_off, in_len, d_out, out_off, out_cap, res, nullptr, dict);
     if (rc) return rc;
     int worst = LFX_OK;
     for (uint32_t i = 0; i < count; i++) {

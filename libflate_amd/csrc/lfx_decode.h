@@ -21,7 +21,7 @@ struct InflateJob {
     uint64_t hist_avail;  // bytes of this member already produced before this job
     uint64_t stop_bit;    // != 0: the walk ends cleanly when a block ends exactly at this bit (a shard without BFINAL)
     uint32_t flags;
-    uint32_t _pad;
+    uint32_t dict_len;    // inflate_dict_kernel only: of hist_avail, so many bytes are the preset dictionary's tail (not in `out`)
 };
 struct InflateResult {
     uint64_t end_bit;  // bit after the last consumed bit (stored blocks: after the data)
@@ -77,6 +77,9 @@ int launch_blk_emit(hipStream_t st, const uint8_t *in, uint64_t nbytes, const Bl
 int launch_blk_materialize(hipStream_t st, const uint8_t *in, const BlkEmit *jobs, uint32_t njobs,
                            const BlkLanes *lanes, const BlkUnits *units, const uint32_t *codes, uint8_t *out,
                            uint64_t *dbg);
+// the dictionary instance: a preloading job's history is BlkEmit::dict_len bytes that end at dict_end, then `out`
+int launch_blk_materialize_dict(hipStream_t st, const uint8_t *in, const BlkEmit *jobs, uint32_t njobs, const BlkUnits *units,
+                                const uint32_t *codes, uint8_t *out, const uint8_t *dict_end);
 
 // marker-based materialisation (streams whose blocks read earlier blocks):
 //  sym: one 16-bit symbol per output byte — a byte value, or 256 + j = byte j of the 32 KiB in front of the unit
@@ -105,6 +108,12 @@ int launch_container(hipStream_t st, int format, uint32_t count, const uint8_t *
                      const DecStream *streams, DecHeader *hdrs);
 int launch_inflate(hipStream_t st, const uint8_t *in, uint8_t *out, const InflateJob *jobs,
                    InflateResult *results, uint32_t njobs);
+// the dictionary instances: a zlib header with FDICT is accepted when its DICTID is dict_id (DecHeader::flags =
+// HDR_DICT), and refused with ERR_DICT_MISMATCH when not; a job's history is InflateJob::dict_len bytes that end at dict_end
+int launch_container_dict(hipStream_t st, uint32_t count, const uint8_t *in, const DecStream *streams, DecHeader *hdrs,
+                          uint32_t dict_id);
+int launch_inflate_dict(hipStream_t st, const uint8_t *in, uint8_t *out, const InflateJob *jobs, InflateResult *results,
+                        uint32_t njobs, const uint8_t *dict_end);
 // The finder's survivor lists: FIND_SHARDS lists of shard_cap entries — since round 6 a list holds ONE class of survivors
 // (lfx_decode_kernels.hip: FIND_CLASSES classes x FIND_SUB lists each; a device-scope counter serialises at ~11 ns per atomic,
 // and a workgroup of stage 1 now adds to about ten of them instead of one).  The buffer starts with FIND_HDR_WORDS 32-bit

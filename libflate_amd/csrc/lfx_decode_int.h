@@ -46,7 +46,9 @@ struct DecodeOutcome {
 };
 
 // run `njobs` inflate jobs (the exact serial kernel) and fetch their results
-int run_jobs(Ctx *c, const uint8_t *d_in, uint8_t *d_out, const std::vector<InflateJob> &jobs, std::vector<InflateResult> &res);
+// (dict_end: the dictionary instance — the jobs' dict_len bytes of history end there, lfx_decode.h)
+int run_jobs(Ctx *c, const uint8_t *d_in, uint8_t *d_out, const std::vector<InflateJob> &jobs, std::vector<InflateResult> &res,
+             const uint8_t *dict_end = nullptr);
 
 // `consumed` behind an "Invalid huffman coded stream" verdict of the exact kernel (lfx_decode.cpp): the decode, the size call and
 // the batch decode all report what the reference's reader has pulled from its input at that point
@@ -61,8 +63,13 @@ int huff_consumed(Ctx *c, const uint8_t *d_in, const std::vector<HuffProbe> &pro
 // partial: a WINDOW of a member (the stream decoders): decode the blocks that are complete in d_in[0..n) and fit into
 // `cap`, stop cleanly in front of the first one that is not (mr.end_bit = its header bit, mr.final_seen = false); `hist`
 // = bytes of the member produced by earlier windows — the last 32 KiB of them lie right in front of d_out.
+// hist_win (not with partial): the history is DETACHED — a preset dictionary's tail, DESIGN §17: the last 32 KiB of the
+// `hist` bytes are hist_win[0, 32768) (fewer: right-aligned), nothing in front of d_out is read.  Blocks that reach into it
+// take the marker path with hist_win as the window in front of the first unit; the exact walk is the dictionary instance
+// of the serial kernel.
 int inflate_member(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t off0, uint8_t *d_out, uint64_t cap, MemberResult &mr,
-                   uint64_t start_bit0 = ~0ull, uint64_t stop_bit = ~0ull, bool partial = false, uint64_t hist = 0);
+                   uint64_t start_bit0 = ~0ull, uint64_t stop_bit = ~0ull, bool partial = false, uint64_t hist = 0,
+                   const uint8_t *hist_win = nullptr);
 
 // ---- stages that the N-GPU range calls and the size path run too
 
@@ -117,7 +124,8 @@ int scan_round(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkJob
                bool &small, bool stamp = false);
 // emit[] (jobs of the scan_round before it, want_tabs) decoded to code words and materialised into d_out; jf[q] != 0: job q
 // reads in front of its history.  stamp: phases "blk_emit" and "lz77_copy".
+// dict_end: the dictionary instance of the materialise kernel (the jobs' dict_len bytes of history end there).
 int emit_round(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkEmit> &emit, uint64_t total_codes, bool small,
-               uint8_t *d_out, std::vector<uint32_t> &jf, bool stamp = false);
+               uint8_t *d_out, std::vector<uint32_t> &jf, bool stamp = false, const uint8_t *dict_end = nullptr);
 
 }  // namespace lfx

@@ -1672,12 +1672,15 @@ struct M2Lds {
     static constexpr uint32_t SW_BYTES = 2 * G::WAVES * 4;
     static constexpr uint32_t BYTES = RING_BYTES + P_BYTES + XC_BYTES + SW_BYTES;
 };
-template <bool SYM, uint32_t THREADS, bool DYN = false>
+// DICT (blk_materialize2_dict_kernel): of a preloading job's history, the first dict_len bytes are the tail of a
+// preset dictionary that ends at dict_end — shared by every job, never copied in front of an output — and the rest lies in `out`.
+template <bool SYM, uint32_t THREADS, bool DYN = false, bool DICT = false>
 __device__ __forceinline__ void materialize2_body(const uint8_t *__restrict__ in, const BlkEmit *__restrict__ jobs,
                                                   const BlkUnits *__restrict__ units,
                                                   const uint32_t *__restrict__ codes,
                                                   typename std::conditional<SYM, uint16_t, uint8_t>::type *__restrict__ out,
-                                                  uint32_t njobs, uint64_t *__restrict__ dbg) {
+                                                  uint32_t njobs, uint64_t *__restrict__ dbg,
+                                                  const uint8_t *__restrict__ dict_end = nullptr) {
     using elem_t = typename std::conditional<SYM, uint16_t, uint8_t>::type;
     using G = M2<THREADS>;
     using LD = M2Lds<SYM, THREADS>;
@@ -1725,6 +1728,15 @@ __device__ __forceinline__ void materialize2_body(const uint8_t *__restrict__ in
     // SYM: the 32 Ki markers "entry j of the window in front of this unit".
     const uint32_t hist = SYM ? 32768u : (u == 0 && job.preload) ? (uint32_t)(job.hist < 32768 ? job.hist : 32768) : 0;
     const uint32_t shift = (uint32_t)((gbase - hist) & (EPD - 1)) + hist;       // < RING
+    if constexpr (DICT && !SYM) {
+        // the ring's history from two sources: the stream's own bytes in front of the block come from `out`, what lies in front
+        // of the stream's first byte from the dictionary's tail (back - own <= job.hist - own = dict_len)
+        const uint64_t own = job.hist - job.dict_len;
+        for (uint32_t k = tid; k < hist; k += THREADS) {
+            const uint32_t back = hist - k;
+            ring[shift - hist + k] = back <= own ? o[-(int64_t)back] : dict_end[(int64_t)own - (int64_t)back];
+        }
+    } else
     for (uint32_t k = tid; k < hist; k += THREADS)
         ring[shift - hist + k] = SYM ? (elem_t)(256 + k) : (elem_t)o[(int64_t)k - (int64_t)hist];
     if (tid < 4) XC[NC + tid] = make_uint2(0xFFFFFFFFu, 0u);
@@ -1934,6 +1946,15 @@ __global__ __launch_bounds__(THREADS) void blk_materialize2_kernel(const uint8_t
                                                                    uint8_t *__restrict__ out, uint32_t njobs,
                                                                    uint64_t *__restrict__ dbg) {
     materialize2_body<false, THREADS>(in, jobs, units, codes, out, njobs, dbg);
+}
+template <uint32_t THREADS>
+__global__ __launch_bounds__(THREADS) void blk_materialize2_dict_kernel(const uint8_t *__restrict__ in,
+                                                                        const BlkEmit *__restrict__ jobs,
+                                                                        const BlkUnits *__restrict__ units,
+                                                                        const uint32_t *__restrict__ codes,
+                                                                        uint8_t *__restrict__ out, uint32_t njobs,
+                                                                        const uint8_t *__restrict__ dict_end) {
+    materialize2_body<false, THREADS, false, true>(in, jobs, units, codes, out, njobs, nullptr, dict_end);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2721,6 +2742,16 @@ int launch_blk_materialize(hipStream_t st, const uint8_t *in, const BlkEmit *job
         hipLaunchKernelGGL(blk_materialize2_kernel<M2_WIDE_THREADS>, dim3(njobs * MAX_UNITS), dim3(M2_WIDE_THREADS), 0, st, in, jobs, units, codes, out, njobs, dbg);
     else
         hipLaunchKernelGGL(blk_materialize2_kernel<M2_THREADS>, dim3(njobs * MAX_UNITS), dim3(M2_THREADS), 0, st, in, jobs, units, codes, out, njobs, dbg);
+    LFX_LAUNCH_CHECK();
+    return 0;
+}
+int launch_blk_materialize_dict(hipStream_t st, const uint8_t *in, const BlkEmit *jobs, uint32_t njobs, const BlkUnits *units,
+                                const uint32_t *codes, uint8_t *out, const uint8_t *dict_end) {
+    if (!njobs) return 0;
+    if (njobs <= M2_FEW_JOBS)       // (the geometries of launch_blk_materialize)
+        hipLaunchKernelGGL(blk_materialize2_dict_kernel<M2_WIDE_THREADS>, dim3(njobs * MAX_UNITS), dim3(M2_WIDE_THREADS), 0, st, in, jobs, units, codes, out, njobs, dict_end);
+    else
+        hipLaunchKernelGGL(blk_materialize2_dict_kernel<M2_THREADS>, dim3(njobs * MAX_UNITS), dim3(M2_THREADS), 0, st, in, jobs, units, codes, out, njobs, dict_end);
     LFX_LAUNCH_CHECK();
     return 0;
 }

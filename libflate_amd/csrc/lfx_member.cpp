@@ -13,7 +13,7 @@
 namespace lfx {
 
 int run_jobs(Ctx *c, const uint8_t *d_in, uint8_t *d_out, const std::vector<InflateJob> &jobs,
-             std::vector<InflateResult> &res) {
+             std::vector<InflateResult> &res, const uint8_t *dict_end) {
     const size_t n = jobs.size();
     res.resize(n);
     if (!n) return LFX_OK;
@@ -21,8 +21,12 @@ int run_jobs(Ctx *c, const uint8_t *d_in, uint8_t *d_out, const std::vector<Infl
     if ((rc = c->d_dec_streams.reserve(sizeof(InflateJob) * n))) return rc;
     if ((rc = c->d_dec_state.reserve(sizeof(InflateResult) * n))) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_dec_streams.p, jobs.data(), sizeof(InflateJob) * n, hipMemcpyHostToDevice, c->stream));
-    LAUNCH_TRY(launch_inflate(c->stream, d_in, d_out, (const InflateJob *)c->d_dec_streams.p,
-                              (InflateResult *)c->d_dec_state.p, (uint32_t)n));
+    if (dict_end)
+        LAUNCH_TRY(launch_inflate_dict(c->stream, d_in, d_out, (const InflateJob *)c->d_dec_streams.p,
+                                       (InflateResult *)c->d_dec_state.p, (uint32_t)n, dict_end));
+    else
+        LAUNCH_TRY(launch_inflate(c->stream, d_in, d_out, (const InflateJob *)c->d_dec_streams.p,
+                                  (InflateResult *)c->d_dec_state.p, (uint32_t)n));
     HIP_TRY(hipMemcpyAsync(res.data(), c->d_dec_state.p, sizeof(InflateResult) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return LFX_OK;
@@ -188,7 +192,7 @@ int scan_round(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkJob
 }
 
 int emit_round(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkEmit> &emit, uint64_t total_codes, bool small,
-               uint8_t *d_out, std::vector<uint32_t> &jf, bool stamp) {
+               uint8_t *d_out, std::vector<uint32_t> &jf, bool stamp, const uint8_t *dict_end) {
     hipStream_t st = c->stream;
     const uint32_t ne = (uint32_t)emit.size();
     const EmitTmp t = emit_tmp_layout(ne);
@@ -204,8 +208,12 @@ int emit_round(Ctx *c, const uint8_t *d_in, uint64_t n, const std::vector<BlkEmi
     LAUNCH_TRY(launch_blk_emit(st, d_in, n, d_emit, ne, (const BlkLanes *)c->d_dec_cand.p, (uint32_t *)c->d_codes.p, d_flags,
                                (BlkUnits *)c->d_hist.p, emit_unit_target(total_codes, c->n_cu), d_jf, c->d_dec_tabs.p, 17, false, small));
     if (stamp) c->phase("blk_emit");
-    LAUNCH_TRY(launch_blk_materialize(st, d_in, d_emit, ne, (const BlkLanes *)c->d_dec_cand.p, (const BlkUnits *)c->d_hist.p,
-                                      (const uint32_t *)c->d_codes.p, d_out, nullptr));
+    if (dict_end)
+        LAUNCH_TRY(launch_blk_materialize_dict(st, d_in, d_emit, ne, (const BlkUnits *)c->d_hist.p, (const uint32_t *)c->d_codes.p,
+                                               d_out, dict_end));
+    else
+        LAUNCH_TRY(launch_blk_materialize(st, d_in, d_emit, ne, (const BlkLanes *)c->d_dec_cand.p, (const BlkUnits *)c->d_hist.p,
+                                          (const uint32_t *)c->d_codes.p, d_out, nullptr));
     if (stamp) c->phase("lz77_copy");
     jf.resize(ne);
     HIP_TRY(hipMemcpyAsync(jf.data(), d_jf, 4ull * ne, hipMemcpyDeviceToHost, st));
@@ -228,6 +236,7 @@ struct Member {
     uint64_t first_bit, stop_bit;
     bool partial;
     uint64_t hist;
+    const uint8_t *hist_win;   // null: the history lies in front of d_out; else a detached 32 KiB window that ends with it
     uint64_t comp;         // compressed bytes from off0 on
     uint64_t end_bits() const { return n * 8; }
 };
@@ -585,7 +594,7 @@ int materialise_markers(const Member &m, const Chain &ch, const BlkEmit *d_emit)
     // (a later window of a member: the 32 KiB in front of d_out hold the member's earlier output — the markers of
     //  the first unit resolve through them; bytes in front of what `hist` covers are never looked up: a reference
     //  that far back raised flag 1 in the emit step)
-    const uint8_t *init_win = m.hist ? m.d_out - MAX_WINDOW : nullptr;
+    const uint8_t *init_win = m.hist_win ? m.hist_win : m.hist ? m.d_out - MAX_WINDOW : nullptr;
     std::vector<BlkUnits> uv(ne);
     HIP_TRY(hipMemcpyAsync(uv.data(), c->d_hist.p, sizeof(BlkUnits) * ne, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -704,16 +713,17 @@ int serial_walk(const Member &m, MemberResult &mr) {
     InflateJob j{};
     j.in_off = 0; j.in_len = n; j.start_bit = m.first_bit;
     j.out_off = 0; j.out_cap = m.cap; j.hist_avail = m.hist; j.flags = 0;
+    j.dict_len = m.hist_win ? (uint32_t)m.hist : 0;      // (a detached history is a dictionary's tail: the dictionary instance)
     j.stop_bit = m.stop_bit == ~0ull ? 0 : m.stop_bit;   // (small or irregular shards: the exact walk, ended at the shard's last bit)
     std::vector<InflateResult> res;
     int rc;
-    if ((rc = run_jobs(c, m.d_in, m.d_out, {j}, res))) return rc;
+    if ((rc = run_jobs(c, m.d_in, m.d_out, {j}, res, m.hist_win ? m.hist_win + MAX_WINDOW : nullptr))) return rc;
     c->phase("serial");
     InflateResult &r = res[0];
     // an unassigned code in a whole member: `consumed` is what the reference's reader has pulled by then, as in the size call
     // (end_bit counts the 16 bits the reference skips without reading them)
     uint64_t huff_used = ~0ull;
-    if (huff_verdict(r) && m.stop_bit == ~0ull && !m.partial && m.hist == 0) {
+    if (huff_verdict(r) && m.stop_bit == ~0ull && !m.partial && (m.hist == 0 || m.hist_win)) {
         std::vector<uint64_t> used;
         if ((rc = huff_consumed(c, m.d_in, {HuffProbe{0, n, r}}, used))) return rc;
         huff_used = used[0];
@@ -748,8 +758,9 @@ int serial_walk(const Member &m, MemberResult &mr) {
 }  // namespace
 
 int inflate_member(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t off0, uint8_t *d_out, uint64_t cap, MemberResult &mr,
-                   uint64_t start_bit0, uint64_t stop_bit, bool partial, uint64_t hist) {
-    const Member m{c, d_in, n, off0, d_out, cap, start_bit0 == ~0ull ? off0 * 8 : start_bit0, stop_bit, partial, hist, n > off0 ? n - off0 : 0};
+                   uint64_t start_bit0, uint64_t stop_bit, bool partial, uint64_t hist, const uint8_t *hist_win) {
+    const Member m{c, d_in, n, off0, d_out, cap, start_bit0 == ~0ull ? off0 * 8 : start_bit0, stop_bit, partial, hist, hist ? hist_win : nullptr,
+                   n > off0 ? n - off0 : 0};
     mr.end_bit = m.first_bit;
     c->pin_reset();        // (the page-locked slots of the small transfers, lfx_ctx.h: nothing of an earlier member is in flight)
     bool done = false;

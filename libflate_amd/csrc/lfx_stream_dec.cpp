@@ -13,6 +13,7 @@
 #include "lfx_device.h"
 #include "lfx_hostio.h"
 #include "lfx_stream_dec.h"
+#include "lfx_dict.h"
 #include "lfx_abi_guard.h"
 
 using namespace lfx;
@@ -36,7 +37,9 @@ int gpu_window(Ctx *c, const WindowIn &wi, DecWindow<PinVec> &W) {
     if (n && hipMemcpyAsync(c->d_io_in.p, wi.in, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LFX_E_DEVICE;
     if (H && hipMemcpyAsync(d_out - H, wi.hist, H, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LFX_E_DEVICE;
     const auto tw0 = std::chrono::steady_clock::now();
-    rc = inflate_member(c, (const uint8_t *)c->d_io_in.p, n, 0, d_out, wi.out_cap, mr, wi.bit_off, ~0ull, wi.partial(), wi.member_out);
+    // (a preset dictionary's tail came with wi.hist and lies in front of d_out like earlier output; it counts for the reach bound)
+    rc = inflate_member(c, (const uint8_t *)c->d_io_in.p, n, 0, d_out, wi.out_cap, mr, wi.bit_off, ~0ull, wi.partial(),
+                        wi.dict_len + wi.member_out);
     if (rc) return rc;
     const auto tw1 = std::chrono::steady_clock::now();
     W.mr.status = mr.status; W.mr.out_len = mr.out_len; W.mr.blk_out_start = mr.blk_out_start; W.mr.end_byte = mr.end_byte;
@@ -119,6 +122,10 @@ extern "C" int64_t lfx_decoder_read(lfx_decoder *d, uint8_t *out, size_t cap) tr
     if (k < 0 && d->next.rc && k == -(int64_t)d->next.rc && d->err.empty()) d->err = d->ctx()->err;
     return k;
 } LFX_ABI_CATCH_NEG
+extern "C" int lfx_decoder_set_dict(lfx_decoder *d, const lfx_dict *dict) try {
+    if (!d || !dict || dict->c != d->ctx()) return LFX_E_ARG;
+    return dec_set_dict(d, dict->tail.data(), dict->usable, dict->id);
+} LFX_ABI_CATCH
 extern "C" int lfx_decoder_unread(lfx_decoder *d, const uint8_t **p, size_t *n) try {
     if (!d) return LFX_E_ARG;
     dec_unread(d, p, n);

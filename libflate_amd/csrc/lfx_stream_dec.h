@@ -86,6 +86,8 @@ struct WindowIn {
     uint64_t in_base;
     int format;
     uint64_t in_max;             // WindowPolicy::window_in_max
+    uint64_t dict_len = 0;       // a member that reads a preset dictionary: so many bytes of history lie in front of the member's
+                                 //   first byte (the backend's reach bound is dict_len + member_out; `hist` holds them like output)
     // (once the reader has ended nothing more can arrive: the exact walk gives the member's verdict)
     bool at_limit() const { return !reader_eof && n >= in_max; }
     bool partial() const { return !reader_eof && !at_limit(); }
@@ -145,6 +147,15 @@ struct StreamDec {
     Window next;
     std::thread worker;
     bool ahead = false;             // `worker` is running (or has finished) window k + 1
+    // ---- a preset dictionary (lfx_decoder_set_dict): its usable tail (the caller's object owns the bytes) and its
+    // id.  zlib: judged against the header's DICTID, used when FDICT is set; raw DEFLATE: always the history of byte 0
+    bool has_dict = false;
+    const uint8_t *dict = nullptr;
+    uint64_t dict_len = 0;
+    uint32_t dict_id = 1;
+    bool header_fdict = false;      // the current member's header carried FDICT (and the dictionary matched)
+    bool started = false;           // a header was parsed or a read was served: too late for a dictionary
+    uint64_t member_dict() const { return has_dict && (format == LFX_DEFLATE || header_fdict) ? dict_len : 0; }
     ~StreamDec() { if (worker.joinable()) worker.join(); }     // (however the decoder goes: never from under its worker)
 };
 
@@ -183,10 +194,13 @@ void dec_serve_nothing(D *d) {
 template <class D>
 int dec_header(D *d) {
     if (d->format == LFX_DEFLATE) { d->have_header = true; d->hf = ContainerFields{}; d->hdr_bytes.clear(); return LFX_OK; }
+    d->started = true;
     for (;;) {
         ContainerFields cf;
-        const DecHeader h = parse_container(d->format, d->in.data(), d->in.size(), &cf);
+        DecHeader h = parse_container(d->format, d->in.data(), d->in.size(), &cf);
+        if (d->has_dict && d->format == LFX_ZLIB) h = resolve_fdict(h, d->dict_id);
         if (h.status == 0) {
+            d->header_fdict = d->format == LFX_ZLIB && (h.flags & HDR_DICT);
             d->hf = cf;                    // (a header that fails to parse leaves the previous member's in place)
             d->hdr_bytes.assign(d->in.begin(), d->in.begin() + (size_t)h.deflate_off);
             d->have_header = true;
@@ -238,7 +252,7 @@ template <class D>
 void dec_window(D *d, typename D::Window &W) {
     for (;;) {
         const WindowIn wi{d->in.data(), d->in.size(), d->bit_off, d->hist.data(), d->hist.size(), d->member_out, d->reader_eof,
-                          d->out_cap, d->consumed_total, d->format, d->pol.window_in_max};
+                          d->out_cap, d->consumed_total, d->format, d->pol.window_in_max, d->member_dict()};
         W.n = wi.n;
         W.crc = 0;
         W.adler = 1;
@@ -416,6 +430,9 @@ int dec_body(D *d) {
         d->consumed_total += hl;
         d->body_started = true;
         d->bit_off = 0; d->member_out = 0; d->hist.clear(); d->run_crc = 0; d->run_adler = 1; d->member_final = false;
+        // (a preset dictionary is history like any other: the first window finds its tail where later ones find earlier output;
+        //  the container checksum never covers it)
+        if (const uint64_t dl = d->member_dict()) d->hist.assign(d->dict, d->dict + dl);
         d->target = 0; d->tried_at = 0;
         d->out_cap = d->pol.window_out;
     }
@@ -432,7 +449,7 @@ int dec_body(D *d) {
 // it lazily (src/non_blocking/gzip.rs:64-88).  → LFX_OK, or the header's failure (err set)
 template <class D>
 int dec_open(D *d) {
-    if (d->flags & LFX_DEC_NONBLOCKING) return LFX_OK;
+    if (d->flags & (LFX_DEC_NONBLOCKING | LFX_DEC_LAZY_HEADER)) return LFX_OK;
     const int rc = dec_header(d);
     if (rc == LFX_OK) d->state = D::ST_BODY;
     return rc;
@@ -442,6 +459,7 @@ int dec_open(D *d) {
 template <class D>
 int64_t dec_read(D *d, uint8_t *out, size_t cap) {
     if (cap == 0) return 0;  // never latches end-of-stream (gzip.rs:1025-1027, zlib.rs:383-385)
+    d->started = true;
     for (;;) {
         switch (d->state) {
             case D::ST_DONE: return 0;
@@ -510,7 +528,7 @@ template <class D>
 int dec_header_get(D *d, lfx_header *h) {
     memset(h, 0, sizeof *h);
     if (!d->have_header) {
-        if (!(d->flags & LFX_DEC_NONBLOCKING) || d->state != D::ST_HEADER) return LFX_E_ARG;
+        if (!(d->flags & (LFX_DEC_NONBLOCKING | LFX_DEC_LAZY_HEADER)) || d->state != D::ST_HEADER) return LFX_E_ARG;
         const int rc = dec_header(d);          // non-blocking decoders read the header on demand (non_blocking/gzip.rs:98-113)
         if (rc) { if (rc != LFX_E_WOULD_BLOCK) d->state = D::ST_FAILED; return rc; }
         d->state = D::ST_BODY;
@@ -543,10 +561,19 @@ void dec_close(D *d, Give give) {
     give(std::move(d->next.out));
     delete d;
 }
+// a preset dictionary for the decoder: only before anything was parsed or served, never for gzip
+template <class D>
+int dec_set_dict(D *d, const uint8_t *tail, uint64_t tail_len, uint32_t id) {
+    if (d->format == LFX_GZIP || d->started || d->has_dict) return LFX_E_ARG;
+    d->has_dict = true; d->dict = tail; d->dict_len = tail_len; d->dict_id = id;
+    return LFX_OK;
+}
 template <class D>
 uint64_t dec_buffered(D *d) {
     dec_settle(d);      // (a window decoded ahead counts, and its buffer is not read while it grows)
-    return (uint64_t)(d->in.size() + d->out.size() + d->hist.size() + d->next.out.size());
+    // (of the history only the member's own bytes: a preset dictionary's tail in front of them is the caller's, not buffered input)
+    const uint64_t own_hist = std::min<uint64_t>(d->hist.size(), d->member_out);
+    return (uint64_t)(d->in.size() + d->out.size() + own_hist + d->next.out.size());
 }
 
 }  // namespace lfx

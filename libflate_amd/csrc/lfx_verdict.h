@@ -48,6 +48,7 @@ inline std::string format_error(uint32_t err, uint32_t a0, uint32_t a1) {
         case ERR_HCRC: snprintf(m, sizeof m, "CRC16 of GZIP header mismatched: value=%u, expected=%u", a0, a1); return m;
         case ERR_CRC32: snprintf(m, sizeof m, "CRC32 mismatched: value=%u, expected=%u", a0, a1); return m;
         case ERR_ADLER32: snprintf(m, sizeof m, "Adler32 checksum mismatched: value=%u, expected=%u", a0, a1); return m;
+        case ERR_DICT_MISMATCH: snprintf(m, sizeof m, "Dictionary mismatch: dictionary_id=0x%X, supplied=0x%X", a0, a1); return m;
         default: return "";
     }
 }

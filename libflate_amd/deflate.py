@@ -67,5 +67,6 @@ class Decoder(_DecoderBase):
     FORMAT = _ffi.DEFLATE
 
     @classmethod
-    def new(cls, inner, context=None):
-        return cls(inner, context)
+    def new(cls, inner, context=None, zdict=None):
+        """zdict: a preset dictionary, bytes or a libflate_amd.Dictionary (what zlib.decompressobj(zdict=...) takes)"""
+        return cls(inner, context, zdict)

@@ -11,8 +11,8 @@ class _NB(_DecoderBase):
     FLAGS = _ffi.DEC_NONBLOCKING
 
     @classmethod
-    def new(cls, inner, context=None):
-        return cls(inner, context)
+    def new(cls, inner, context=None, zdict=None):
+        return cls(inner, context, zdict)
 
 
 class deflate:  # noqa: N801  (module-like namespace: non_blocking::deflate::Decoder)

@@ -35,5 +35,6 @@ class Decoder(_DecoderBase):
     FORMAT = _ffi.ZLIB
 
     @classmethod
-    def new(cls, inner, context=None):
-        return cls(inner, context)
+    def new(cls, inner, context=None, zdict=None):
+        """zdict: a preset dictionary, bytes or a libflate_amd.Dictionary (what zlib.decompressobj(zdict=...) takes)"""
+        return cls(inner, context, zdict)
