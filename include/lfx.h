@@ -657,6 +657,42 @@ int lfx_decode_batch_dict_device(lfx_ctx *c, int format, const lfx_dict *dict, u
 #define LFX_DEC_LAZY_HEADER 4u
 int lfx_decoder_set_dict(lfx_decoder *d, const lfx_dict *dict);
 
+/* ---- encoding with a preset dictionary: what zlib.decompressobj(zdict=...) and the decode calls above read ----
+ * The reference has no dictionary-primed parse; this is the definition the encoder is exact with.
+ *
+ *  Let T be the usable tail of the dictionary, its last min(len, 32768) bytes, and buf the FIRST LZ77 flush unit ("chunk") of a
+ *  stream as the plan cuts it (options and schedule as in the dictionary-less call).  The code words of that chunk are what
+ *  DefaultLz77Encoder::flush (default.rs:69-109) writes for the buffer T ‖ buf when its prefix table already holds every
+ *  position < |T|, each inserted once, in order, and its walk starts at i = |T|.  Everything else is the reference's:
+ *    - end = max(3, |T| + |buf|) - 3, and the positions from end on are literals;
+ *    - a candidate is the most recent earlier occurrence of the 3-byte prefix — the two prefixes that straddle the boundary, at
+ *      |T|-2 and |T|-1, are positions of T, are in the table and depend on the chunk's first two bytes;
+ *    - a candidate farther than window_size makes a literal, no older occurrence is tried;
+ *    - lengths are capped by max_length; a match may start in T and run on into buf.
+ *  The reference clears its buffer at every flush: later chunks are exactly what the dictionary-less call makes of them.
+ *  (Whenever the reference's own flush of T ‖ buf has a code-word boundary at |T|, the chunk's code words are the suffix of that
+ *  flush's output behind the boundary.)
+ *
+ *  Container.  LFX_ZLIB: CMF and FLEVEL as lfx_encode_device writes them, FDICT set, FCHECK recomputed, then DICTID =
+ *  lfx_dict_id(dict) in four bytes, big-endian, the body, and the Adler-32 of the input only.  LFX_DEFLATE: the body alone.
+ *  LFX_GZIP: LFX_E_ARG, whatever `dict` is.  dict == NULL: byte for byte the dictionary-less twin.  A dictionary of another
+ *  context: LFX_E_ARG.  Options that do no matching (no_compression, LFX_LZ77_NOCOMPRESSION) still write FDICT and DICTID; their
+ *  code words are unchanged.  Huffman coding, block cutting, packing and the checksum run unchanged on the new code words.
+ *  In the batch call every stream's first chunk is primed by the one dictionary, read in place; status, LFX_E_NOSPACE and the
+ *  zero fill are lfx_encode_batch_device's.  lfx_encode_dict_bound = lfx_encode_bound + 4 (0 where that is 0).
+ *  The first encode call that uses a dictionary builds its prefix table on the device and keeps it in the lfx_dict.
+ *  Not covered: the stream encoder (lfx_encoder_*), the members encode, the encode-time index, the N-GPU encode, lfx_lz77. */
+uint64_t lfx_encode_dict_bound(uint64_t n, const lfx_encode_opts *o, const lfx_schedule *s);
+int lfx_encode_dict_device(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
+                           const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len);
+/* same, host buffers (staged like lfx_encode_host) */
+int lfx_encode_dict_host(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
+                         const void *in, uint64_t n, void *out, uint64_t cap, uint64_t *out_len);
+/* lfx_encode_batch_device with one dictionary for every stream (out_cap[i] >= lfx_encode_dict_bound(in_len[i])) */
+int lfx_encode_batch_dict_device(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
+                                 uint32_t count, const void *d_in, const uint64_t *in_off, const uint64_t *in_len, void *d_out,
+                                 const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status);
+
 /* ---- plug-in: libflate_lz77::Lz77Encode (libflate_lz77/src/lib.rs:83-107) -----------------
  * Codes are delivered in batches: word = (val << 16) | dist; dist == 0 → Code::Literal(val),
  * else Code::Pointer{length: val, backward_distance: dist} (lib.rs:27-42). */

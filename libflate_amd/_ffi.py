@@ -43,6 +43,7 @@ EXPORTS = [
     "lfx_decode_members_size_host", "lfx_bgzf_read_device", "lfx_bgzf_read_host", "lfx_members_voffset",
     "lfx_dict_new", "lfx_dict_id", "lfx_dict_free", "lfx_decode_dict_device", "lfx_decode_dict_host",
     "lfx_decode_batch_dict_device", "lfx_decoder_set_dict",
+    "lfx_encode_dict_bound", "lfx_encode_dict_device", "lfx_encode_dict_host", "lfx_encode_batch_dict_device",
 ]
 
 
@@ -204,6 +205,11 @@ def lib():
     L.lfx_decode_dict_host.argtypes = [vp, i32, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.lfx_decode_batch_dict_device.argtypes = [vp, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lfx_decoder_set_dict.argtypes = [vp, vp]
+    L.lfx_encode_dict_bound.restype = u64
+    L.lfx_encode_dict_bound.argtypes = [u64, C.POINTER(EncodeOpts), C.POINTER(Schedule)]
+    L.lfx_encode_dict_device.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.lfx_encode_dict_host.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.lfx_encode_batch_dict_device.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lfx_decode_members_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,
                                             C.POINTER(u32)]
     L.lfx_decode_members_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,

@@ -373,6 +373,50 @@ class Context:
             raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
         return [(st[i], out_len[i]) for i in range(k)]
 
+    # ---- encoding with a preset dictionary (lfx_encode_dict_*) ---------------------------
+    def encode_dict_device(self, fmt, zdict, d_in, n, d_out, cap, opts=None, schedule=None):
+        """lfx_encode_dict_device: zlib (FDICT + DICTID) / raw DEFLATE whose first chunk is primed by a Dictionary (None: exactly
+        encode_device) → out_len"""
+        out_len = C.c_uint64(0)
+        rc = _ffi.lib().lfx_encode_dict_device(self._h, fmt, C.byref(opts) if opts is not None else None,
+                                               C.byref(schedule) if schedule is not None else None, self._dict_handle(zdict),
+                                               d_in, n, d_out, cap, C.byref(out_len))
+        if rc:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return out_len.value
+
+    def encode_dict_host(self, fmt, zdict, data, opts=None, schedule=None):
+        """lfx_encode_dict_host on host bytes → the stream"""
+        data = bytes(data)
+        bound = _ffi.lib().lfx_encode_dict_bound(len(data), C.byref(opts) if opts is not None else None,
+                                                 C.byref(schedule) if schedule is not None else None)
+        if bound == 0:
+            raise _ffi.LfxError(_ffi.E_ARG, "option outside the reference's domain")
+        out = C.create_string_buffer(bound)
+        out_len = C.c_uint64(0)
+        rc = _ffi.lib().lfx_encode_dict_host(self._h, fmt, C.byref(opts) if opts is not None else None,
+                                             C.byref(schedule) if schedule is not None else None, self._dict_handle(zdict),
+                                             data, len(data), out, bound, C.byref(out_len))
+        if rc:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return out.raw[:out_len.value]
+
+    def encode_batch_dict_device(self, fmt, zdict, d_in, in_offs, in_lens, d_out, out_offs, out_caps, opts=None, schedule=None):
+        """lfx_encode_batch_dict_device: the records d_in[in_offs[i], +in_lens[i]) as streams at d_out[out_offs[i], +out_caps[i]),
+        every one primed by the one Dictionary (None: lfx_encode_batch_device); the offsets and lengths are host-side lists
+        → (rc, [(status, out_len)] per stream); rc is LFX_OK or LFX_E_NOSPACE (the call is void, status says which streams did
+        not fit), anything else raises"""
+        k = len(in_offs)
+        a = lambda v: (C.c_uint64 * max(k, 1))(*v)
+        io, il, oo, oc = a(in_offs), a(in_lens), a(out_offs), a(out_caps)
+        out_len, st = (C.c_uint64 * max(k, 1))(), (C.c_int32 * max(k, 1))()
+        rc = _ffi.lib().lfx_encode_batch_dict_device(self._h, fmt, C.byref(opts) if opts is not None else None,
+                                                     C.byref(schedule) if schedule is not None else None, self._dict_handle(zdict),
+                                                     k, d_in, io, il, d_out, oo, oc, out_len, st)
+        if rc and rc != _ffi.E_NOSPACE:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return rc, [(st[i], out_len[i]) for i in range(k)]
+
 
 class Dictionary:
     """A preset dictionary (lfx_dict): what zlib.compressobj(zdict=...) was given.  The last 32 KiB are the

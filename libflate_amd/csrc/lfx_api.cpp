@@ -352,8 +352,24 @@ extern "C" int lfx_ctx_last_timing(lfx_ctx *cc, lfx_timing *t) try {
 
 // ------------------------------------------------------------------------------------------------
 // encode entry points: argument checks, the plan, then the encode core (lfx_encode.cpp)
-extern "C" int lfx_encode_device(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s,
-                                 const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len) try {
+// A preset dictionary in the container and in the plan.  zlib: FDICT set, FCHECK recomputed, DICTID behind
+// the two header bytes (RFC 1950 2.2); raw DEFLATE: nothing.
+static void dict_header(int format, const lfx_dict *dict, std::vector<uint8_t> &hdr) {
+    if (format != LFX_ZLIB || hdr.size() != 2) return;
+    uint8_t flg = (uint8_t)((hdr[1] & 0xC0) | 0x20);
+    const uint32_t check = ((uint32_t)hdr[0] << 8) + flg;
+    if (check % 31 != 0) flg = (uint8_t)(flg + (31 - check % 31));
+    hdr[1] = flg;
+    for (int sh = 24; sh >= 0; sh -= 8) hdr.push_back((uint8_t)(dict->id >> sh));
+}
+// the stream's first LZ77 flush unit is the one the dictionary primes — where the options match at all and the dictionary
+// has bytes to offer
+static void dict_prime(const lfx_dict *dict, Plan &p) {
+    if (dict->usable && !p.chunks.empty() && !(p.chunks[0].flags & CH_LITERALS)) p.chunks[0].flags |= CH_DICT;
+}
+
+static int encode_device_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
+                              const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len) {
     if (!cc) return LFX_E_DEVICE;
     Ctx *c = reinterpret_cast<Ctx *>(cc);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
@@ -366,12 +382,13 @@ extern "C" int lfx_encode_device(lfx_ctx *cc, int format, const lfx_encode_opts 
     Planner pl(po);
     apply_schedule(pl, s, n);
     Plan &plan = pl.finish();
+    if (dict) { dict_header(format, dict, hdr); dict_prime(dict, plan); }
     EncodeResult res{};
     const bool fill_ok = ((uintptr_t)d_out & 3) == 0 && cap >= 16;
     if (fill_ok) (void)hipSetDevice(c->device);
     c->prezero.start(d_out, fill_ok ? cap / 4 * 4 : 0);
     rc = with_match_fallback(c, res, [&]() -> int {
-        if (int rc2 = encode_prepare(c, plan, po, (const uint8_t *)d_in, n, ck_mode_of(format))) return rc2;
+        if (int rc2 = encode_prepare(c, plan, po, (const uint8_t *)d_in, n, ck_mode_of(format), nullptr, dict)) return rc2;
         return encode_emit(c, format, true, 0, true, n, hdr.data(), (uint32_t)hdr.size(), 8 * (uint64_t)hdr.size(),
                            (uint8_t *)d_out, cap, &res);
     });
@@ -381,15 +398,32 @@ extern "C" int lfx_encode_device(lfx_ctx *cc, int format, const lfx_encode_opts 
     // (an index build, lfx_encode_index_device: the candidates of the stream the last emit wrote, while its buffers hold it)
     if (c->idx_enc) return idx_encode_cand(c, plan);
     return LFX_OK;
+}
+extern "C" int lfx_encode_device(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s,
+                                 const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len) try {
+    return encode_device_impl(cc, format, o, s, nullptr, d_in, n, d_out, cap, out_len);
+} LFX_ABI_CATCH
+// ---- the dictionary calls: the same encode with the first chunk of the stream primed; without a dictionary,
+// the dictionary-less twin itself
+extern "C" uint64_t lfx_encode_dict_bound(uint64_t n, const lfx_encode_opts *o, const lfx_schedule *s) {
+    const uint64_t b = lfx_encode_bound(n, o, s);
+    return b ? b + 4 : 0;
+}
+extern "C" int lfx_encode_dict_device(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
+                                      const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len) try {
+    if (!cc) return LFX_E_DEVICE;
+    if (format != LFX_ZLIB && format != LFX_DEFLATE) return LFX_E_ARG;      // (gzip has no preset dictionary)
+    if (dict && dict->c != reinterpret_cast<Ctx *>(cc)) return LFX_E_ARG;
+    return encode_device_impl(cc, format, o, s, dict, d_in, n, d_out, cap, out_len);
 } LFX_ABI_CATCH
 
 // ---- batch encode: `count` independent streams in ONE launch set (thousands of small streams).
 // Every stream is what lfx_encode_device would make of its bytes alone (same options, the schedule applied to each
 // stream); the streams' chunks and blocks form one merged plan, so that the match / parse / Huffman / pack kernels see
 // thousands of chunks at once instead of one launch set per 64 KiB.
-extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s, uint32_t count,
-                                       const void *d_in, const uint64_t *in_off, const uint64_t *in_len, void *d_out,
-                                       const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status) try {
+static int encode_batch_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
+                             uint32_t count, const void *d_in, const uint64_t *in_off, const uint64_t *in_len, void *d_out,
+                             const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status) {
     if (!cc) return LFX_E_DEVICE;
     Ctx *c = reinterpret_cast<Ctx *>(cc);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
@@ -399,6 +433,7 @@ extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode
     if (rc) { c->set_error("option outside the reference's domain"); return rc; }
     std::vector<uint8_t> hdr;
     if ((rc = container_header(format, d, hdr))) { c->set_error("bad container options"); return rc; }
+    if (dict) dict_header(format, dict, hdr);
     if (!count) return LFX_OK;
     const PlanOpts po = plan_opts(format, d);
     // ---- the merged plan: every stream planned alone, its descriptors shifted into the shared index spaces
@@ -410,6 +445,7 @@ extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode
         Planner pl(po);
         apply_schedule(pl, s, in_len[i]);
         Plan &p = pl.finish();
+        if (dict) dict_prime(dict, p);
         streams[i] = BatchStream{in_off[i], in_len[i], out_off[i], out_cap[i], (uint32_t)plan.blocks.size(), (uint32_t)p.blocks.size()};
         plan.append(p, in_off[i]);
         in_extent = std::max(in_extent, in_off[i] + in_len[i]);
@@ -430,7 +466,7 @@ extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode
     std::vector<uint64_t> h_len;
     std::vector<int32_t> h_status;
     EncodeResult res{};
-    const BatchCall call{format, streams, hdr, (const uint8_t *)d_in, in_extent, (uint8_t *)d_out, out_lo, out_hi};
+    const BatchCall call{format, streams, hdr, (const uint8_t *)d_in, in_extent, (uint8_t *)d_out, out_lo, out_hi, dict};
     if ((rc = encode_batch(c, plan, po, call, h_len, h_status, res))) return rc;
     for (uint32_t i = 0; i < count; i++) {
         if (status) status[i] = res.status ? h_status[i] : LFX_OK;     // (a voided call: non-zero for exactly the streams that were too small)
@@ -441,6 +477,20 @@ extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode
         return LFX_E_NOSPACE;
     }
     return LFX_OK;
+}
+extern "C" int lfx_encode_batch_device(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s, uint32_t count,
+                                       const void *d_in, const uint64_t *in_off, const uint64_t *in_len, void *d_out,
+                                       const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status) try {
+    return encode_batch_impl(cc, format, o, s, nullptr, count, d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status);
+} LFX_ABI_CATCH
+extern "C" int lfx_encode_batch_dict_device(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s,
+                                            const lfx_dict *dict, uint32_t count, const void *d_in, const uint64_t *in_off,
+                                            const uint64_t *in_len, void *d_out, const uint64_t *out_off, const uint64_t *out_cap,
+                                            uint64_t *out_len, int32_t *status) try {
+    if (!cc) return LFX_E_DEVICE;
+    if (format != LFX_ZLIB && format != LFX_DEFLATE) return LFX_E_ARG;
+    if (dict && dict->c != reinterpret_cast<Ctx *>(cc)) return LFX_E_ARG;
+    return encode_batch_impl(cc, format, o, s, dict, count, d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status);
 } LFX_ABI_CATCH
 
 // A host variant: `in` staged into d_io_in, run(len) — the device entry point on d_io_in / d_io_out — and len bytes back.
@@ -471,6 +521,22 @@ extern "C" int lfx_encode_host(lfx_ctx *cc, int format, const lfx_encode_opts *o
     if (bound == 0) { c->set_error("option outside the reference's domain"); return LFX_E_ARG; }
     return encode_staged(c, in, n, bound, out, cap, out_len, [&](uint64_t &len) {
         return lfx_encode_device(cc, format, o, s, c->d_io_in.p, n, c->d_io_out.p, bound & ~3ull, &len);
+    });
+} LFX_ABI_CATCH
+
+extern "C" int lfx_encode_dict_host(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
+                                    const void *in, uint64_t n, void *out, uint64_t cap, uint64_t *out_len) try {
+    if (!cc) return LFX_E_DEVICE;
+    if (format != LFX_ZLIB && format != LFX_DEFLATE) return LFX_E_ARG;
+    if (!dict) return lfx_encode_host(cc, format, o, s, in, n, out, cap, out_len);
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    if (dict->c != c) return LFX_E_ARG;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    const uint64_t bound = lfx_encode_dict_bound(n, o, s);
+    if (bound == 0) { c->set_error("option outside the reference's domain"); return LFX_E_ARG; }
+    return encode_staged(c, in, n, bound, out, cap, out_len, [&](uint64_t &len) {
+        return lfx_encode_dict_device(cc, format, o, s, dict, c->d_io_in.p, n, c->d_io_out.p, bound & ~3ull, &len);
     });
 } LFX_ABI_CATCH
 

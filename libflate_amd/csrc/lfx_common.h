@@ -32,6 +32,8 @@ struct ChunkDesc {
 enum : uint32_t {
     CH_LAST_IN_BLOCK = 1,  // parse appends Symbol::EndOfBlock (encode.rs:417)
     CH_LITERALS = 2,       // NoCompressionLz77Encoder: every byte a literal (lib.rs:127-135)
+    CH_DICT = 4,           // a stream's first chunk in a call with a preset dictionary: its candidates and matches may reach
+                           // into the dictionary's tail; never set by a dictionary-less call
 };
 
 // One DEFLATE block (Block::flush, encode.rs:287-295)

@@ -8,6 +8,7 @@
 
 #include "lfx_common.h"
 #include "lfx_device.h"
+#include "lfx_dict_enc.h"
 #include <string.h>
 
 #include "lfx_hostio.h"
@@ -91,6 +92,10 @@ struct Ctx {
     // encode scratch
     DevBuf d_chunks, d_blocks, d_segs, d_pwgs, d_cd, d_md, d_codes, d_ncodes, d_hist, d_bc, d_block_start, d_tile_bits,
         d_tile_start, d_ck, d_res, d_small, d_hdr, d_io_in, d_io_out, d_vis, d_segtmp, d_stage, d_chunkmap, d_glnk, d_ucount;
+    // an encode with a preset dictionary: the work list of the dictionary candidate kernel, and its host copy
+    // (it outlives the asynchronous upload: every encode entry point synchronises before it returns)
+    DevBuf d_dict_items;
+    std::vector<DictItem> dict_items;
     // decode scratch
     // host shadows of the plan tables last uploaded (chunks, blocks, segments, parse workgroups) and the device buffers they
     // went to: an encode with the same plan (same size, schedule and options — every step of a loop) uploads nothing, and a
@@ -112,7 +117,7 @@ struct Ctx {
                 &d_tile_bits, &d_tile_start, &d_ck, &d_res, &d_small, &d_hdr, &d_io_in, &d_io_out, &d_vis, &d_segtmp, &d_stage, &d_chunkmap, &d_glnk, &d_ucount,
                 &d_dec_streams, &d_dec_state, &d_dec_tmp, &d_dec_cand, &d_dec_blocks, &d_dec_tabs, &d_dec_sym, &d_dec_win, &d_dec_maps,
                 &d_dec_temp, &d_dec_lanesx, &d_idx_tasks, &d_idx_probe, &d_idx_stage, &d_idx_enc,
-                &d_bgzf_meta, &d_bgzf_tasks, &d_bgzf_scratch, &d_bgzf_pack};
+                &d_bgzf_meta, &d_bgzf_tasks, &d_bgzf_scratch, &d_bgzf_pack, &d_dict_items};
     }
     void *h_res = nullptr;  // pinned, 4 KiB (+ the arena below)
     // Small transfers of the decode paths (job lists up, scan results and counters down) go through page-locked memory: a

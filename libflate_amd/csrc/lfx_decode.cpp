@@ -297,6 +297,7 @@ extern "C" void lfx_dict_free(lfx_dict *d) {
         (void)hipSetDevice(d->c->device);
         (void)hipStreamSynchronize(d->c->stream);
         (void)hipFree(d->d_win);
+        if (d->d_tab) (void)hipFree(d->d_tab);      // (the encode's prefix table)
     }
     delete d;
 }

@@ -60,7 +60,10 @@ int launch_parse(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Chu
                  uint32_t emit_parts = 0 /* ... and workgroups for the chunk of most segments (grid = nchunks x emit_parts) */,
                  hipEvent_t ev_walked = nullptr /* recorded behind the walk kernel (in front of the chaining kernels) */,
                  const uint32_t *mflags = nullptr /* EncodeResult::match_flags of this call (bit 1 picks the walk's instance) */,
-                 int start_at = 0 /* 1: the walk kernel has been launched (by a call with stop_after = 1): the chaining kernels only */);
+                 int start_at = 0 /* 1: the walk kernel has been launched (by a call with stop_after = 1): the chaining kernels only */,
+                 const uint8_t *dict_win = nullptr /* a preset dictionary's 32 KiB device window, its usable tail at the end: the
+                                                      dictionary instances of the walking kernels serve the CH_DICT chunks */,
+                 uint32_t dict_usable = 0);
 struct ZeroSpan { uint32_t *p; uint32_t n; };      // n words at p to be cleared (by the kernel that runs first anyway)
 int launch_chunk_maps(hipStream_t st, const ChunkDesc *chunks, uint32_t nchunks, uint64_t ntiles, uint32_t nsegs,
                       uint32_t *tile_map, uint32_t *seg_map, ZeroSpan z0 = ZeroSpan{nullptr, 0}, ZeroSpan z1 = ZeroSpan{nullptr, 0},

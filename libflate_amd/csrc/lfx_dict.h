@@ -1,4 +1,5 @@
-// lfx_dict.h — a preset dictionary (C ABI: lfx_dict_*) as the decode paths see it.  Internal.
+// lfx_dict.h — a preset dictionary (C ABI: lfx_dict_*) as the decode paths see it, and the prefix table the
+// encode paths add to it on their first use.  Internal.
 #pragma once
 #include <stdint.h>
 
@@ -17,5 +18,9 @@ struct lfx_dict {
     uint32_t usable = 0;
     uint8_t *d_win = nullptr;
     std::vector<uint8_t> tail;
+    // encode only: the prefix table of the tail (lfx_dict_enc.hip), built by the first encode call that takes this dictionary
+    // (under the context's lock) and kept; lfx_dict_new and the decode paths never touch it
+    mutable uint64_t *d_tab = nullptr;
+    mutable bool tab_built = false;
     const uint8_t *d_end() const { return d_win + lfx::MAX_WINDOW; }
 };

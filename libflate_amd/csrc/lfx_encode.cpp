@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "lfx_dict_enc.h"
 #include "lfx_encode_stages.h"
 
 namespace lfx {
@@ -59,6 +60,7 @@ struct EncCall {
     uint64_t n;
     int ck_mode;
     const HostCodes *hc;
+    const lfx_dict *dict;         // a preset dictionary with a usable tail, or nullptr
     bool match_v1;                // the first-generation match kernel: it once saw a lane-order violation (or LFX_MATCH_V1 is set)
     EncodeGeom g;
     uint64_t nspans = 0;          // partial results of the checksum kernels
@@ -99,7 +101,8 @@ int dbg_dump_seg(Ctx *c, const EncCall &k) {
     const uint32_t sg = (uint32_t)atoi(getenv("LFX_DUMP_SEG"));
     for (int stage_no = 1; stage_no <= 3 && sg < k.plan.n_segs; stage_no++) {
         LAUNCH_TRY(launch_parse(st, k.d_in, k.n, v.chunks, c->cur_nchunks, k.plan.n_segs, v.pwgs, (uint32_t)k.g.pwgs.size(), v.cd,
-                                k.po.max_length, v.vis, v.segtmp, v.codes, v.ncodes, v.stage, v.seg_map, stage_no % 3));
+                                k.po.max_length, v.vis, v.segtmp, v.codes, v.ncodes, v.stage, v.seg_map, stage_no % 3, nullptr, nullptr, 0, 0,
+                                nullptr, nullptr, 0, k.dict ? k.dict->d_win : nullptr, k.dict ? k.dict->usable : 0u));
         (void)hipStreamSynchronize(st);
         uint64_t vw[4];
         uint32_t t[6];
@@ -272,6 +275,31 @@ int stage_match(Ctx *c, const EncCall &k) {
     return LFX_OK;
 }
 
+// A call with a preset dictionary, behind the match stage whichever generation ran: the candidates it left
+// open among the first min(end, window_size) positions of every primed chunk are filled from the dictionary — its prefix table
+// is built here the first time the dictionary is used for an encode, and kept.  One launch for all primed chunks of the call.
+int stage_dict(Ctx *c, const EncCall &k) {
+    const lfx_dict *d = k.dict;
+    hipStream_t st = c->stream;
+    dict_items(k.plan.chunks, k.po.window_size, c->dict_items);
+    if (c->dict_items.empty()) return LFX_OK;
+    if (!d->d_tab) {
+        if (hipMalloc((void **)&d->d_tab, DICT_TAB_BYTES) != hipSuccess) { d->d_tab = nullptr; c->set_error("out of device memory"); return LFX_E_OOM; }
+        d->tab_built = false;
+    }
+    if (!d->tab_built) {
+        LAUNCH_TRY(launch_dict_table(st, d->d_win, d->usable, d->d_tab));
+        d->tab_built = true;
+    }
+    const size_t bytes = sizeof(DictItem) * c->dict_items.size();
+    if (int rc = c->d_dict_items.reserve(bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_dict_items.p, c->dict_items.data(), bytes, hipMemcpyHostToDevice, st));
+    LAUNCH_TRY(launch_dict_cand(st, k.d_in, k.v.chunks, (const DictItem *)c->d_dict_items.p, (uint32_t)c->dict_items.size(),
+                                k.po.window_size, d->d_end(), d->usable, d->d_tab, k.v.cd));
+    c->phase("lz77_dict");
+    return LFX_OK;
+}
+
 // the greedy walk → code words per chunk (and, fused_hist, the blocks' symbol counts); with a checksum the first half of its
 // sweep goes to the side stream from behind the walk kernel on
 int stage_parse(Ctx *c, EncCall &k) {
@@ -285,7 +313,8 @@ int stage_parse(Ctx *c, EncCall &k) {
         LAUNCH_TRY(launch_parse(st, k.d_in, k.n, v.chunks, c->cur_nchunks, k.plan.n_segs, v.pwgs, (uint32_t)k.g.pwgs.size(), v.cd,
                                 k.po.max_length, v.vis, v.segtmp, v.codes, v.ncodes, v.stage, v.seg_map, part == 1 ? 1 : 0,
                                 v.mdbg ? v.mdbg + 256 : nullptr, k.g.fused_hist ? v.hist : nullptr, k.g.emit_per, k.g.emit_parts,
-                                want_checksum ? c->ev_fork : nullptr, v.d_match_flags, part == 2 ? 1 : 0));
+                                want_checksum ? c->ev_fork : nullptr, v.d_match_flags, part == 2 ? 1 : 0,
+                                k.dict ? k.dict->d_win : nullptr, k.dict ? k.dict->usable : 0u));
         if (part == 1) c->phase("lz77_walk");
     }
     if (want_checksum) {
@@ -331,11 +360,12 @@ int stage_huffman(Ctx *c, const EncCall &k) {
 
 }  // namespace
 
-int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *d_in, uint64_t n, int ck_mode, const HostCodes *hc) {
+int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *d_in, uint64_t n, int ck_mode, const HostCodes *hc,
+                   const lfx_dict *dict) {
     (void)hipSetDevice(c->device);
     c->n_ev = 0;
     c->phase("start");
-    EncCall k{plan, po, d_in, n, ck_mode, hc, c->force_match_v1 || c->diag.match_v1,
+    EncCall k{plan, po, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
               encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
     if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)
@@ -349,7 +379,11 @@ int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *
     if ((rc = upload_tables(c, k))) return rc;
     if ((rc = chunk_maps(c, k))) return rc;
     if (hc) rc = upload_codes(c, k);
-    else if (!(rc = stage_match(c, k))) rc = stage_parse(c, k);
+    else {
+        rc = stage_match(c, k);
+        if (!rc && k.dict) rc = stage_dict(c, k);
+        if (!rc) rc = stage_parse(c, k);
+    }
     if (rc) return rc;
     if (ck_mode && (rc = checksum_fork(c, k))) return rc;
     if ((rc = stage_huffman(c, k))) return rc;
@@ -428,7 +462,7 @@ int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &
     h_len.resize(count);
     h_status.resize(count);
     return with_match_fallback(c, res, [&]() -> int {
-        if (int rc = encode_prepare(c, plan, po, b.d_in, b.in_extent, 0)) return rc;
+        if (int rc = encode_prepare(c, plan, po, b.d_in, b.in_extent, 0, nullptr, b.dict)) return rc;
         HIP_TRY(hipMemcpyAsync(d_streams, b.streams.data(), sz_streams, hipMemcpyHostToDevice, st));
         if (!b.hdr.empty()) HIP_TRY(hipMemcpyAsync(d_hdr, b.hdr.data(), b.hdr.size(), hipMemcpyHostToDevice, st));
         if (trailer)

@@ -5,6 +5,7 @@
 
 #include "lfx_ctx.h"
 #include "lfx_device.h"
+#include "lfx_dict.h"
 #include "lfx_plan.h"
 #include "lfx_try.h"
 #include "lfx_verdict.h"
@@ -20,8 +21,10 @@ struct HostCodes {
 
 // Stage A: plan upload → match → parse → histogram → Huffman (+ checksum: ck_mode 1 CRC-32, 2 Adler-32, 3 both — a shard, whose
 // caller folds either).  Leaves everything the emit stage needs in the context.
+// dict: a preset dictionary — the plan's CH_DICT chunks take their open candidates from it and the parse reads
+// its window; nullptr: the kernels and launches of a dictionary-less call, unchanged.
 int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *d_in, uint64_t n, int ck_mode,
-                   const HostCodes *hc = nullptr);
+                   const HostCodes *hc = nullptr, const lfx_dict *dict = nullptr);
 // Stage B: offsets → pack → framing.  `prefix` bytes are placed at the start of d_out; the DEFLATE bits start at bit
 // `start_bit` of d_out (prefix may end with a partial byte).
 // async_slot (page-locked, the caller's own): the result is copied there and the call returns WITHOUT waiting — the stream
@@ -57,6 +60,7 @@ struct BatchCall {
     uint64_t in_extent;
     uint8_t *d_out;
     uint64_t out_lo, out_hi;      // the span of d_out the streams' ranges lie in
+    const lfx_dict *dict = nullptr;   // lfx_encode_batch_dict_device: primes every stream's first chunk
 };
 int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &b, std::vector<uint64_t> &h_len,
                  std::vector<int32_t> &h_status, EncodeResult &res);

@@ -79,6 +79,30 @@ __device__ __forceinline__ ByteSrcG make_src(const uint8_t *p, uint64_t n) {
     s.nbytes = n;
     return s;
 }
+// The bytes of a chunk that a preset dictionary primes (CH_DICT): offsets in front of the chunk's first byte
+// — as the unsigned wrap of pos + 3 - d leaves them — are bytes of the dictionary's tail, counted back from dict_end.  A match
+// may start there and run on into the chunk.  The dictionary instances of the chaining kernels read through this; a chunk
+// that is not primed never asks for such an offset.
+struct ByteSrcD {
+    ByteSrcG g;
+    const uint8_t *dict_end;
+    __device__ __forceinline__ uint32_t load4(uint64_t off) const {
+        if ((int64_t)off >= 0) return g.load4(off);
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {                                  // (at most 32 KiB in front: a handful of steps per segment)
+            const int64_t o = (int64_t)off + k;
+            const uint32_t b = o < 0 ? dict_end[o] : ((uint64_t)o < g.nbytes ? g.load1((uint64_t)o) : 0u);
+            v |= b << (8 * k);
+        }
+        return v;
+    }
+    __device__ __forceinline__ uint32_t load1(uint64_t off) const { return g.load1(off); }
+};
+template <bool DICT> struct SrcOf { typedef ByteSrcG type; };
+template <> struct SrcOf<true> { typedef ByteSrcD type; };
+__device__ __forceinline__ ByteSrcG src_for(const ByteSrcG &g, ByteSrcG *) { return g; }
+__device__ __forceinline__ ByteSrcD src_for(const ByteSrcG &g, const uint8_t *dict_end, ByteSrcD *) { return ByteSrcD{g, dict_end}; }
 
 __device__ __forceinline__ uint64_t lanemask_lt() {
     const uint32_t lane = __lane_id();
@@ -297,12 +321,15 @@ struct WalkSlot {
     uint32_t n, end, g0, w0, sh, csh;
     p2::gptr_x4 gw, gc;       // first 16-byte unit of the bytes / of the candidates
     uint32_t lastw, lastc;    // last unit that may be read
+    uint32_t lbase;           // dictionary instance: first LDS unit of the bytes (MAX_WINDOW / 16 for the first workgroup of a primed chunk)
 };
+template <bool DICT>
 __device__ __forceinline__ WalkSlot walk_slot(uint32_t slot, uint32_t nwgs, const uint8_t *in, uint64_t in_bytes,
                                               const ChunkDesc *chunks, const ParseWg *wgs, const uint16_t *cd) {
     using namespace p2;
     WalkSlot q;
     q.kind = 0;
+    q.lbase = 0;
     if (slot >= nwgs) return q;
     q.wg = wgs[slot];
     if (q.wg.chunk == 0xFFFFFFFFu) return q;          // an empty slot of the XCD-aware order (lfx_api.cpp)
@@ -327,6 +354,14 @@ __device__ __forceinline__ WalkSlot walk_slot(uint32_t slot, uint32_t nwgs, cons
     q.lastw = (uint32_t)(want < have ? want : have) - 1;                                 // (>= 1 unit here)
     q.gc = (gptr_x4)(cd + (e0 - q.csh));
     q.lastc = ((min(WG_POS, q.end - q.g0) + q.csh + 7) >> 3) - 1;
+    if (DICT && (q.ch.flags & CH_DICT) && q.g0 == 0) {
+        // The first workgroup of a primed chunk (WG_POS > MAX_WINDOW: no other one reaches the dictionary): the chunk's bytes
+        // are staged MAX_WINDOW further up, the dictionary's window in front of them — LDS byte sh + MAX_WINDOW is position 0,
+        // the window start takes the part of a (wrapped) position -MAX_WINDOW.  The room is that of a workgroup with a full
+        // window of its own chunk in front.
+        q.lbase = MAX_WINDOW / 16;
+        q.w0 = 0u - MAX_WINDOW;
+    }
     return q;
 }
 
@@ -500,13 +535,41 @@ __device__ __forceinline__ void walk_segment(const WalkSlot &q, uint32_t max_len
     if (DBG && stamps && lane == 0) { stamps[1] = t2 - t1; stamps[2] = t3 - t2; stamps[3] = clock64() - t3; }
 }
 
-template <bool DBG>
+// A preset dictionary's window: the one extra argument of the dictionary instances (a parameter pack that is empty for the
+// instances a dictionary-less call launches, whose parameter lists stay what they were)
+struct WalkDict {
+    const uint8_t *win;       // lfx_dict::d_win: MAX_WINDOW bytes, the usable tail at their end
+    uint32_t usable;
+};
+// The dictionary's tail into LDS bytes [sh + MAX_WINDOW - usable, sh + MAX_WINDOW), right in front of position 0 of a primed
+// chunk (walk_slot): whole dwords through aligned loads, the up to three bytes at either edge one by one.  Runs behind the
+// barrier that follows the stores of the chunk's own 16-byte units — the unit that holds position 0 also holds sh bytes from
+// in front of the chunk, which the tail overwrites — and in front of a barrier of its own.
+__device__ __forceinline__ void fill_dict(uint32_t sh, uint32_t *win32, uint32_t tid, const WalkDict &wd) {
+    using namespace p2;
+    const uint32_t hi = sh + MAX_WINDOW, lo = hi - wd.usable;
+    const uint32_t d0 = (lo + 3) >> 2, d1 = hi >> 2;
+    const ByteSrcG ds = make_src(wd.win, MAX_WINDOW);
+    for (uint32_t D = d0 + tid; D < d1; D += THREADS) win32[D] = ds.load4((uint64_t)(4 * D - sh));
+    uint8_t *win8 = (uint8_t *)win32;
+    if (tid < 4) {
+        const uint32_t x = lo + tid;                                  // head: [lo, 4 * d0)
+        if (x < hi && x < 4 * d0) win8[x] = wd.win[x - sh];
+    } else if (tid < 8 && d1 >= d0) {
+        const uint32_t x = 4 * d1 + (tid - 4);                        // tail: [4 * d1, hi)
+        if (x >= lo && x < hi) win8[x] = wd.win[x - sh];
+    }
+}
+__device__ __forceinline__ void fill_dict(uint32_t, uint32_t *, uint32_t) {}
+
+template <bool DBG, class... WD>
 __global__ __launch_bounds__(p2::THREADS) void parse_walk_kernel(
     const uint8_t *__restrict__ in, uint64_t in_bytes, const ChunkDesc *__restrict__ chunks,
     const ParseWg *__restrict__ wgs, uint32_t nwgs, const uint16_t *__restrict__ cd, uint32_t max_len,
     uint64_t *__restrict__ vis, uint32_t *__restrict__ seg_exit, uint32_t *__restrict__ seg_count,
-    uint32_t *__restrict__ stage, const uint32_t *__restrict__ mflags, uint64_t *__restrict__ dbg) {
+    uint32_t *__restrict__ stage, const uint32_t *__restrict__ mflags, uint64_t *__restrict__ dbg, WD... wd) {
     using namespace p2;
+    constexpr bool DICT = sizeof...(WD) != 0;
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
     // (bit 1 of the match stage's flags: a segment of this call held runs of equal bytes — lfx_match7.hip's sample)
     const bool coop = mflags && (*mflags & 2u);
@@ -517,7 +580,7 @@ __global__ __launch_bounds__(p2::THREADS) void parse_walk_kernel(
     const uint32_t dbg_slot = nwgs > 1000 ? 1000u : 0u;          // (a workgroup in the middle of the launch)
 
     uint32_t slot = blockIdx.x;
-    WalkSlot q = walk_slot(slot, nwgs, in, in_bytes, chunks, wgs, cd);
+    WalkSlot q = walk_slot<DICT>(slot, nwgs, in, in_bytes, chunks, wgs, cd);
     u32x4 wv[WQ], cv[CQ];
     // (branch-free: indices past the end are clamped to the last unit — a few redundant loads and stores of the same value)
     if (q.kind == 2) {
@@ -530,14 +593,18 @@ __global__ __launch_bounds__(p2::THREADS) void parse_walk_kernel(
         const uint64_t t0 = DBG ? clock64() : 0;
         // (the next slot's descriptors — two dependent scalar loads — are fetched beside the LDS stores)
         const uint32_t nslot = slot + gridDim.x;
-        const WalkSlot qn = walk_slot(nslot, nwgs, in, in_bytes, chunks, wgs, cd);
+        const WalkSlot qn = walk_slot<DICT>(nslot, nwgs, in, in_bytes, chunks, wgs, cd);
         if (q.kind == 2) {
 #pragma unroll
             for (uint32_t k = 0; k < CQ; ++k) cdx[min(k * THREADS + tid, q.lastc)] = cv[k];
 #pragma unroll
-            for (uint32_t k = 0; k < WQ; ++k) winx[min(k * THREADS + tid, q.lastw)] = wv[k];
+            for (uint32_t k = 0; k < WQ; ++k) winx[(DICT ? q.lbase : 0u) + min(k * THREADS + tid, q.lastw)] = wv[k];
         }
         __syncthreads();
+        if (DICT && q.kind == 2 && q.lbase) {        // (uniform) the dictionary's tail in front of a primed chunk
+            fill_dict(q.sh, win32, tid, wd...);
+            __syncthreads();
+        }
         // the next slot's loads: in flight while this one is walked
         if (qn.kind == 2) {
 #pragma unroll
@@ -570,12 +637,15 @@ constexpr uint32_t PARSE_HIST_STRIDE = 320;      // a block's symbol counters: [
 // ------------------------------------------------------------------------------------------------
 // Walk steps out of global memory, one at a time, by a whole wavefront (the chaining kernels: a handful of steps per
 // segment).  Lane k compares bytes [4k, 4k+4) behind the prefix: one round settles a whole match.
-struct GWalk {
-    p2::ByteSrcG src;
+template <class SRC>
+struct GWalkT {
+    SRC src;                 // p2::ByteSrcG; the dictionary instances: p2::ByteSrcD
     const uint16_t *cd;      // this chunk's candidates
     uint32_t n, max_len;
 };
-__device__ __forceinline__ uint32_t gwalk_step(const GWalk &g, uint32_t pos, uint32_t lane) {
+typedef GWalkT<p2::ByteSrcG> GWalk;
+template <class SRC>
+__device__ __forceinline__ uint32_t gwalk_step(const GWalkT<SRC> &g, uint32_t pos, uint32_t lane) {
     const uint32_t d = g.cd[pos];                                    // (uniform address)
     if (d == 0) return 1;
     uint32_t lim = g.n - (pos + 3);
@@ -599,7 +669,8 @@ __device__ __forceinline__ uint32_t gwalk_step(const GWalk &g, uint32_t pos, uin
 // from the entry until the walk lands on a position the speculative walk visited — from there on both
 // coincide — and rewrite the visited masks, the count and the exit of the segment accordingly.
 struct SegFix { uint32_t cnt, ex, mpos, kspec; };   // codes, exit; merge position, staged codes in front of it
-__device__ __forceinline__ SegFix parse_rewalk(const GWalk &gw, uint64_t *__restrict__ vw, uint32_t s0, uint32_t s1,
+template <class SRC>
+__device__ __forceinline__ SegFix parse_rewalk(const GWalkT<SRC> &gw, uint64_t *__restrict__ vw, uint32_t s0, uint32_t s1,
                                                uint32_t e, uint32_t cnt, uint32_t ex, uint32_t lane) {
     using p2::U;
     uint32_t pos = e, walked = 0, spec_below = 0, merge_pos = s1;
@@ -638,6 +709,7 @@ __device__ __forceinline__ SegFix parse_rewalk(const GWalk &gw, uint64_t *__rest
     return f;
 }
 
+template <class... DE>      // (DE: empty, or the dictionary instance's `const uint8_t *dict_end`)
 __global__ __launch_bounds__(64) void parse_fixseg_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes,
                                                           const ChunkDesc *__restrict__ chunks,
                                                           const uint16_t *__restrict__ cd, uint32_t max_len,
@@ -647,7 +719,8 @@ __global__ __launch_bounds__(64) void parse_fixseg_kernel(const uint8_t *__restr
                                                           uint32_t *__restrict__ seg_exit2,
                                                           uint32_t *__restrict__ seg_mpos,
                                                           uint32_t *__restrict__ seg_kspec,
-                                                          const uint32_t *__restrict__ seg_map) {
+                                                          const uint32_t *__restrict__ seg_map, DE... dict_end) {
+    typedef typename p2::SrcOf<sizeof...(DE) != 0>::type Src;
     const uint32_t seg = blockIdx.x;
     const ChunkDesc ch = chunks[seg_map[seg]];
     if (ch.flags & CH_LITERALS) return;
@@ -660,7 +733,7 @@ __global__ __launch_bounds__(64) void parse_fixseg_kernel(const uint8_t *__restr
     SegFix f{seg_count[seg], seg_exit[seg], s0, 0u};                 // (entered where assumed: every staged code is final)
     if (s0 >= end) { f.cnt = 0; f.ex = e; }                          // behind the last walked position: pass through
     else if (e != s0) {
-        GWalk gw{p2::make_src(in + ch.in_off, in_bytes - ch.in_off), cd + ch.in_off, n, max_len};
+        GWalkT<Src> gw{p2::src_for(p2::make_src(in + ch.in_off, in_bytes - ch.in_off), dict_end..., (Src *)nullptr), cd + ch.in_off, n, max_len};
         f = parse_rewalk(gw, vis + ch.vis_base + (uint64_t)s * 64, s0, s1, e, f.cnt, f.ex, lane);
     }
     if (lane == 0) { seg_count[seg] = f.cnt; seg_exit2[seg] = f.ex; seg_mpos[seg] = f.mpos; seg_kspec[seg] = f.kspec; }
@@ -671,6 +744,7 @@ __global__ __launch_bounds__(64) void parse_fixseg_kernel(const uint8_t *__restr
 // the counts into offsets; then the chunk's tail and the EndOfBlock marker.
 // 64 lanes when a chunk has a few dozen segments (the reference's 256 KiB chunks), 1024 when one chunk is the whole input
 // (schedule S1: 80 K segments per 256 MiB).
+template <class... DE>
 __global__ __launch_bounds__(1024) void parse_fix_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes,
                                                          const ChunkDesc *__restrict__ chunks,
                                                          const uint16_t *__restrict__ cd, uint32_t max_len,
@@ -680,7 +754,8 @@ __global__ __launch_bounds__(1024) void parse_fix_kernel(const uint8_t *__restri
                                                          uint32_t *__restrict__ seg_exit2,
                                                          uint32_t *__restrict__ seg_off, uint32_t *__restrict__ codes,
                                                          uint32_t *__restrict__ ncodes, uint32_t *__restrict__ seg_mpos,
-                                                         uint32_t *__restrict__ hist) {
+                                                         uint32_t *__restrict__ hist, DE... dict_end) {
+    typedef typename p2::SrcOf<sizeof...(DE) != 0>::type Src;
     __shared__ uint32_t s_first_bad, s_wsum[16], s_redo[2];
     const ChunkDesc ch = chunks[blockIdx.x];
     const uint32_t tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = T >> 6;
@@ -731,7 +806,7 @@ __global__ __launch_bounds__(1024) void parse_fix_kernel(const uint8_t *__restri
                     SegFix f{sc[sb], sx2[sb], 0u, 0u};
                     if (s0 >= end) { f.cnt = 0; f.ex = e_last; }
                     else {
-                        GWalk gw{src, cd + ch.in_off, n, max_len};
+                        GWalkT<Src> gw{p2::src_for(src, dict_end..., (Src *)nullptr), cd + ch.in_off, n, max_len};
                         f = parse_rewalk(gw, vis + ch.vis_base + (uint64_t)sb * 64, s0, s1, e_last, f.cnt, f.ex, lane);
                     }
                     // (walked a second time: the staged codes no longer line up with the visit bits — emit all of this
@@ -967,8 +1042,12 @@ int launch_parse(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Chu
                  uint32_t nsegs, const ParseWg *wgs, uint32_t nwgs, const uint16_t *cd, uint32_t max_len, uint64_t *vis,
                  uint32_t *seg_tmp, uint32_t *codes, uint32_t *ncodes, uint32_t *stage, const uint32_t *seg_map, int stop_after,
                  uint64_t *dbg, uint32_t *hist, uint32_t emit_per, uint32_t emit_parts, hipEvent_t ev_walked, const uint32_t *mflags,
-                 int start_at) {
+                 int start_at, const uint8_t *dict_win, uint32_t dict_usable) {
     if (nchunks == 0) return 0;
+    // (a call with a preset dictionary — dict_win: its 32 KiB device window — launches the dictionary instances of the walk and
+    //  of the two chaining kernels that walk; every other call the instances it always launched)
+    const WalkDict wd{dict_win, dict_usable};
+    const uint8_t *dict_end = dict_win ? dict_win + MAX_WINDOW : nullptr;
     // seg_tmp: six arrays of nsegs words
     uint32_t *seg_exit = seg_tmp, *seg_count = seg_tmp + nsegs, *seg_off = seg_tmp + 2 * (size_t)nsegs;
     uint32_t *seg_exit2 = seg_tmp + 3 * (size_t)nsegs, *seg_mpos = seg_tmp + 4 * (size_t)nsegs;
@@ -976,7 +1055,13 @@ int launch_parse(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Chu
     if (nwgs && start_at < 1) {
         // persistent: one workgroup per CU (153 KB of LDS), every grid-th slot; the grid a multiple of 8 so that a slot keeps its XCD
         const uint32_t grid = std::min<uint32_t>((nwgs + 7) & ~7u, walk_grid());
-        if (dbg)
+        if (dict_win && dbg)
+            hipLaunchKernelGGL((parse_walk_kernel<true, WalkDict>), dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd,
+                               max_len, vis, seg_exit, seg_count, stage, mflags, dbg, wd);
+        else if (dict_win)
+            hipLaunchKernelGGL((parse_walk_kernel<false, WalkDict>), dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd,
+                               max_len, vis, seg_exit, seg_count, stage, mflags, dbg, wd);
+        else if (dbg)
             hipLaunchKernelGGL(parse_walk_kernel<true>, dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd, max_len,
                                vis, seg_exit, seg_count, stage, mflags, dbg);
         else
@@ -989,15 +1074,23 @@ int launch_parse(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Chu
     if (start_at < 1 && ev_walked && hipEventRecord(ev_walked, st) != hipSuccess) return (int)hipGetLastError();
     if (stop_after == 1) return 0;      // (LFX_DEBUG dumps; the walk's own bracket of the fine phase timing)
     if (nsegs) {
-        hipLaunchKernelGGL(parse_fixseg_kernel, dim3(nsegs), dim3(64), 0, st, in, in_bytes, chunks, cd, max_len, vis, seg_exit,
-                           seg_count, seg_exit2, seg_mpos, seg_kspec, seg_map);
+        if (dict_win)
+            hipLaunchKernelGGL(parse_fixseg_kernel<const uint8_t *>, dim3(nsegs), dim3(64), 0, st, in, in_bytes, chunks, cd, max_len, vis,
+                               seg_exit, seg_count, seg_exit2, seg_mpos, seg_kspec, seg_map, dict_end);
+        else
+            hipLaunchKernelGGL(parse_fixseg_kernel<>, dim3(nsegs), dim3(64), 0, st, in, in_bytes, chunks, cd, max_len, vis, seg_exit,
+                               seg_count, seg_exit2, seg_mpos, seg_kspec, seg_map);
         LFX_LAUNCH_CHECK();
     }
     if (stop_after == 2) return 0;
     // (workgroup size by the segments per chunk: the fold over a chunk's segments is serial in batches of that size)
     const uint32_t fix_threads = nsegs / nchunks > 128 ? 1024u : 64u;
-    hipLaunchKernelGGL(parse_fix_kernel, dim3(nchunks), dim3(fix_threads), 0, st, in, in_bytes, chunks, cd, max_len, vis,
-                       seg_exit, seg_count, seg_exit2, seg_off, codes, ncodes, seg_mpos, hist);
+    if (dict_win)
+        hipLaunchKernelGGL(parse_fix_kernel<const uint8_t *>, dim3(nchunks), dim3(fix_threads), 0, st, in, in_bytes, chunks, cd, max_len,
+                           vis, seg_exit, seg_count, seg_exit2, seg_off, codes, ncodes, seg_mpos, hist, dict_end);
+    else
+        hipLaunchKernelGGL(parse_fix_kernel<>, dim3(nchunks), dim3(fix_threads), 0, st, in, in_bytes, chunks, cd, max_len, vis,
+                           seg_exit, seg_count, seg_exit2, seg_off, codes, ncodes, seg_mpos, hist);
     LFX_LAUNCH_CHECK();
     if (nsegs && hist) {
         // (the caller sizes the grid: emit_per segments per workgroup, emit_parts = the longest chunk's workgroups)

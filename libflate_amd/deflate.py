@@ -62,6 +62,28 @@ class Encoder(_EncoderBase):
         return cls(inner, options, context)
 
 
+def _compress(fmt, data, zdict, options, context):
+    from .context import Dictionary, default_context
+    ctx = context if context is not None else default_context()
+    opts = options._to_c() if options is not None else None
+    if zdict is None:
+        return ctx.encode_host(fmt, data, opts)
+    own = not hasattr(zdict, "handle")
+    d = Dictionary(zdict, ctx) if own else zdict
+    try:
+        return ctx.encode_dict_host(fmt, d, data, opts)
+    finally:
+        if own:
+            d.close()
+
+
+def compress(data, zdict=None, options=None, context=None):
+    """`data` as one raw DEFLATE stream, encoded in one call (one write_all + finish).  zdict: a preset dictionary, bytes or a
+    libflate_amd.Dictionary — the stream then starts with the dictionary as history, what
+    zlib.decompressobj(wbits=-15, zdict=...) reads (lfx_encode_dict_host)."""
+    return _compress(_ffi.DEFLATE, data, zdict, options, context)
+
+
 class Decoder(_DecoderBase):
     """deflate::Decoder (decode.rs:8-164)."""
     FORMAT = _ffi.DEFLATE

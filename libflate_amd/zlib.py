@@ -30,6 +30,13 @@ class Encoder(_EncoderBase):
         return cls(inner, options, context)
 
 
+def compress(data, zdict=None, options=None, context=None):
+    """`data` as one zlib stream, encoded in one call (one write_all + finish).  zdict: a preset dictionary, bytes or a
+    libflate_amd.Dictionary — the stream then carries FDICT and the dictionary's id, what zlib.decompressobj(zdict=...)
+    reads (lfx_encode_dict_host)."""
+    return _deflate._compress(_ffi.ZLIB, data, zdict, options, context)
+
+
 class Decoder(_DecoderBase):
     """zlib::Decoder (zlib.rs:284-410)."""
     FORMAT = _ffi.ZLIB
