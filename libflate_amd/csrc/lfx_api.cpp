@@ -1,5 +1,6 @@
-// lfx_api.cpp — C ABI (include/lfx.h) over the HIP kernels.  Host side = framing bytes, the write
-// schedule planner and kernel orchestration; every byte of compression work runs on the GPU.
+// lfx_api.cpp — C ABI (include/lfx.h) over the HIP kernels: the context, the one-shot / batch / members / sharded encode entry
+// points, the Lz77Encode plug-in and the test hooks.  (The stream encoder: lfx_stream_enc.cpp; the decoders: lfx_decode.cpp,
+// lfx_stream_dec.cpp.)  Every byte of compression work runs on the GPU.
 #include "../../include/lfx.h"
 #include "../../include/lfx_testhooks.h"
 
@@ -16,6 +17,7 @@
 
 #include "lfx_ctx.h"
 #include "lfx_device.h"
+#include "lfx_enc_frame.h"
 #include "lfx_encode_int.h"
 #include "lfx_huff.h"
 #include "lfx_index.h"
@@ -25,137 +27,12 @@
 using namespace lfx;
 
 // ------------------------------------------------------------------------------------------------
-// small host helpers (framing only)
-static uint32_t host_crc32(const uint8_t *p, size_t n) {
-    static uint32_t tab[256];
-    static std::once_flag once;
-    std::call_once(once, [] {
-        for (uint32_t i = 0; i < 256; i++) {
-            uint32_t c = i;
-            for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1)));
-            tab[i] = c;
-        }
-    });
-    uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < n; i++) c = (c >> 8) ^ tab[(c ^ p[i]) & 0xFF];
-    return ~c;
-}
-static uint32_t gf2_mulmod(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & 0x80000000u) p ^= b;
-        a <<= 1;
-        b = (b >> 1) ^ (0xEDB88320u & (0u - (b & 1)));
-    }
-    return p;
-}
-static uint32_t gf2_xpow8n(uint64_t nbytes) {
-    uint32_t r = 0x80000000u, sq = 0x00800000u;
-    while (nbytes) {
-        if (nbytes & 1) r = gf2_mulmod(r, sq);
-        sq = gf2_mulmod(sq, sq);
-        nbytes >>= 1;
-    }
-    return r;
-}
-
-extern "C" uint32_t lfx_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
-    // CRC(A||B) from CRC(A), CRC(B), |B| (the reference never combines)
-    return gf2_mulmod(crc1, gf2_xpow8n(len2)) ^ crc2;
-}
-extern "C" uint32_t lfx_adler32_combine(uint32_t ad1, uint32_t ad2, uint64_t len2) {
-    const uint32_t M = 65521u;
-    uint32_t a1 = ad1 & 0xFFFF, b1 = ad1 >> 16, a2 = ad2 & 0xFFFF, b2 = ad2 >> 16;
-    uint32_t rem = (uint32_t)(len2 % M);
-    uint32_t a = (a1 + a2 + M - 1) % M;
-    uint32_t b = (uint32_t)((b1 + b2 + (uint64_t)rem * ((a1 + M - 1) % M)) % M);
-    return (b << 16) | a;
-}
-
-extern "C" void lfx_encode_opts_default(lfx_encode_opts *o) {
-    memset(o, 0, sizeof *o);
-    o->block_size = 1u << 20;
-    o->dynamic_huffman = 1;
-    o->window_size = MAX_WINDOW;
-    o->max_length = MAX_LENGTH;
-    o->os = 3;
-}
+// the framing helpers' C ABI (the helpers themselves: lfx_enc_frame.h)
+extern "C" uint32_t lfx_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) { return crc32_combine(crc1, crc2, len2); }
+extern "C" uint32_t lfx_adler32_combine(uint32_t ad1, uint32_t ad2, uint64_t len2) { return adler32_combine(ad1, ad2, len2); }
+extern "C" void lfx_encode_opts_default(lfx_encode_opts *o) { encode_opts_default(o); }
 extern "C" uint32_t lfx_version(void) { return LFX_VERSION; }
 
-static lfx_encode_opts norm_opts(const lfx_encode_opts *o) {
-    lfx_encode_opts d;
-    if (o) d = *o; else lfx_encode_opts_default(&d);
-    if (d.window_size > MAX_WINDOW) d.window_size = MAX_WINDOW;  // default.rs:228
-    if (d.max_length > MAX_LENGTH) d.max_length = MAX_LENGTH;    // default.rs:240
-    return d;
-}
-static int check_opts(const lfx_encode_opts &o) {
-    if (o.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
-    if (o.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
-    return LFX_OK;
-}
-static PlanOpts plan_opts(int format, const lfx_encode_opts &o) {
-    PlanOpts p;
-    p.block_size = o.block_size;
-    p.dynamic_huffman = o.dynamic_huffman != 0;
-    p.no_compression = o.no_compression != 0;
-    p.lz77_kind = o.lz77_kind;
-    p.window_size = o.window_size;
-    p.max_length = o.max_length;
-    p.zlib_sync = format == LFX_ZLIB && o.zlib_flush_mode == LFX_FLUSH_SYNC;
-    return p;
-}
-
-// gzip Header::write_to gzip.rs:368-389 (+flags 343-355, crc16 356-367)
-static void gzip_header(const lfx_encode_opts &o, bool with_hcrc, std::vector<uint8_t> &b) {
-    uint8_t flg = (uint8_t)((o.is_text ? 1 : 0) | (with_hcrc ? 2 : 0) | (o.extra ? 4 : 0) |
-                            (o.filename ? 8 : 0) | (o.comment ? 16 : 0));
-    // XFL is the level of the header the options hold when the encoder is made (gzip.rs:368-389): DefaultLz77Encoder →
-    // Balance → Unknown(0); NoCompression → None → Unknown(0); a caller's E: Fast → Fastest(4), Best → Slowest(2)
-    // (gzip.rs:84-92,684).  no_compression() resets it to Unknown WHEN IT IS CALLED (gzip.rs:703) and a later header(h)
-    // replaces it again (gzip.rs:717-720): the option builders above this ABI apply both in call order and pass the result in
-    // lz77_level — it is not overridden here (no_compression().header(h with Fastest) writes XFL 4).
-    const uint8_t xfl = o.lz77_level == 1 + LFX_LEVEL_FAST ? 4 : o.lz77_level == 1 + LFX_LEVEL_BEST ? 2 : 0;
-    const uint8_t h[10] = {31, 139, 8, flg, (uint8_t)o.mtime, (uint8_t)(o.mtime >> 8),
-                           (uint8_t)(o.mtime >> 16), (uint8_t)(o.mtime >> 24), xfl, o.os};
-    b.insert(b.end(), h, h + 10);
-    if (o.extra) {
-        b.push_back((uint8_t)o.extra_len);
-        b.push_back((uint8_t)(o.extra_len >> 8));
-        b.insert(b.end(), o.extra, o.extra + o.extra_len);
-    }
-    if (o.filename) b.insert(b.end(), o.filename, o.filename + strlen(o.filename) + 1);
-    if (o.comment) b.insert(b.end(), o.comment, o.comment + strlen(o.comment) + 1);
-    if (with_hcrc) {
-        // the reference checksums the header serialised with is_verified = false (FLG.HCRC clear)
-        std::vector<uint8_t> t;
-        gzip_header(o, false, t);
-        uint32_t c = host_crc32(t.data(), t.size());
-        b.push_back((uint8_t)c);
-        b.push_back((uint8_t)(c >> 8));
-    }
-}
-static int container_header(int format, const lfx_encode_opts &o, std::vector<uint8_t> &b) {
-    if (format == LFX_GZIP) {
-        if (o.extra && o.extra_len > 0xFFFF) return LFX_E_INVALID_DATA;  // gzip.rs:490-492
-        gzip_header(o, o.hcrc != 0, b);
-    } else if (format == LFX_ZLIB) {
-        // zlib Header::write_to zlib.rs:267-279; from_lz77 212-220; Lz77WindowSize::from_u16 132-151
-        uint32_t ws = o.window_size;
-        uint8_t cinfo = ws > 16384 ? 7 : ws > 8192 ? 6 : ws > 4096 ? 5 : ws > 2048 ? 4 : ws > 1024 ? 3
-                        : ws > 512 ? 2 : ws > 256 ? 1 : 0;
-        uint8_t level = (o.no_compression || o.lz77_kind == LFX_LZ77_NOCOMPRESSION) ? 0 : 2;
-        if (o.lz77_level && !o.no_compression) level = (uint8_t)((o.lz77_level - 1) & 3);   // lz77 None/Fast/Balance/Best → 0..3 (zlib.rs:59-68)
-        uint8_t cmf = (uint8_t)((cinfo << 4) | 8), flg = (uint8_t)(level << 6);
-        uint32_t check = ((uint32_t)cmf << 8) + flg;
-        if (check % 31 != 0) flg = (uint8_t)(flg + (31 - check % 31));
-        b.push_back(cmf);
-        b.push_back(flg);
-    } else if (format != LFX_DEFLATE) {
-        return LFX_E_ARG;
-    }
-    return LFX_OK;
-}
 extern "C" uint64_t lfx_container_header_len(int format, const lfx_encode_opts *o) {
     std::vector<uint8_t> b;
     lfx_encode_opts d = norm_opts(o);
@@ -819,379 +696,6 @@ extern "C" int lfx_shard_place_device(lfx_ctx *cc, void *d_member, uint64_t cap,
     HIP_TRY(hipStreamSynchronize(c->stream));
     return LFX_OK;
 } LFX_ABI_CATCH
-
-// ------------------------------------------------------------------------------------------------
-// stream encoder: io::Write shaped
-struct lfx_encoder {
-    Ctx *c;
-    int format;
-    lfx_encode_opts o;
-    std::string filename, comment;
-    std::vector<uint8_t> extra;
-    PlanOpts po;
-    lfx_write_cb w;
-    lfx_flush_cb f;
-    void *user;
-    PinVec pending;                     // input bytes not yet encoded: the planner's byte 0 is pending[0].  Page-locked (lfx_hostio.h):
-                                        // the batch's H2D copy is one DMA transfer straight out of it
-    PinVec h_out;                       // a batch's output lands here (page-locked) and goes to the sink from here: no copy between
-    // one batch in flight on the GPU (bytes mode; enc_launch / enc_collect)
-    PinVec inflight_buf, h_res;         // the batch's input bytes (DMA source until collected); result slot + the shared byte
-    bool inflight = false, inflight_final = false;
-    uint64_t inflight_n = 0, inflight_bound = 0;
-    Plan inflight_plan;
-    hipEvent_t ev_out = nullptr, ev_small = nullptr;
-    Planner *pl = nullptr;              // incremental write-schedule state (chunks / blocks of `pending`)
-    uint64_t total_in = 0, encoded_in = 0;
-    uint32_t crc = 0, adler = 1;        // running container checksum (combined per batch)
-    uint8_t carry = 0;                  // partial last byte of the bitstream so far
-    uint32_t carry_bits = 0;
-    bool finished = false, failed = false;
-    std::string err;
-    DevBuf d_in, d_out;
-    // ---- codes mode (lfx_encoder_write_codes): the caller runs its own Lz77Encode, the GPU Huffman-codes what it emitted.
-    // `pending` then holds the raw bytes whose checksum is still due (they are never matched).
-    int mode = 0;                        // 0 undecided, 1 bytes (lfx_encoder_write), 2 codes
-    struct CodeBlock { uint64_t n_codes; uint32_t type, final; };   // n_codes includes the EndOfBlock; BT_RAW = zlib sync marker
-    std::vector<uint32_t> codes;         // code words of the closed blocks, then of the open one
-    std::vector<CodeBlock> cblocks;      // closed blocks not yet encoded
-    uint64_t closed_codes = 0, open_codes = 0;
-    bool final_closed = false;
-};
-
-static int enc_emit_bytes(lfx_encoder *e, const uint8_t *p, size_t n) {
-    if (!n) return LFX_OK;
-    int64_t r = e->w(e->user, p, n);
-    if (r != (int64_t)n) { e->err = "write callback failed"; e->failed = true; return LFX_E_IO; }
-    return LFX_OK;
-}
-
-// ---- bytes mode: the closed blocks of `pending` as one GPU batch, ONE BATCH IN FLIGHT (round 6).
-// The write() that closes a batch starts it — H2D straight out of the page-locked pending buffer, match … pack — and returns;
-// the GPU works while the caller copies the next batch's bytes in (io::copy: 8192 at a time).  The NEXT batch's start (or
-// flush / finish) collects it: result, the partial last byte (the next batch's first bits share it), the bytes to the sink.
-// A failure of a batch therefore surfaces at the call that collects it — like an io::BufWriter's; the bytes and their
-// order are those of the synchronous form.
-struct EncCollected { uint64_t whole = 0; bool have = false; };
-
-// One batch through the GPU: prepare + emit of `plan` over d_in[0, n) into d_out[0, cap), the bits behind the partial byte the
-// batch before left (`carry`).  The container trailer is written by the host (the checksum spans batches).  async_slot: as
-// encode_emit's — the call returns without waiting.
-static int enc_encode(lfx_encoder *e, const Plan &plan, uint64_t n, uint64_t cap, const HostCodes *hc, EncodeResult *res,
-                      EncodeResult *async_slot) {
-    Ctx *c = e->c;
-    const uint8_t prefix[1] = {e->carry};
-    int rc = encode_prepare(c, plan, e->po, (const uint8_t *)e->d_in.p, n, ck_mode_of(e->format), hc);
-    if (!rc) rc = encode_emit(c, LFX_DEFLATE, false, 0, true, 0, prefix, e->carry_bits ? 1 : 0, e->carry_bits, (uint8_t *)e->d_out.p,
-                              cap & ~3ull, res, async_slot);
-    if (rc) e->err = c->err;
-    return rc;
-}
-// A batch of n input bytes is encoded: its checksum folded into the running one, its bits counted → the bytes of output that
-// are whole (all of them when `final`); the rest stays as `carry_bits` of a byte the caller fetches into `carry`.
-static uint64_t enc_account(lfx_encoder *e, const EncodeResult &res, uint64_t n, bool final) {
-    if (n) {
-        if (e->format == LFX_GZIP) e->crc = e->encoded_in == 0 ? res.crc32 : lfx_crc32_combine(e->crc, res.crc32, n);
-        if (e->format == LFX_ZLIB) e->adler = e->encoded_in == 0 ? res.adler32 : lfx_adler32_combine(e->adler, res.adler32, n);
-        e->encoded_in += n;
-    }
-    e->carry_bits = final ? 0 : (uint32_t)(res.end_bit & 7);
-    return final ? (res.end_bit + 7) / 8 : res.end_bit / 8;
-}
-
-// start the batch; nothing is waited for.  The batch's bytes move to `inflight_buf`, the open block's bytes stay pending.
-static int enc_launch(lfx_encoder *e, Plan &&plan, uint64_t n, bool final) {
-    Ctx *c = e->c;
-    int rc;
-    if ((rc = e->d_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
-    const uint64_t bound = n + n / 4 + 1024 * (uint64_t)plan.blocks.size() + 128;
-    if ((rc = e->d_out.reserve(bound))) return rc;
-    if (e->h_res.size() < 256) e->h_res.resize(256);
-    // ping-pong: appends of later writes must not move (or free) memory a DMA transfer is still reading
-    e->inflight_buf.assign(e->pending.begin() + (std::ptrdiff_t)n, e->pending.end());
-    e->inflight_buf.swap(e->pending);              // pending = the open block's bytes, inflight_buf = the batch (its first n bytes)
-    if (n && hipMemcpyAsync(e->d_in.p, e->inflight_buf.data(), n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LFX_E_DEVICE;
-    if ((rc = enc_encode(e, plan, n, bound, nullptr, nullptr, (EncodeResult *)e->h_res.data()))) return rc;
-    e->inflight = true;
-    e->inflight_final = final;
-    e->inflight_n = n;
-    e->inflight_bound = bound;
-    e->inflight_plan = std::move(plan);
-    return LFX_OK;
-}
-
-// wait for the batch in flight, take its result and the byte the next batch shares with it, queue its bytes' way back
-// (into h_out; `*done` tells when they have arrived)
-static int enc_collect(lfx_encoder *e, EncCollected *out) {
-    Ctx *c = e->c;
-    out->have = false;
-    if (!e->inflight) return LFX_OK;
-    e->inflight = false;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return LFX_E_DEVICE;
-    EncodeResult res{};
-    const uint64_t n = e->inflight_n;
-    // the first pass is the batch in flight, its result in the slot; (never observed) a violation: the batch's bytes are still
-    // in d_in — once more, on the fallback kernel, synchronously
-    bool in_flight = true;
-    int rc = with_match_fallback(c, res, [&]() -> int {
-        if (in_flight) { in_flight = false; res = *(const EncodeResult *)e->h_res.data(); return LFX_OK; }
-        return enc_encode(e, e->inflight_plan, n, e->inflight_bound, nullptr, &res, nullptr);
-    });
-    if (rc) return rc;
-    if (res.status != 0) { c->set_error("output capacity too small"); e->err = c->err; return LFX_E_NOSPACE; }
-    const uint64_t whole = enc_account(e, res, n, e->inflight_final);
-    e->h_out.resize(whole + 1);
-    // the shared byte first (the next batch's launch needs it), then the bulk — which travels while that launch is prepared
-    uint8_t *slot = e->h_res.data() + 128;
-    if (hipMemcpyAsync(slot, (const uint8_t *)e->d_out.p + whole, 1, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipEventRecord(e->ev_small, c->stream) != hipSuccess ||
-        (whole && hipMemcpyAsync(e->h_out.data(), e->d_out.p, whole, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-        hipEventRecord(e->ev_out, c->stream) != hipSuccess || hipEventSynchronize(e->ev_small) != hipSuccess) return LFX_E_DEVICE;
-    e->carry = e->carry_bits ? *slot : 0;
-    out->whole = whole;
-    out->have = true;
-    return LFX_OK;
-}
-
-// Start the closed blocks of `pending` (all of it when `final`, which first closes the stream) as a batch; collect the batch
-// before it; with `drain` also the one just started.  The open block's bytes stay pending.
-static int enc_run(lfx_encoder *e, bool final, bool drain = true) {
-    Ctx *c = e->c;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    (void)hipSetDevice(c->device);
-    if (!e->ev_out && (hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming) != hipSuccess ||
-                       hipEventCreateWithFlags(&e->ev_small, hipEventDisableTiming) != hipSuccess)) return LFX_E_DEVICE;
-    if (final) e->pl->finish();
-    const uint64_t n = final ? e->pending.size() : e->pl->closed_bytes();
-    Plan plan = final ? std::move(e->pl->plan()) : e->pl->take_closed();
-    int rc;
-    EncCollected prev;
-    if ((rc = enc_collect(e, &prev))) return rc;
-    const bool launched = !plan.blocks.empty();
-    if (launched && (rc = enc_launch(e, std::move(plan), n, final))) return rc;
-    if (prev.have) {
-        // the earlier batch's bytes go to the sink while the GPU works on the batch just started
-        if (hipEventSynchronize(e->ev_out) != hipSuccess) return LFX_E_DEVICE;
-        if ((rc = enc_emit_bytes(e, e->h_out.data(), prev.whole))) return rc;
-    }
-    if (drain && launched) {
-        EncCollected cur;
-        if ((rc = enc_collect(e, &cur))) return rc;
-        if (cur.have) {
-            if (hipEventSynchronize(e->ev_out) != hipSuccess) return LFX_E_DEVICE;
-            if ((rc = enc_emit_bytes(e, e->h_out.data(), cur.whole))) return rc;
-        }
-    }
-    return LFX_OK;
-}
-
-// codes mode: encode every closed block (CompressBuf::flush from the histogram on, encode.rs:416-425)
-static int enc_run_codes(lfx_encoder *e) {
-    Ctx *c = e->c;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    (void)hipSetDevice(c->device);
-    if (e->cblocks.empty()) return LFX_OK;
-    Plan plan;
-    std::vector<uint32_t> chunk_codes;
-    uint64_t code_cursor = 0, tile_cursor = 0;
-    for (const lfx_encoder::CodeBlock &cb : e->cblocks) {
-        BlockDesc b{};
-        b.type = cb.type;
-        b.final = cb.final;
-        b.first_chunk = (uint32_t)plan.chunks.size();
-        if (cb.type != BT_RAW) {
-            ChunkDesc ch{};
-            ch.len = cb.n_codes - 1;            // (slots = len + 1, as for a chunk of len bytes that is all literals + EndOfBlock)
-            ch.code_off = code_cursor;
-            ch.block = (uint32_t)plan.blocks.size();
-            ch.flags = CH_LAST_IN_BLOCK;
-            ch.tile_base = tile_cursor;
-            code_cursor += cb.n_codes;
-            tile_cursor += div_up(cb.n_codes, PACK_TILE);
-            plan.chunks.push_back(ch);
-            chunk_codes.push_back((uint32_t)cb.n_codes);
-            b.n_chunks = 1;
-        }
-        plan.blocks.push_back(b);
-    }
-    if (e->final_closed) plan.blocks.back().align_after = 1;     // Block::finish → BitWriter::flush encode.rs:301
-    plan.n_codes_cap = code_cursor;
-    plan.n_tiles = tile_cursor;
-    const uint64_t n = e->pending.size();
-    int rc;
-    if ((rc = e->d_in.reserve(std::max<uint64_t>(n, 4)))) return rc;
-    // a code costs at most 15 + 5 + 15 + 13 bits
-    const uint64_t bound = 6 * code_cursor + 1024 * (uint64_t)plan.blocks.size() + 128;
-    if ((rc = e->d_out.reserve(bound))) return rc;
-    if (n && hipMemcpyAsync(e->d_in.p, e->pending.data(), n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return LFX_E_DEVICE;
-    EncodeResult res{};
-    const HostCodes hc{e->codes.data(), code_cursor, chunk_codes.data()};
-    if ((rc = enc_encode(e, plan, n, bound, &hc, &res, nullptr))) return rc;
-    const uint64_t whole = enc_account(e, res, n, e->final_closed);
-    e->h_out.resize(whole + 1);
-    if (hipMemcpyAsync(e->h_out.data(), e->d_out.p, whole + 1, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) return LFX_E_DEVICE;
-    e->carry = e->carry_bits ? e->h_out[whole] : 0;
-    e->pending.clear();
-    e->codes.erase(e->codes.begin(), e->codes.begin() + (std::ptrdiff_t)e->closed_codes);
-    e->closed_codes = 0;
-    e->cblocks.clear();
-    return enc_emit_bytes(e, e->h_out.data(), whole);
-}
-
-// closed blocks of the codes mode are encoded once this many code words wait (about 8 MiB of text)
-static const uint64_t ENC_BATCH_CODES = 2ull << 20;
-// closed blocks (either mode) are encoded once this many raw bytes wait
-static const uint64_t ENC_BATCH_BYTES_DEFAULT = 8ull << 20;
-static uint64_t enc_batch_bytes(const lfx_encoder *e) { return e->c->diag.enc_batch_mb > 0 ? (uint64_t)e->c->diag.enc_batch_mb << 20 : ENC_BATCH_BYTES_DEFAULT; }
-
-extern "C" int lfx_encoder_write_codes(lfx_encoder *e, const uint32_t *codes, size_t n_codes, const uint8_t *raw, size_t n_raw,
-                                       int end_block) try {
-    if (!e || e->finished || e->final_closed || end_block < 0 || end_block > 2 || (n_codes && !codes) || (n_raw && !raw)) return LFX_E_ARG;
-    if (e->failed) return LFX_E_IO;
-    // stored blocks never run an Lz77Encode (RawBuf, encode.rs:348-383); bytes and codes cannot be mixed on one encoder
-    if (e->mode == 1 || e->po.no_compression) { e->err = "lfx_encoder_write_codes on an encoder that takes bytes"; return LFX_E_ARG; }
-    for (size_t i = 0; i < n_codes; i++) {       // Code::Literal(u8) / Code::Pointer{3..=258, 1..=32768} (lib.rs:27-42)
-        const uint32_t dist = codes[i] & 0xFFFFu, val = codes[i] >> 16;
-        if (dist == 0 ? val > 255 : (val < 3 || val > MAX_LENGTH || dist > MAX_WINDOW)) { e->err = "code word outside Code's domain"; return LFX_E_ARG; }
-    }
-    e->mode = 2;
-    e->codes.insert(e->codes.end(), codes, codes + n_codes);
-    e->open_codes += n_codes;
-    e->pending.insert(e->pending.end(), raw, raw + n_raw);
-    e->total_in += n_raw;
-    if (end_block) {
-        e->codes.push_back(CODE_EOB);            // encode.rs:417
-        e->cblocks.push_back(lfx_encoder::CodeBlock{e->open_codes + 1, e->po.dynamic_huffman ? (uint32_t)BT_DYNAMIC : (uint32_t)BT_FIXED,
-                                                    end_block == 2 ? 1u : 0u});
-        e->closed_codes += e->open_codes + 1;
-        e->open_codes = 0;
-        if (end_block == 2) e->final_closed = true;
-        else if (e->closed_codes >= ENC_BATCH_CODES || e->pending.size() >= enc_batch_bytes(e)) {
-            // (the byte threshold: a well-compressing Lz77Encode — 258-byte matches — closes 2 M code words only after half a
-            //  gigabyte of raw bytes; the reference emits every block as it closes)
-            int rc = enc_run_codes(e);
-            if (rc) { e->failed = true; return rc; }
-        }
-    }
-    return LFX_OK;
-} LFX_ABI_CATCH
-
-extern "C" void lfx_encoder_free(lfx_encoder *e);
-extern "C" lfx_encoder *lfx_encoder_new(lfx_ctx *cc, int format, const lfx_encode_opts *o, lfx_write_cb w,
-                                        lfx_flush_cb f, void *user, int *status) try {
-    if (!cc || !w) { if (status) *status = cc ? LFX_E_ARG : LFX_E_DEVICE; return nullptr; }
-    lfx_encode_opts d = norm_opts(o);
-    int rc = check_opts(d);
-    if (rc) { if (status) *status = rc; return nullptr; }
-    lfx_encoder *e = new lfx_encoder();
-    e->c = reinterpret_cast<Ctx *>(cc);
-    e->format = format;
-    e->o = d;
-    if (d.filename) { e->filename = d.filename; e->o.filename = e->filename.c_str(); }
-    if (d.comment) { e->comment = d.comment; e->o.comment = e->comment.c_str(); }
-    if (d.extra) { e->extra.assign(d.extra, d.extra + d.extra_len); e->o.extra = e->extra.data(); }
-    e->po = plan_opts(format, e->o);
-    e->pl = new Planner(e->po);
-    // (page-locked and device buffers of an earlier encoder of this context, when there are any)
-    e->pending = e->c->take_pin();
-    e->h_out = e->c->take_pin();
-    e->inflight_buf = e->c->take_pin();
-    e->d_in = e->c->take_dev();
-    e->d_out = e->c->take_dev();
-    e->w = w;
-    e->f = f;
-    e->user = user;
-    // gzip/zlib write their header immediately (gzip.rs:805, zlib.rs:578)
-    std::vector<uint8_t> hdr;
-    rc = container_header(format, e->o, hdr);
-    if (!rc) rc = enc_emit_bytes(e, hdr.data(), hdr.size());
-    if (rc) { if (status) *status = rc; lfx_encoder_free(e); return nullptr; }
-    if (status) *status = LFX_OK;
-    return e;
-} LFX_ABI_CATCH_NEW
-
-// closed blocks are encoded — and handed to the sink — once this much input is waiting; the open block's bytes — all the
-// reference itself would be holding (encode.rs:386-426) — stay in `pending`.  8 MiB keeps what the encoder buffers within
-// eight default blocks (the reference emits per block, encode.rs:277-286) at a third of the one-shot call's throughput:
-// a batch is one GPU pass with ~0.4 ms of fixed latency.
-
-extern "C" int64_t lfx_encoder_write(lfx_encoder *e, const uint8_t *p, size_t n) try {
-    if (!e || e->finished) return -(int64_t)LFX_E_ARG;
-    if (e->failed) return -(int64_t)LFX_E_IO;
-    if (e->mode == 2) { e->err = "lfx_encoder_write on an encoder that takes code words"; return -(int64_t)LFX_E_ARG; }
-    e->mode = 1;
-    e->pending.insert(e->pending.end(), p, p + n);
-    e->pl->write(n);
-    e->total_in += n;
-    if (e->pl->closed_bytes() >= enc_batch_bytes(e) || (e->po.no_compression && e->pl->closed_blocks() >= 1024)) {
-        // the batch is started; the next one — or flush / finish — collects it.  Stored blocks (a batch is 64 MiB of them,
-        // copied, not compressed) leave as they are closed.
-        int rc = enc_run(e, false, /*drain=*/e->po.no_compression);
-        if (rc) { e->failed = true; return -(int64_t)rc; }
-    }
-    return (int64_t)n;  // encode.rs:243: always consumes everything
-} LFX_ABI_CATCH_NEG
-
-extern "C" int lfx_encoder_flush(lfx_encoder *e) try {
-    if (!e || e->finished) return LFX_E_ARG;
-    if (e->failed) return LFX_E_IO;
-    int rc;
-    if (e->mode == 2) {
-        // the caller closed the block with E::flush()'s codes (end_block = 1) — Encoder::flush is Block::flush (encode.rs:245-248)
-        if (e->open_codes) { e->err = "close the open block first (end_block = 1)"; return LFX_E_ARG; }
-        if (e->po.zlib_sync) { e->cblocks.push_back(lfx_encoder::CodeBlock{0, (uint32_t)BT_RAW, 0u}); }   // zlib_sync_flush encode.rs:225-234
-        rc = enc_run_codes(e);
-        if (rc) { e->failed = true; return rc; }
-        if (e->f && e->f(e->user) != 0) { e->failed = true; e->err = "flush callback failed"; return LFX_E_IO; }
-        return LFX_OK;
-    }
-    e->pl->flush();
-    rc = enc_run(e, false);  // io::Write::flush pushes everything to the inner writer
-    if (rc) { e->failed = true; return rc; }
-    if (e->f && e->f(e->user) != 0) { e->failed = true; e->err = "flush callback failed"; return LFX_E_IO; }
-    return LFX_OK;
-} LFX_ABI_CATCH
-
-extern "C" int lfx_encoder_finish(lfx_encoder *e) try {
-    if (!e || e->finished) return LFX_E_ARG;
-    if (e->failed) return LFX_E_IO;
-    if (e->mode == 2 && !e->final_closed) { e->err = "close the final block first (end_block = 2)"; return LFX_E_ARG; }
-    e->finished = true;
-    int rc = e->mode == 2 ? enc_run_codes(e) : enc_run(e, true);
-    if (rc) return rc;
-    uint8_t t[8];
-    size_t nt = 0;
-    if (e->format == LFX_GZIP) {  // Trailer::write_to gzip.rs:114-121; ISIZE wraps (gzip.rs:893)
-        uint32_t c = e->total_in ? e->crc : 0, sz = (uint32_t)e->total_in;
-        t[0] = c; t[1] = c >> 8; t[2] = c >> 16; t[3] = c >> 24;
-        t[4] = sz; t[5] = sz >> 8; t[6] = sz >> 16; t[7] = sz >> 24;
-        nt = 8;
-    } else if (e->format == LFX_ZLIB) {  // zlib.rs:630-639
-        uint32_t a = e->total_in ? e->adler : 1;
-        t[0] = a >> 24; t[1] = a >> 16; t[2] = a >> 8; t[3] = a;
-        nt = 4;
-    }
-    rc = enc_emit_bytes(e, t, nt);
-    if (rc) return rc;
-    if (e->f && e->f(e->user) != 0) { e->err = "flush callback failed"; return LFX_E_IO; }
-    return LFX_OK;
-} LFX_ABI_CATCH
-extern "C" const char *lfx_encoder_last_error(const lfx_encoder *e) { return e ? e->err.c_str() : "null"; }
-extern "C" void lfx_encoder_free(lfx_encoder *e) {
-    if (!e) return;
-    (void)hipSetDevice(e->c->device);
-    e->c->give_dev(e->d_in);
-    e->c->give_dev(e->d_out);
-    (void)hipStreamSynchronize(e->c->stream);      // (freed without finish, or after a failed launch: the DMA engine may still read the buffers)
-    if (e->ev_out) (void)hipEventDestroy(e->ev_out);
-    if (e->ev_small) (void)hipEventDestroy(e->ev_small);
-    e->c->give_pin(std::move(e->pending));
-    e->c->give_pin(std::move(e->h_out));
-    e->c->give_pin(std::move(e->inflight_buf));
-    delete e->pl;
-    delete e;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Lz77Encode plug-in

@@ -48,22 +48,25 @@ int launch_match5(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Ch
                   uint32_t nsegs, uint32_t window, uint16_t *cd, uint16_t *glnk, uint32_t *flags, uint64_t *dbg = nullptr);
 // the first-generation kernel's answers (length << 16 | distance) → cd
 int launch_md_to_cd(hipStream_t st, const uint32_t *md, uint64_t n, uint16_t *cd);
-// the greedy walk with lazy match lengths (lfx_parse2.hip) → code words per chunk
-int launch_parse(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, uint32_t nchunks,
-                 uint32_t nsegs, const ParseWg *wgs, uint32_t nwgs, const uint16_t *cd, uint32_t max_len, uint64_t *vis,
-                 uint32_t *seg_tmp, uint32_t *codes, uint32_t *ncodes, uint32_t *stage /* 4 bytes per input byte */,
-                 const uint32_t *seg_map, int stop_after = 0 /* diagnostics: 1 = behind the walk, 2 = behind fixseg */,
-                 uint64_t *dbg = nullptr /* LFX_DEBUG: cycle stamps of one walk workgroup */,
-                 uint32_t *hist = nullptr /* 320 zeroed counters per block: the code words are counted as they are emitted
-                                             (launch_histogram is then not needed) */,
-                 uint32_t emit_per = 0 /* with hist: segments per emit workgroup ... */,
-                 uint32_t emit_parts = 0 /* ... and workgroups for the chunk of most segments (grid = nchunks x emit_parts) */,
-                 hipEvent_t ev_walked = nullptr /* recorded behind the walk kernel (in front of the chaining kernels) */,
-                 const uint32_t *mflags = nullptr /* EncodeResult::match_flags of this call (bit 1 picks the walk's instance) */,
-                 int start_at = 0 /* 1: the walk kernel has been launched (by a call with stop_after = 1): the chaining kernels only */,
-                 const uint8_t *dict_win = nullptr /* a preset dictionary's 32 KiB device window, its usable tail at the end: the
-                                                      dictionary instances of the walking kernels serve the CH_DICT chunks */,
-                 uint32_t dict_usable = 0);
+// the greedy walk with lazy match lengths (lfx_parse2.hip) → code words per chunk, in two launchers: the persistent walk kernel
+// (n_cu: the device's compute units, one workgroup each) ...
+int launch_parse_walk(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, uint32_t nsegs, const ParseWg *wgs,
+                      uint32_t nwgs, uint32_t n_cu, const uint16_t *cd, uint32_t max_len, uint64_t *vis, uint32_t *seg_tmp,
+                      uint32_t *stage /* 4 bytes per input byte */,
+                      const uint32_t *mflags /* EncodeResult::match_flags of this call (bit 1 picks the walk's instance) */,
+                      uint64_t *dbg /* LFX_DEBUG: cycle stamps of one walk workgroup */,
+                      const uint8_t *dict_win /* a preset dictionary's 32 KiB device window, its usable tail at the end: the
+                                                 dictionary instances of the walking kernels serve the CH_DICT chunks */,
+                      uint32_t dict_usable);
+// ... and the chaining kernels behind it: fixseg, fix, emit.  The caller may fork a side stream between the two (stage_parse).
+int launch_parse_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, uint32_t nchunks, uint32_t nsegs,
+                       const uint16_t *cd, uint32_t max_len, uint64_t *vis, uint32_t *seg_tmp, uint32_t *codes, uint32_t *ncodes,
+                       uint32_t *stage, const uint32_t *seg_map,
+                       uint32_t *hist /* 320 zeroed counters per block: the code words are counted as they are emitted
+                                         (launch_histogram is then not needed); nullptr: not counted */,
+                       uint32_t emit_per /* with hist: segments per emit workgroup ... */,
+                       uint32_t emit_parts /* ... and workgroups for the chunk of most segments (grid = nchunks x emit_parts) */,
+                       const uint8_t *dict_win, bool fixseg_only = false /* diagnostics (LFX_DUMP_SEG): stop behind fixseg */);
 struct ZeroSpan { uint32_t *p; uint32_t n; };      // n words at p to be cleared (by the kernel that runs first anyway)
 int launch_chunk_maps(hipStream_t st, const ChunkDesc *chunks, uint32_t nchunks, uint64_t ntiles, uint32_t nsegs,
                       uint32_t *tile_map, uint32_t *seg_map, ZeroSpan z0 = ZeroSpan{nullptr, 0}, ZeroSpan z1 = ZeroSpan{nullptr, 0},

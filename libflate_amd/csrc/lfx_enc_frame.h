@@ -1,0 +1,143 @@
+// lfx_enc_frame.h — host only, no HIP: what the encode entry points and the stream encoder's state machine (lfx_stream_enc.h,
+// built by a plain host compiler) share of the framing — the options' normal form and domain, the planner's options, the
+// container header, and the arithmetic that folds two checksums into one.  The C ABI's wrappers around it stay in lfx_api.cpp.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <mutex>
+#include <vector>
+
+#include "../../include/lfx.h"
+#include "lfx_common.h"
+#include "lfx_plan.h"
+
+namespace lfx {
+
+inline uint32_t host_crc32(const uint8_t *p, size_t n) {
+    static uint32_t tab[256];
+    static std::once_flag once;
+    std::call_once(once, [] {
+        for (uint32_t i = 0; i < 256; i++) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1)));
+            tab[i] = c;
+        }
+    });
+    uint32_t c = 0xFFFFFFFFu;
+    for (size_t i = 0; i < n; i++) c = (c >> 8) ^ tab[(c ^ p[i]) & 0xFF];
+    return ~c;
+}
+inline uint32_t gf2_mulmod(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 0; i < 32; ++i) {
+        if (a & 0x80000000u) p ^= b;
+        a <<= 1;
+        b = (b >> 1) ^ (0xEDB88320u & (0u - (b & 1)));
+    }
+    return p;
+}
+inline uint32_t gf2_xpow8n(uint64_t nbytes) {
+    uint32_t r = 0x80000000u, sq = 0x00800000u;
+    while (nbytes) {
+        if (nbytes & 1) r = gf2_mulmod(r, sq);
+        sq = gf2_mulmod(sq, sq);
+        nbytes >>= 1;
+    }
+    return r;
+}
+// CRC(A||B) from CRC(A), CRC(B), |B| (the reference never combines)
+inline uint32_t crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) { return gf2_mulmod(crc1, gf2_xpow8n(len2)) ^ crc2; }
+inline uint32_t adler32_combine(uint32_t ad1, uint32_t ad2, uint64_t len2) {
+    const uint32_t M = 65521u;
+    uint32_t a1 = ad1 & 0xFFFF, b1 = ad1 >> 16, a2 = ad2 & 0xFFFF, b2 = ad2 >> 16;
+    uint32_t rem = (uint32_t)(len2 % M);
+    uint32_t a = (a1 + a2 + M - 1) % M;
+    uint32_t b = (uint32_t)((b1 + b2 + (uint64_t)rem * ((a1 + M - 1) % M)) % M);
+    return (b << 16) | a;
+}
+
+inline void encode_opts_default(lfx_encode_opts *o) {
+    memset(o, 0, sizeof *o);
+    o->block_size = 1u << 20;
+    o->dynamic_huffman = 1;
+    o->window_size = MAX_WINDOW;
+    o->max_length = MAX_LENGTH;
+    o->os = 3;
+}
+inline lfx_encode_opts norm_opts(const lfx_encode_opts *o) {
+    lfx_encode_opts d;
+    if (o) d = *o; else encode_opts_default(&d);
+    if (d.window_size > MAX_WINDOW) d.window_size = MAX_WINDOW;  // default.rs:228
+    if (d.max_length > MAX_LENGTH) d.max_length = MAX_LENGTH;    // default.rs:240
+    return d;
+}
+inline int check_opts(const lfx_encode_opts &o) {
+    if (o.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
+    if (o.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
+    return LFX_OK;
+}
+inline PlanOpts plan_opts(int format, const lfx_encode_opts &o) {
+    PlanOpts p;
+    p.block_size = o.block_size;
+    p.dynamic_huffman = o.dynamic_huffman != 0;
+    p.no_compression = o.no_compression != 0;
+    p.lz77_kind = o.lz77_kind;
+    p.window_size = o.window_size;
+    p.max_length = o.max_length;
+    p.zlib_sync = format == LFX_ZLIB && o.zlib_flush_mode == LFX_FLUSH_SYNC;
+    return p;
+}
+
+// gzip Header::write_to gzip.rs:368-389 (+flags 343-355, crc16 356-367)
+inline void gzip_header(const lfx_encode_opts &o, bool with_hcrc, std::vector<uint8_t> &b) {
+    uint8_t flg = (uint8_t)((o.is_text ? 1 : 0) | (with_hcrc ? 2 : 0) | (o.extra ? 4 : 0) |
+                            (o.filename ? 8 : 0) | (o.comment ? 16 : 0));
+    // XFL is the level of the header the options hold when the encoder is made (gzip.rs:368-389): DefaultLz77Encoder →
+    // Balance → Unknown(0); NoCompression → None → Unknown(0); a caller's E: Fast → Fastest(4), Best → Slowest(2)
+    // (gzip.rs:84-92,684).  no_compression() resets it to Unknown WHEN IT IS CALLED (gzip.rs:703) and a later header(h)
+    // replaces it again (gzip.rs:717-720): the option builders above this ABI apply both in call order and pass the result in
+    // lz77_level — it is not overridden here (no_compression().header(h with Fastest) writes XFL 4).
+    const uint8_t xfl = o.lz77_level == 1 + LFX_LEVEL_FAST ? 4 : o.lz77_level == 1 + LFX_LEVEL_BEST ? 2 : 0;
+    const uint8_t h[10] = {31, 139, 8, flg, (uint8_t)o.mtime, (uint8_t)(o.mtime >> 8),
+                           (uint8_t)(o.mtime >> 16), (uint8_t)(o.mtime >> 24), xfl, o.os};
+    b.insert(b.end(), h, h + 10);
+    if (o.extra) {
+        b.push_back((uint8_t)o.extra_len);
+        b.push_back((uint8_t)(o.extra_len >> 8));
+        b.insert(b.end(), o.extra, o.extra + o.extra_len);
+    }
+    if (o.filename) b.insert(b.end(), o.filename, o.filename + strlen(o.filename) + 1);
+    if (o.comment) b.insert(b.end(), o.comment, o.comment + strlen(o.comment) + 1);
+    if (with_hcrc) {
+        // the reference checksums the header serialised with is_verified = false (FLG.HCRC clear)
+        std::vector<uint8_t> t;
+        gzip_header(o, false, t);
+        uint32_t c = host_crc32(t.data(), t.size());
+        b.push_back((uint8_t)c);
+        b.push_back((uint8_t)(c >> 8));
+    }
+}
+inline int container_header(int format, const lfx_encode_opts &o, std::vector<uint8_t> &b) {
+    if (format == LFX_GZIP) {
+        if (o.extra && o.extra_len > 0xFFFF) return LFX_E_INVALID_DATA;  // gzip.rs:490-492
+        gzip_header(o, o.hcrc != 0, b);
+    } else if (format == LFX_ZLIB) {
+        // zlib Header::write_to zlib.rs:267-279; from_lz77 212-220; Lz77WindowSize::from_u16 132-151
+        uint32_t ws = o.window_size;
+        uint8_t cinfo = ws > 16384 ? 7 : ws > 8192 ? 6 : ws > 4096 ? 5 : ws > 2048 ? 4 : ws > 1024 ? 3
+                        : ws > 512 ? 2 : ws > 256 ? 1 : 0;
+        uint8_t level = (o.no_compression || o.lz77_kind == LFX_LZ77_NOCOMPRESSION) ? 0 : 2;
+        if (o.lz77_level && !o.no_compression) level = (uint8_t)((o.lz77_level - 1) & 3);   // lz77 None/Fast/Balance/Best → 0..3 (zlib.rs:59-68)
+        uint8_t cmf = (uint8_t)((cinfo << 4) | 8), flg = (uint8_t)(level << 6);
+        uint32_t check = ((uint32_t)cmf << 8) + flg;
+        if (check % 31 != 0) flg = (uint8_t)(flg + (31 - check % 31));
+        b.push_back(cmf);
+        b.push_back(flg);
+    } else if (format != LFX_DEFLATE) {
+        return LFX_E_ARG;
+    }
+    return LFX_OK;
+}
+
+}  // namespace lfx

@@ -94,15 +94,31 @@ void dbg_match(Ctx *c, const EncCall &k) {
                     (unsigned)(hv[w * 8 + 3] >> 32), (unsigned)hv[w * 8 + 4], (unsigned)(hv[w * 8 + 4] >> 32));
     }
 }
+// the parse's two launchers over a call's views: the persistent walk, and the chaining kernels behind it (counted: with the
+// blocks' symbol counts where the geometry fuses them)
+int parse_walk(Ctx *c, const EncCall &k, const uint32_t *mflags, uint64_t *dbg) {
+    const EncView &v = k.v;
+    LAUNCH_TRY(launch_parse_walk(c->stream, k.d_in, k.n, v.chunks, k.plan.n_segs, v.pwgs, (uint32_t)k.g.pwgs.size(),
+                                 (uint32_t)(c->n_cu > 0 ? c->n_cu : 256), v.cd, k.po.max_length, v.vis, v.segtmp, v.stage, mflags, dbg,
+                                 k.dict ? k.dict->d_win : nullptr, k.dict ? k.dict->usable : 0u));
+    return LFX_OK;
+}
+int parse_chain(Ctx *c, const EncCall &k, bool counted, bool fixseg_only = false) {
+    const EncView &v = k.v;
+    LAUNCH_TRY(launch_parse_chain(c->stream, k.d_in, k.n, v.chunks, c->cur_nchunks, k.plan.n_segs, v.cd, k.po.max_length, v.vis, v.segtmp,
+                                  v.codes, v.ncodes, v.stage, v.seg_map, counted && k.g.fused_hist ? v.hist : nullptr, k.g.emit_per,
+                                  k.g.emit_parts, k.dict ? k.dict->d_win : nullptr, fixseg_only));
+    return LFX_OK;
+}
 // LFX_DUMP_SEG: the parse state of one segment behind the walk, behind fixseg and at the end
 int dbg_dump_seg(Ctx *c, const EncCall &k) {
     const EncView &v = k.v;
     hipStream_t st = c->stream;
     const uint32_t sg = (uint32_t)atoi(getenv("LFX_DUMP_SEG"));
     for (int stage_no = 1; stage_no <= 3 && sg < k.plan.n_segs; stage_no++) {
-        LAUNCH_TRY(launch_parse(st, k.d_in, k.n, v.chunks, c->cur_nchunks, k.plan.n_segs, v.pwgs, (uint32_t)k.g.pwgs.size(), v.cd,
-                                k.po.max_length, v.vis, v.segtmp, v.codes, v.ncodes, v.stage, v.seg_map, stage_no % 3, nullptr, nullptr, 0, 0,
-                                nullptr, nullptr, 0, k.dict ? k.dict->d_win : nullptr, k.dict ? k.dict->usable : 0u));
+        if (int rc = parse_walk(c, k, nullptr, nullptr)) return rc;
+        if (stage_no != 1)
+            if (int rc = parse_chain(c, k, false, stage_no == 2)) return rc;
         (void)hipStreamSynchronize(st);
         uint64_t vw[4];
         uint32_t t[6];
@@ -308,15 +324,13 @@ int stage_parse(Ctx *c, EncCall &k) {
     const bool want_checksum = k.ck_mode != 0;
     if (c->diag.debug && getenv("LFX_DUMP_SEG"))
         if (int rc = dbg_dump_seg(c, k)) return rc;
-    // (fine timing: the walk kernel in a bracket of its own — the same launches in two calls)
-    for (int part = c->timing_fine() ? 1 : 0; part <= (c->timing_fine() ? 2 : 0); part++) {
-        LAUNCH_TRY(launch_parse(st, k.d_in, k.n, v.chunks, c->cur_nchunks, k.plan.n_segs, v.pwgs, (uint32_t)k.g.pwgs.size(), v.cd,
-                                k.po.max_length, v.vis, v.segtmp, v.codes, v.ncodes, v.stage, v.seg_map, part == 1 ? 1 : 0,
-                                v.mdbg ? v.mdbg + 256 : nullptr, k.g.fused_hist ? v.hist : nullptr, k.g.emit_per, k.g.emit_parts,
-                                want_checksum ? c->ev_fork : nullptr, v.d_match_flags, part == 2 ? 1 : 0,
-                                k.dict ? k.dict->d_win : nullptr, k.dict ? k.dict->usable : 0u));
-        if (part == 1) c->phase("lz77_walk");
-    }
+    if (int rc = parse_walk(c, k, v.d_match_flags, v.mdbg ? v.mdbg + 256 : nullptr)) return rc;
+    // The side stream's fork point: behind the walk kernel, in front of the chaining kernels.  Recorded HERE, whatever the walk
+    // launched — a plan without chunks (stored blocks) launches nothing, and the side stream must still wait for what the main
+    // stream holds in front: a caller's H2D copy of the input (the stream encoder's batch).
+    if (want_checksum) HIP_TRY(hipEventRecord(c->ev_fork, st));
+    if (c->timing_fine()) c->phase("lz77_walk");     // (fine timing: the walk kernel in a bracket of its own)
+    if (int rc = parse_chain(c, k, true)) return rc;
     if (want_checksum) {
         // the first half of the container checksum's sweep: on the side stream from behind the walk kernel on, beside the
         // chaining kernels (one wavefront per segment and a handful of steps each: they leave most of the GPU idle); the

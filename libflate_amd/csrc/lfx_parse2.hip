@@ -1024,82 +1024,74 @@ int launch_md_to_cd(hipStream_t st, const uint32_t *md, uint64_t n, uint16_t *cd
     return 0;
 }
 
-// workgroups of the persistent walk kernel: one per CU of the current device (read once)
-static uint32_t walk_grid() {
-    static uint32_t g = 0;
-    if (!g) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        const char *e = getenv("LFX_WALK_GRID");     // (experiments)
-        if (e && atoi(e) > 0) cus = atoi(e);
-        g = ((uint32_t)cus + 7) & ~7u;
-    }
-    return g;
+// seg_tmp: six arrays of nsegs words
+struct SegTmp {
+    uint32_t *exit, *count, *off, *exit2, *mpos, *kspec;
+    SegTmp(uint32_t *t, uint32_t nsegs)
+        : exit(t), count(t + nsegs), off(t + 2 * (size_t)nsegs), exit2(t + 3 * (size_t)nsegs), mpos(t + 4 * (size_t)nsegs),
+          kspec(t + 5 * (size_t)nsegs) {}
+};
+
+// (a call with a preset dictionary — dict_win: its 32 KiB device window — launches the dictionary instances of the walk and
+//  of the two chaining kernels that walk; every other call the instances it always launched)
+int launch_parse_walk(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, uint32_t nsegs, const ParseWg *wgs,
+                      uint32_t nwgs, uint32_t n_cu, const uint16_t *cd, uint32_t max_len, uint64_t *vis, uint32_t *seg_tmp, uint32_t *stage,
+                      const uint32_t *mflags, uint64_t *dbg, const uint8_t *dict_win, uint32_t dict_usable) {
+    if (nwgs == 0) return 0;
+    const WalkDict wd{dict_win, dict_usable};
+    const SegTmp t(seg_tmp, nsegs);
+    // persistent: one workgroup per CU (153 KB of LDS), every grid-th slot; the grid a multiple of 8 so that a slot keeps its XCD
+    const uint32_t grid = std::min<uint32_t>((nwgs + 7) & ~7u, (n_cu + 7) & ~7u);
+    if (dict_win && dbg)
+        hipLaunchKernelGGL((parse_walk_kernel<true, WalkDict>), dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd,
+                           max_len, vis, t.exit, t.count, stage, mflags, dbg, wd);
+    else if (dict_win)
+        hipLaunchKernelGGL((parse_walk_kernel<false, WalkDict>), dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd,
+                           max_len, vis, t.exit, t.count, stage, mflags, dbg, wd);
+    else if (dbg)
+        hipLaunchKernelGGL(parse_walk_kernel<true>, dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd, max_len,
+                           vis, t.exit, t.count, stage, mflags, dbg);
+    else
+        hipLaunchKernelGGL(parse_walk_kernel<false>, dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd, max_len,
+                           vis, t.exit, t.count, stage, mflags, dbg);
+    LFX_LAUNCH_CHECK();
+    return 0;
 }
 
-int launch_parse(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, uint32_t nchunks,
-                 uint32_t nsegs, const ParseWg *wgs, uint32_t nwgs, const uint16_t *cd, uint32_t max_len, uint64_t *vis,
-                 uint32_t *seg_tmp, uint32_t *codes, uint32_t *ncodes, uint32_t *stage, const uint32_t *seg_map, int stop_after,
-                 uint64_t *dbg, uint32_t *hist, uint32_t emit_per, uint32_t emit_parts, hipEvent_t ev_walked, const uint32_t *mflags,
-                 int start_at, const uint8_t *dict_win, uint32_t dict_usable) {
+int launch_parse_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, uint32_t nchunks, uint32_t nsegs,
+                       const uint16_t *cd, uint32_t max_len, uint64_t *vis, uint32_t *seg_tmp, uint32_t *codes, uint32_t *ncodes,
+                       uint32_t *stage, const uint32_t *seg_map, uint32_t *hist, uint32_t emit_per, uint32_t emit_parts,
+                       const uint8_t *dict_win, bool fixseg_only) {
     if (nchunks == 0) return 0;
-    // (a call with a preset dictionary — dict_win: its 32 KiB device window — launches the dictionary instances of the walk and
-    //  of the two chaining kernels that walk; every other call the instances it always launched)
-    const WalkDict wd{dict_win, dict_usable};
     const uint8_t *dict_end = dict_win ? dict_win + MAX_WINDOW : nullptr;
-    // seg_tmp: six arrays of nsegs words
-    uint32_t *seg_exit = seg_tmp, *seg_count = seg_tmp + nsegs, *seg_off = seg_tmp + 2 * (size_t)nsegs;
-    uint32_t *seg_exit2 = seg_tmp + 3 * (size_t)nsegs, *seg_mpos = seg_tmp + 4 * (size_t)nsegs;
-    uint32_t *seg_kspec = seg_tmp + 5 * (size_t)nsegs;
-    if (nwgs && start_at < 1) {
-        // persistent: one workgroup per CU (153 KB of LDS), every grid-th slot; the grid a multiple of 8 so that a slot keeps its XCD
-        const uint32_t grid = std::min<uint32_t>((nwgs + 7) & ~7u, walk_grid());
-        if (dict_win && dbg)
-            hipLaunchKernelGGL((parse_walk_kernel<true, WalkDict>), dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd,
-                               max_len, vis, seg_exit, seg_count, stage, mflags, dbg, wd);
-        else if (dict_win)
-            hipLaunchKernelGGL((parse_walk_kernel<false, WalkDict>), dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd,
-                               max_len, vis, seg_exit, seg_count, stage, mflags, dbg, wd);
-        else if (dbg)
-            hipLaunchKernelGGL(parse_walk_kernel<true>, dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd, max_len,
-                               vis, seg_exit, seg_count, stage, mflags, dbg);
-        else
-            hipLaunchKernelGGL(parse_walk_kernel<false>, dim3(grid), dim3(p2::THREADS), 0, st, in, in_bytes, chunks, wgs, nwgs, cd, max_len,
-                               vis, seg_exit, seg_count, stage, mflags, dbg);
-        LFX_LAUNCH_CHECK();
-    }
-    // (the caller's side stream — the container checksum — starts here: beside the chaining kernels, which leave the GPU
-    //  mostly idle, instead of behind all of the parse)
-    if (start_at < 1 && ev_walked && hipEventRecord(ev_walked, st) != hipSuccess) return (int)hipGetLastError();
-    if (stop_after == 1) return 0;      // (LFX_DEBUG dumps; the walk's own bracket of the fine phase timing)
+    const SegTmp t(seg_tmp, nsegs);
     if (nsegs) {
         if (dict_win)
             hipLaunchKernelGGL(parse_fixseg_kernel<const uint8_t *>, dim3(nsegs), dim3(64), 0, st, in, in_bytes, chunks, cd, max_len, vis,
-                               seg_exit, seg_count, seg_exit2, seg_mpos, seg_kspec, seg_map, dict_end);
+                               t.exit, t.count, t.exit2, t.mpos, t.kspec, seg_map, dict_end);
         else
-            hipLaunchKernelGGL(parse_fixseg_kernel<>, dim3(nsegs), dim3(64), 0, st, in, in_bytes, chunks, cd, max_len, vis, seg_exit,
-                               seg_count, seg_exit2, seg_mpos, seg_kspec, seg_map);
+            hipLaunchKernelGGL(parse_fixseg_kernel<>, dim3(nsegs), dim3(64), 0, st, in, in_bytes, chunks, cd, max_len, vis, t.exit,
+                               t.count, t.exit2, t.mpos, t.kspec, seg_map);
         LFX_LAUNCH_CHECK();
     }
-    if (stop_after == 2) return 0;
+    if (fixseg_only) return 0;
     // (workgroup size by the segments per chunk: the fold over a chunk's segments is serial in batches of that size)
     const uint32_t fix_threads = nsegs / nchunks > 128 ? 1024u : 64u;
     if (dict_win)
         hipLaunchKernelGGL(parse_fix_kernel<const uint8_t *>, dim3(nchunks), dim3(fix_threads), 0, st, in, in_bytes, chunks, cd, max_len,
-                           vis, seg_exit, seg_count, seg_exit2, seg_off, codes, ncodes, seg_mpos, hist, dict_end);
+                           vis, t.exit, t.count, t.exit2, t.off, codes, ncodes, t.mpos, hist, dict_end);
     else
         hipLaunchKernelGGL(parse_fix_kernel<>, dim3(nchunks), dim3(fix_threads), 0, st, in, in_bytes, chunks, cd, max_len, vis,
-                           seg_exit, seg_count, seg_exit2, seg_off, codes, ncodes, seg_mpos, hist);
+                           t.exit, t.count, t.exit2, t.off, codes, ncodes, t.mpos, hist);
     LFX_LAUNCH_CHECK();
     if (nsegs && hist) {
         // (the caller sizes the grid: emit_per segments per workgroup, emit_parts = the longest chunk's workgroups)
         hipLaunchKernelGGL(parse_emit_hist_kernel, dim3(nchunks, emit_parts ? emit_parts : 1), dim3(64 * EMIT_WAVES), 0, st, in, in_bytes,
-                           chunks, cd, vis, seg_off, codes, stage, seg_count, seg_exit2, seg_mpos, seg_kspec, emit_per ? emit_per : 1, hist);
+                           chunks, cd, vis, t.off, codes, stage, t.count, t.exit2, t.mpos, t.kspec, emit_per ? emit_per : 1, hist);
         LFX_LAUNCH_CHECK();
     } else if (nsegs) {
-        hipLaunchKernelGGL(parse_emit_kernel, dim3(nsegs), dim3(64), 0, st, in, in_bytes, chunks, cd, vis, seg_off, codes,
-                           stage, seg_count, seg_exit2, seg_mpos, seg_kspec, seg_map);
+        hipLaunchKernelGGL(parse_emit_kernel, dim3(nsegs), dim3(64), 0, st, in, in_bytes, chunks, cd, vis, t.off, codes,
+                           stage, t.count, t.exit2, t.mpos, t.kspec, seg_map);
         LFX_LAUNCH_CHECK();
     }
     return 0;

@@ -601,3 +601,24 @@ def test_stream_decoder_state_machine_over_a_stand_in_backend(tmp_path):
                     os.path.join(root, "oracle", "lfo_core.c"), os.path.join(root, "oracle", "lfo_deflate.c")], check=True)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "stream_dec ok:" in out.stdout, out.stdout[-400:] + out.stderr[-400:]
+
+
+def test_stream_encoder_state_machine_over_a_stand_in_backend(tmp_path):
+    """The stream encoder's state machine (libflate_amd/csrc/lfx_stream_enc.h: no HIP, no context, a plain host compiler builds
+    it) with kilobyte-sized batches over a stand-in batch backend that answers from the oracle's stream for the same calls.
+    tests/c/stream_enc.cpp: all three formats, inputs of 0, 1, block_size - 1, block_size and many blocks, writes of 1, 7, 8192,
+    65537 bytes and all at once, dynamic / fixed / stored blocks; flushes (empty, twice, mid-block, before finish, zlib sync);
+    the order collect → launch → bytes → sink per call and which calls drain; both input buffers reused; the bound on what is
+    buffered; a failing sink at every call, a failing flush callback, a backend failing at launch and at collect, no space, calls
+    after finish; the codes mode with its thresholds, domain and mode rules, codes_plan; an encoder freed with a batch in
+    flight."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "stream_enc")
+    subprocess.run([gxx, "-O2", "-std=c++17", "-Wall", "-o", exe, os.path.join(root, "tests", "c", "stream_enc.cpp"),
+                    os.path.join(root, "oracle", "lfo_core.c"), os.path.join(root, "oracle", "lfo_deflate.c")], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "stream_enc ok:" in out.stdout, out.stdout[-400:] + out.stderr[-400:]
