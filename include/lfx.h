@@ -42,7 +42,27 @@ enum {
 /* libflate_lz77::CompressionLevel (libflate_lz77/src/lib.rs:44-58) */
 enum { LFX_LEVEL_NONE = 0, LFX_LEVEL_FAST = 1, LFX_LEVEL_BALANCE = 2, LFX_LEVEL_BEST = 3 };
 /* which Lz77Encode implementation (lib.rs:83-145, default.rs:14-51) */
-enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1 };
+enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1, LFX_LZ77_CHAIN = 2 };
+/* LFX_LZ77_CHAIN — ChainLz77Encoder(depth K, window_size W, max_length M), an Lz77Encode of this library's own (the reference
+ * takes any through EncodeOptions::with_lz77, encode.rs:59-65): DefaultLz77Encoder with the longest of K chained candidates
+ * instead of the one most recent.  Opt-in; the default stays bit-exact with the reference.
+ *  - Buffering is DefaultLz77Encoder's: encode appends and flushes at W * 8 bytes (default.rs:60-68).
+ *  - flush is default.rs:69-109 with one change at a visited position i < end.  Let c1 > c2 > ... be the earlier occurrences of
+ *    buf[i..i+3] in this buffer, most recent first (every position < end is inserted once, in order, as in the reference).  The
+ *    candidates are c1 .. cK, cut off at the first ck with i - ck > W; none: a literal, as in the reference.
+ *    L(c) = 3 + longest_common_prefix(buf, i + 3, c + 3), capped by M and by the end of the buffer (default.rs:122-129).
+ *    Emitted: Pointer{L(c*), i - c*}, c* the candidate of the greatest L, among equal lengths the nearest (the first one met);
+ *    then i += L.  (A walk may stop once L == min(M, n - i): nothing can be longer.)
+ *  - compression_level() is Best: with lz77_level == 0 zlib's FLEVEL is 3 and gzip's XFL is 2 (no_compression resets both, as
+ *    for any Lz77Encode); a caller's lz77_level wins.
+ *  - At K = 1 the code words are the reference's.
+ * lz77_kind & 0xFF is the kind; for LFX_LZ77_CHAIN bits 8..15 hold the depth K, 1..255 — there is no default depth.  Depth 0 or
+ * any bit above 15 set: LFX_E_ARG.  For the kinds 0 and 1 the bits above bit 7 are not read.
+ * Served by lfx_encode_device / _host, lfx_encode_batch_device, lfx_encoder_* (bytes mode), lfx_encode_members_* (BGZF too) and
+ * lfx_encode_index_device.  LFX_E_UNSUPPORTED from the dictionary encode calls (a dictionary candidate has no chain behind
+ * it) and from the N-GPU encode (lfx_encode_shard_prepare, lfx_sharded_encode_begin); the lfx_lz77 plug-in handle takes no
+ * options and stays DefaultLz77Encoder. */
+#define LFX_LZ77_CHAIN_DEPTH(k) (LFX_LZ77_CHAIN | (k) << 8)
 /* zlib::FlushMode (src/zlib.rs:184-195) */
 enum { LFX_FLUSH_NONE = 0, LFX_FLUSH_SYNC = 2 };
 

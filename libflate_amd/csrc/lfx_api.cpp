@@ -239,6 +239,12 @@ static void dict_header(int format, const lfx_dict *dict, std::vector<uint8_t> &
     hdr[1] = flg;
     for (int sh = 24; sh >= 0; sh -= 8) hdr.push_back((uint8_t)(dict->id >> sh));
 }
+// ChainLz77Encoder has no chain behind a dictionary candidate (Limits)
+static int chain_dict_refused(Ctx *c, const lfx_dict *dict, const lfx_encode_opts &d) {
+    if (!dict || lz77_kind_of(d) != LFX_LZ77_CHAIN) return LFX_OK;
+    c->set_error("lz77_kind: LFX_LZ77_CHAIN with a preset dictionary is not supported");
+    return LFX_E_UNSUPPORTED;
+}
 // the stream's first LZ77 flush unit is the one the dictionary primes — where the options match at all and the dictionary
 // has bytes to offer
 static void dict_prime(const lfx_dict *dict, Plan &p) {
@@ -253,6 +259,7 @@ static int encode_device_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o,
     lfx_encode_opts d = norm_opts(o);
     int rc = check_opts(d);
     if (rc) { c->set_error("option outside the reference's domain"); return rc; }
+    if ((rc = chain_dict_refused(c, dict, d))) return rc;
     std::vector<uint8_t> hdr;
     if ((rc = container_header(format, d, hdr))) { c->set_error("bad container options"); return rc; }
     PlanOpts po = plan_opts(format, d);
@@ -265,7 +272,7 @@ static int encode_device_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o,
     if (fill_ok) (void)hipSetDevice(c->device);
     c->prezero.start(d_out, fill_ok ? cap / 4 * 4 : 0);
     rc = with_match_fallback(c, res, [&]() -> int {
-        if (int rc2 = encode_prepare(c, plan, po, (const uint8_t *)d_in, n, ck_mode_of(format), nullptr, dict)) return rc2;
+        if (int rc2 = encode_prepare(c, plan, po, (const uint8_t *)d_in, n, ck_mode_of(format), nullptr, dict, chain_depth_of(d))) return rc2;
         return encode_emit(c, format, true, 0, true, n, hdr.data(), (uint32_t)hdr.size(), 8 * (uint64_t)hdr.size(),
                            (uint8_t *)d_out, cap, &res);
     });
@@ -308,6 +315,7 @@ static int encode_batch_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o, 
     lfx_encode_opts d = norm_opts(o);
     int rc = check_opts(d);
     if (rc) { c->set_error("option outside the reference's domain"); return rc; }
+    if ((rc = chain_dict_refused(c, dict, d))) return rc;
     std::vector<uint8_t> hdr;
     if ((rc = container_header(format, d, hdr))) { c->set_error("bad container options"); return rc; }
     if (dict) dict_header(format, dict, hdr);
@@ -343,7 +351,7 @@ static int encode_batch_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o, 
     std::vector<uint64_t> h_len;
     std::vector<int32_t> h_status;
     EncodeResult res{};
-    const BatchCall call{format, streams, hdr, (const uint8_t *)d_in, in_extent, (uint8_t *)d_out, out_lo, out_hi, dict};
+    const BatchCall call{format, streams, hdr, (const uint8_t *)d_in, in_extent, (uint8_t *)d_out, out_lo, out_hi, dict, chain_depth_of(d)};
     if ((rc = encode_batch(c, plan, po, call, h_len, h_status, res))) return rc;
     for (uint32_t i = 0; i < count; i++) {
         if (status) status[i] = res.status ? h_status[i] : LFX_OK;     // (a voided call: non-zero for exactly the streams that were too small)
@@ -548,7 +556,7 @@ extern "C" int lfx_encode_members_device(lfx_ctx *cc, const lfx_encode_opts *o, 
     const uint64_t bound = lfx_encode_members_bound(n, member_size, flags, o, s);
     EncodeResult res{};
     const MembersCall call{g, hdr, (const uint8_t *)d_in, (uint8_t *)d_out, cap, std::min(cap, bound), members,
-                           members ? std::min(count, max_members) : 0};
+                           members ? std::min(count, max_members) : 0, chain_depth_of(d)};
     if ((rc = encode_members(c, plan, po, call, res))) return rc;
     if (n_members) *n_members = count;
     if (res.status) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
@@ -613,6 +621,7 @@ extern "C" int lfx_encode_shard_prepare(lfx_ctx *cc, int format, const lfx_encod
     int rc = check_opts(d);
     if (rc) return rc;
     if (d.no_compression) { c->set_error("sharded encode of stored blocks is not supported (their size depends on the bit phase)"); return LFX_E_UNSUPPORTED; }
+    if (lz77_kind_of(d) == LFX_LZ77_CHAIN) { c->set_error("lz77_kind: the N-GPU encode does not serve LFX_LZ77_CHAIN"); return LFX_E_UNSUPPORTED; }
     PlanOpts po = plan_opts(format, d);
     Planner pl(po);
     apply_schedule(pl, s, n);

@@ -72,17 +72,30 @@ inline lfx_encode_opts norm_opts(const lfx_encode_opts *o) {
     if (d.max_length > MAX_LENGTH) d.max_length = MAX_LENGTH;    // default.rs:240
     return d;
 }
+// lz77_kind: the kind in bits 0..7; LFX_LZ77_CHAIN carries its depth in bits 8..15 (include/lfx.h).  The bits above bit 7 are
+// not read for the other kinds.
+inline int lz77_kind_of(const lfx_encode_opts &o) { return (int)((uint32_t)o.lz77_kind & 0xFFu); }
+inline uint32_t chain_depth_of(const lfx_encode_opts &o) {
+    return lz77_kind_of(o) == LFX_LZ77_CHAIN ? ((uint32_t)o.lz77_kind >> 8) & 0xFFu : 0u;
+}
 inline int check_opts(const lfx_encode_opts &o) {
     if (o.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
     if (o.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
+    if (lz77_kind_of(o) == LFX_LZ77_CHAIN && (chain_depth_of(o) == 0 || ((uint32_t)o.lz77_kind >> 16) != 0)) return LFX_E_ARG;
     return LFX_OK;
+}
+// E::compression_level() as lz77_level holds it (1 + LFX_LEVEL_*, 0: the kind's own): ChainLz77Encoder is Best unless the caller
+// says otherwise; no_compression() resets the header's level like any other (zlib.rs:471-475, gzip.rs:703)
+inline uint8_t lz77_level_of(const lfx_encode_opts &o) {
+    if (o.lz77_level == 0 && lz77_kind_of(o) == LFX_LZ77_CHAIN && !o.no_compression) return 1 + LFX_LEVEL_BEST;
+    return o.lz77_level;
 }
 inline PlanOpts plan_opts(int format, const lfx_encode_opts &o) {
     PlanOpts p;
     p.block_size = o.block_size;
     p.dynamic_huffman = o.dynamic_huffman != 0;
     p.no_compression = o.no_compression != 0;
-    p.lz77_kind = o.lz77_kind;
+    p.lz77_kind = lz77_kind_of(o);     // (without the depth)
     p.window_size = o.window_size;
     p.max_length = o.max_length;
     p.zlib_sync = format == LFX_ZLIB && o.zlib_flush_mode == LFX_FLUSH_SYNC;
@@ -98,7 +111,8 @@ inline void gzip_header(const lfx_encode_opts &o, bool with_hcrc, std::vector<ui
     // (gzip.rs:84-92,684).  no_compression() resets it to Unknown WHEN IT IS CALLED (gzip.rs:703) and a later header(h)
     // replaces it again (gzip.rs:717-720): the option builders above this ABI apply both in call order and pass the result in
     // lz77_level — it is not overridden here (no_compression().header(h with Fastest) writes XFL 4).
-    const uint8_t xfl = o.lz77_level == 1 + LFX_LEVEL_FAST ? 4 : o.lz77_level == 1 + LFX_LEVEL_BEST ? 2 : 0;
+    const uint8_t lvl = lz77_level_of(o);
+    const uint8_t xfl = lvl == 1 + LFX_LEVEL_FAST ? 4 : lvl == 1 + LFX_LEVEL_BEST ? 2 : 0;
     const uint8_t h[10] = {31, 139, 8, flg, (uint8_t)o.mtime, (uint8_t)(o.mtime >> 8),
                            (uint8_t)(o.mtime >> 16), (uint8_t)(o.mtime >> 24), xfl, o.os};
     b.insert(b.end(), h, h + 10);
@@ -127,8 +141,8 @@ inline int container_header(int format, const lfx_encode_opts &o, std::vector<ui
         uint32_t ws = o.window_size;
         uint8_t cinfo = ws > 16384 ? 7 : ws > 8192 ? 6 : ws > 4096 ? 5 : ws > 2048 ? 4 : ws > 1024 ? 3
                         : ws > 512 ? 2 : ws > 256 ? 1 : 0;
-        uint8_t level = (o.no_compression || o.lz77_kind == LFX_LZ77_NOCOMPRESSION) ? 0 : 2;
-        if (o.lz77_level && !o.no_compression) level = (uint8_t)((o.lz77_level - 1) & 3);   // lz77 None/Fast/Balance/Best → 0..3 (zlib.rs:59-68)
+        uint8_t level = (o.no_compression || lz77_kind_of(o) == LFX_LZ77_NOCOMPRESSION) ? 0 : 2;
+        if (lz77_level_of(o) && !o.no_compression) level = (uint8_t)((lz77_level_of(o) - 1) & 3);   // lz77 None/Fast/Balance/Best → 0..3 (zlib.rs:59-68)
         uint8_t cmf = (uint8_t)((cinfo << 4) | 8), flg = (uint8_t)(level << 6);
         uint32_t check = ((uint32_t)cmf << 8) + flg;
         if (check % 31 != 0) flg = (uint8_t)(flg + (31 - check % 31));

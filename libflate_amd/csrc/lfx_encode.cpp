@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "lfx_chain.h"
 #include "lfx_dict_enc.h"
 #include "lfx_encode_stages.h"
 
@@ -62,6 +63,7 @@ struct EncCall {
     const HostCodes *hc;
     const lfx_dict *dict;         // a preset dictionary with a usable tail, or nullptr
     bool match_v1;                // the first-generation match kernel: it once saw a lane-order violation (or LFX_MATCH_V1 is set)
+    uint32_t chain_depth;         // ChainLz77Encoder's depth; 0: any other kind — no chain stage, no second candidate buffer
     EncodeGeom g;
     uint64_t nspans = 0;          // partial results of the checksum kernels
     bool forked = false;          // the first half of the checksum's sweep is on the side stream already
@@ -163,6 +165,7 @@ int reserve_scratch(Ctx *c, EncCall &k) {
     if ((rc = c->d_segs.reserve(sizeof(SegDesc) * std::max<size_t>(nsegs, 1)))) return rc;
     if ((rc = c->d_pwgs.reserve(sizeof(ParseWg) * std::max<size_t>(k.g.pwgs.size(), 1)))) return rc;
     if (!hc && (rc = c->d_cd.reserve(2 * n + 64))) return rc;                   // candidate distances, 16 bits per position
+    if (!hc && k.chain_depth && (rc = c->d_cd2.reserve(2 * n + 64))) return rc;  // ... and the chain stage's, which the parse then reads
     if (!hc && !match_v1 && (rc = c->d_glnk.reserve(264 * std::max<uint64_t>(lnk_units, 1)))) return rc;   // lfx_match7: link records (4 bytes) + ballot words (8 bytes per 64); lfx_match5: links (2 bytes)
     if (!hc && !match_v1 && (rc = c->d_ucount.reserve(4 * std::max<size_t>(nsegs, 1)))) return rc;   // lfx_match7: unresolved positions per segment
     if (!hc && match_v1 && (rc = c->d_md.reserve(4 * std::max<uint64_t>(n, 1)))) return rc;   // first-generation kernel: (length, distance) words
@@ -316,6 +319,25 @@ int stage_dict(Ctx *c, const EncCall &k) {
     return LFX_OK;
 }
 
+// ChainLz77Encoder, behind the match stage whichever generation ran: the longest of the first chain_depth
+// candidates on every position's chain through cd → cd2, which the parse reads from here on.  One launch for all chunks.
+int stage_chain(Ctx *c, EncCall &k) {
+    hipStream_t st = c->stream;
+    const bool small = chain_small(k.plan.chunks);
+    chain_items(k.plan.chunks, small ? CHAIN_TILE_SMALL : CHAIN_TILE, c->chain_items);
+    uint16_t *cd2 = (uint16_t *)c->d_cd2.p;
+    if (!c->chain_items.empty()) {
+        const size_t bytes = sizeof(ChainItem) * c->chain_items.size();
+        if (int rc = c->d_chain_items.reserve(bytes)) return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_chain_items.p, c->chain_items.data(), bytes, hipMemcpyHostToDevice, st));
+        LAUNCH_TRY(launch_chain(st, k.d_in, k.n, k.v.chunks, (const ChainItem *)c->d_chain_items.p, (uint32_t)c->chain_items.size(), small,
+                                k.po.window_size, k.po.max_length, k.chain_depth, k.v.cd, cd2));
+    }
+    k.v.cd = cd2;
+    c->phase("lz77_chain_cand");
+    return LFX_OK;
+}
+
 // the greedy walk → code words per chunk (and, fused_hist, the blocks' symbol counts); with a checksum the first half of its
 // sweep goes to the side stream from behind the walk kernel on
 int stage_parse(Ctx *c, EncCall &k) {
@@ -375,13 +397,16 @@ int stage_huffman(Ctx *c, const EncCall &k) {
 }  // namespace
 
 int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *d_in, uint64_t n, int ck_mode, const HostCodes *hc,
-                   const lfx_dict *dict) {
+                   const lfx_dict *dict, uint32_t chain_depth) {
     (void)hipSetDevice(c->device);
     c->n_ev = 0;
     c->phase("start");
     EncCall k{plan, po, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
+              po.lz77_kind == LFX_LZ77_CHAIN && !hc ? chain_depth : 0u,
               encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
+    if (k.chain_depth && k.dict) { c->set_error("LFX_LZ77_CHAIN with a preset dictionary is not supported"); return LFX_E_UNSUPPORTED; }
+    if (po.lz77_kind == LFX_LZ77_CHAIN && !hc && !chain_depth) { c->set_error("LFX_LZ77_CHAIN: this entry point does not serve it"); return LFX_E_UNSUPPORTED; }
     if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)
     c->cur_nchunks = (uint32_t)plan.chunks.size();
     c->cur_nblocks = (uint32_t)plan.blocks.size();
@@ -396,6 +421,7 @@ int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *
     else {
         rc = stage_match(c, k);
         if (!rc && k.dict) rc = stage_dict(c, k);
+        if (!rc && k.chain_depth) rc = stage_chain(c, k);
         if (!rc) rc = stage_parse(c, k);
     }
     if (rc) return rc;
@@ -476,7 +502,7 @@ int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &
     h_len.resize(count);
     h_status.resize(count);
     return with_match_fallback(c, res, [&]() -> int {
-        if (int rc = encode_prepare(c, plan, po, b.d_in, b.in_extent, 0, nullptr, b.dict)) return rc;
+        if (int rc = encode_prepare(c, plan, po, b.d_in, b.in_extent, 0, nullptr, b.dict, b.chain_depth)) return rc;
         HIP_TRY(hipMemcpyAsync(d_streams, b.streams.data(), sz_streams, hipMemcpyHostToDevice, st));
         if (!b.hdr.empty()) HIP_TRY(hipMemcpyAsync(d_hdr, b.hdr.data(), b.hdr.size(), hipMemcpyHostToDevice, st));
         if (trailer)
@@ -519,7 +545,7 @@ int encode_members(Ctx *c, const Plan &plan, const PlanOpts &po, const MembersCa
     // bound, and nothing is written when the total exceeds cap
     c->prezero.start(m.d_out, m.fill);
     const int rc = with_match_fallback(c, res, [&]() -> int {
-        if (int rc2 = encode_prepare(c, plan, po, m.d_in, g.n, 0)) return rc2;
+        if (int rc2 = encode_prepare(c, plan, po, m.d_in, g.n, 0, nullptr, nullptr, m.chain_depth)) return rc2;
         HIP_TRY(hipMemcpyAsync(d_hdr, m.hdr.data(), m.hdr.size(), hipMemcpyHostToDevice, st));
         EncodeResult *dres = (EncodeResult *)c->d_res.p;
         LAUNCH_TRY(launch_members_layout(st, g, (BlockDesc *)c->d_blocks.p, (const BlockCodes *)c->d_bc.p, d_local, d_mlen, d_wg, m.cap,

@@ -20,7 +20,7 @@ struct PlanOpts {
     uint64_t block_size = 1u << 20;
     bool dynamic_huffman = true;
     bool no_compression = false;
-    int lz77_kind = 0;  // 0 default, 1 NoCompressionLz77Encoder
+    int lz77_kind = 0;  // 0 default, 1 NoCompressionLz77Encoder, 2 ChainLz77Encoder (the kind alone: its depth is no concern of the plan)
     uint32_t window_size = MAX_WINDOW;
     uint32_t max_length = MAX_LENGTH;
     bool zlib_sync = false;  // zlib FlushMode::Sync (only meaningful for the zlib container)
@@ -65,7 +65,7 @@ class Planner {
         }
         original_size_ += n;  // CompressBuf::append encode.rs:405-408
         lz_len_ += n;
-        if (o_.lz77_kind == 0 && lz_len_ >= (uint64_t)o_.window_size * 8) lz_flush();  // default.rs:65
+        if (buffers() && lz_len_ >= (uint64_t)o_.window_size * 8) lz_flush();  // default.rs:65
         while (original_size_ >= block_size_) block_flush(false);
     }
     // `count` consecutive write() calls of n bytes each — the reference's io::copy protocol is 32768 writes of 8 KiB per
@@ -80,7 +80,7 @@ class Planner {
             if (raw_) quiet = raw_len_ < block_size_ ? (block_size_ - raw_len_ - 1) / n : 0;      // raw_len_ + k n < block_size_
             else {
                 quiet = original_size_ < block_size_ ? (block_size_ - original_size_ - 1) / n : 0;
-                if (o_.lz77_kind == 0) {
+                if (buffers()) {
                     const uint64_t w8 = (uint64_t)o_.window_size * 8;
                     const uint64_t q2 = lz_len_ < w8 ? (w8 - lz_len_ - 1) / n : 0;
                     quiet = quiet < q2 ? quiet : q2;
@@ -155,6 +155,8 @@ class Planner {
     }
 
   private:
+    // DefaultLz77Encoder's buffering (default.rs:60-68): its own, and ChainLz77Encoder's (kind 2)
+    bool buffers() const { return o_.lz77_kind == 0 || o_.lz77_kind == 2; }
     void emit_chunk(uint64_t off, uint64_t len, uint32_t flags) {
         ChunkDesc c{};
         c.in_off = off;

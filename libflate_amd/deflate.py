@@ -62,9 +62,17 @@ class Encoder(_EncoderBase):
         return cls(inner, options, context)
 
 
-def _compress(fmt, data, zdict, options, context):
+def _with_lz77(options, lz77, cls):
+    """options with `lz77` (an Lz77Encode of this package, e.g. lz77.ChainLz77Encoder(8)) put in; None: options as they are"""
+    if lz77 is None:
+        return options
+    return (options if options is not None else cls()).with_lz77(lz77)
+
+
+def _compress(fmt, data, zdict, options, context, lz77=None):
     from .context import Dictionary, default_context
     ctx = context if context is not None else default_context()
+    options = _with_lz77(options, lz77, EncodeOptions)
     opts = options._to_c() if options is not None else None
     if zdict is None:
         return ctx.encode_host(fmt, data, opts)
@@ -77,11 +85,12 @@ def _compress(fmt, data, zdict, options, context):
             d.close()
 
 
-def compress(data, zdict=None, options=None, context=None):
+def compress(data, zdict=None, options=None, context=None, lz77=None):
     """`data` as one raw DEFLATE stream, encoded in one call (one write_all + finish).  zdict: a preset dictionary, bytes or a
     libflate_amd.Dictionary — the stream then starts with the dictionary as history, what
-    zlib.decompressobj(wbits=-15, zdict=...) reads (lfx_encode_dict_host)."""
-    return _compress(_ffi.DEFLATE, data, zdict, options, context)
+    zlib.decompressobj(wbits=-15, zdict=...) reads (lfx_encode_dict_host).  lz77: an Lz77Encode of this package
+    for the options, e.g. lz77.ChainLz77Encoder(8)."""
+    return _compress(_ffi.DEFLATE, data, zdict, options, context, lz77)
 
 
 class Decoder(_DecoderBase):

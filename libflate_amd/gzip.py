@@ -147,14 +147,23 @@ def list_members(data, context=None):
     return members
 
 
-def encode_members(data, member_size=1 << 20, bgzf=False, options=None, context=None):
+def compress(data, options=None, context=None, lz77=None):
+    """`data` as one gzip member, encoded in one call (one write_all + finish; modification time 0 unless the options say
+    otherwise).  lz77: an Lz77Encode of this package for the options, e.g. lz77.ChainLz77Encoder(8)."""
+    if options is None:
+        options = EncodeOptions()
+    return _deflate._compress(_ffi.GZIP, data, None, options, context, lz77)
+
+
+def encode_members(data, member_size=1 << 20, bgzf=False, options=None, context=None, lz77=None):
     """`data` as gzip members of member_size input bytes each, lying back to back: what decode_members, zcat and Python's gzip
     read, and with bgzf=True (member_size at most 65505; bgzip's own is _ffi.BGZF_MEMBER_SIZE = 65280) a BGZF file with its
     end-of-file marker.  All members are encoded on the GPU in one pass (lfx_encode_members_host) → (bytes, [(in_off, in_len,
     out_off, out_len)] per member: the slice of `data`, the member in the result).  members_to_gzi(members) is bgzip's index of
-    them.  Raises StreamError where the call fails."""
+    them.  lz77: an Lz77Encode of this package for the options, e.g. lz77.ChainLz77Encoder(8).  Raises StreamError where the call
+    fails."""
     ctx = context if context is not None else default_context()
-    opts = (options if options is not None else EncodeOptions())._to_c()
+    opts = _deflate._with_lz77(options if options is not None else EncodeOptions(), lz77, EncodeOptions)._to_c()
     try:
         rc, out, _count, members, msg = ctx.encode_members_host(data, member_size, _ffi.MEMBERS_BGZF if bgzf else 0, opts)
     except _ffi.DeviceError:

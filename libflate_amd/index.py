@@ -76,13 +76,16 @@ class Index:
             return out[:ol], cls(h, ctx)
 
     @classmethod
-    def encode(cls, data, format="gzip", spacing=1 << 20, options=None, schedule=None, ctx=None):
+    def encode(cls, data, format="gzip", spacing=1 << 20, options=None, schedule=None, ctx=None, lz77=None):
         """Compress `data` and index the stream written (lfx_encode_index_device) → (encoded CUDA uint8 tensor, Index).
         options: an lfx_encode_opts or a {deflate,zlib,gzip}.EncodeOptions; schedule: an lfx_schedule (None: one write_all).
         The encoded bytes are exactly lfx_encode_device's.  Raises LfxError where the encode fails."""
         import torch
         ctx = ctx if ctx is not None else default_context()
         fmt = _FORMATS[format] if isinstance(format, str) else int(format)
+        if lz77 is not None:        # (an Lz77Encode of this package for the options, e.g. lz77.ChainLz77Encoder(8))
+            from . import deflate, gzip as _gzip
+            options = deflate._with_lz77(options, lz77, _gzip.EncodeOptions if fmt == _ffi.GZIP else deflate.EncodeOptions)
         opts = options._to_c() if hasattr(options, "_to_c") else options
         src = _device_bytes(data, ctx.device)
         n = src.numel()

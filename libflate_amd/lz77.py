@@ -113,6 +113,30 @@ class DefaultLz77EncoderBuilder:  # default.rs:202-249
         return DefaultLz77Encoder(self._w, self._m)
 
 
+class ChainLz77Encoder:
+    """This library's own Lz77Encode (LFX_LZ77_CHAIN): DefaultLz77Encoder's buffering and walk, but at every
+    visited position the longest of the first `depth` (1..255) chained occurrences of the 3-byte prefix instead of the most
+    recent one; among equal lengths the nearest.  Compresses better and is NOT bit-exact with the reference's default (at
+    depth 1 it is).  For EncodeOptions.with_lz77 / EncodeOptions(lz77=...): the whole path runs on the GPU.  It has no encode /
+    flush of its own (the lfx_lz77 plug-in handle is DefaultLz77Encoder's)."""
+
+    def __init__(self, depth, window_size=MAX_WINDOW_SIZE, max_length=MAX_LENGTH):
+        self._depth = int(depth)
+        self._window = min(window_size, MAX_WINDOW_SIZE)
+        self._max_length = min(max_length, MAX_LENGTH)
+
+    def compression_level(self):
+        return CompressionLevel.BEST
+
+    def window_size(self):
+        return self._window
+
+    def _opts(self):
+        # (a depth outside 1..255 reaches check_opts as it is: LFX_E_ARG, not a silently different depth)
+        return {"lz77_kind": _ffi.LZ77_CHAIN | (self._depth if 0 <= self._depth <= 255 else 256) << 8,
+                "window_size": self._window, "max_length": self._max_length}
+
+
 class NoCompressionLz77Encoder:
     """lib.rs:111-145: every byte a literal (still Huffman coded by the block encoder)."""
 

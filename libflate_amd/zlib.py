@@ -30,11 +30,14 @@ class Encoder(_EncoderBase):
         return cls(inner, options, context)
 
 
-def compress(data, zdict=None, options=None, context=None):
+def compress(data, zdict=None, options=None, context=None, lz77=None):
     """`data` as one zlib stream, encoded in one call (one write_all + finish).  zdict: a preset dictionary, bytes or a
     libflate_amd.Dictionary — the stream then carries FDICT and the dictionary's id, what zlib.decompressobj(zdict=...)
-    reads (lfx_encode_dict_host)."""
-    return _deflate._compress(_ffi.ZLIB, data, zdict, options, context)
+    reads (lfx_encode_dict_host).  lz77: an Lz77Encode of this package for the options, e.g.
+    lz77.ChainLz77Encoder(8)."""
+    if lz77 is not None and options is None:
+        options = EncodeOptions()
+    return _deflate._compress(_ffi.ZLIB, data, zdict, options, context, lz77)
 
 
 class Decoder(_DecoderBase):

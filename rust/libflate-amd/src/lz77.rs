@@ -101,6 +101,11 @@ impl<E: Lz77Encode + 'static> GpuLz77 for E {
         } else if any.is::<NoCompressionLz77Encoder>() {
             o.lz77_kind = ffi::LFX_LZ77_NOCOMPRESSION;
             true
+        } else if let Some(c) = any.downcast_ref::<ChainLz77Encoder>() {
+            o.lz77_kind = ffi::lfx_lz77_chain_depth(c.depth);     // (depth 0: LFX_E_ARG from the encoder's constructor)
+            o.window_size = c.window_size as u32;
+            o.max_length = c.max_length as u32;
+            true
         } else {
             // only the container header looks at these two (zlib.rs:212-220, gzip.rs:684)
             o.lz77_kind = ffi::LFX_LZ77_DEFAULT;
@@ -211,6 +216,27 @@ impl DefaultLz77EncoderBuilder {
     pub fn window_size(self, window_size: u16) -> Self { DefaultLz77EncoderBuilder { window_size: std::cmp::min(window_size, MAX_WINDOW_SIZE), ..self } }
     pub fn max_length(self, max_length: u16) -> Self { DefaultLz77EncoderBuilder { max_length: std::cmp::min(max_length, MAX_LENGTH), ..self } }
     pub fn build(self) -> DefaultLz77Encoder { DefaultLz77Encoder { window_size: self.window_size, max_length: self.max_length, gpu: None } }
+}
+
+/// This library's own `Lz77Encode` (`LFX_LZ77_CHAIN`, include/lfx.h): `DefaultLz77Encoder`'s buffering and walk,
+/// but at every visited position the longest of the first `depth` chained occurrences of the 3-byte prefix instead of the most
+/// recent one; among equal lengths the nearest.  Compresses better and is not bit-exact with the reference's default (at depth
+/// 1 it is).  As the `E` of this crate's encoders it only configures the device pipeline; it has no device path of its own
+/// behind `Lz77Encode::encode` / `flush` (the `lfx_lz77` handle is `DefaultLz77Encoder`'s), so those two panic.
+#[derive(Debug, Clone)]
+pub struct ChainLz77Encoder { depth: u8, window_size: u16, max_length: u16 }
+impl ChainLz77Encoder {
+    /// `depth`: 1..=255 candidates per visited position (0 is refused when the encoder is made: `LFX_E_ARG`)
+    pub fn new(depth: u8) -> Self { ChainLz77Encoder { depth, window_size: MAX_WINDOW_SIZE, max_length: MAX_LENGTH } }
+    pub fn with_window_size(self, window_size: u16) -> Self { ChainLz77Encoder { window_size: std::cmp::min(window_size, MAX_WINDOW_SIZE), ..self } }
+    pub fn with_max_length(self, max_length: u16) -> Self { ChainLz77Encoder { max_length: std::cmp::min(max_length, MAX_LENGTH), ..self } }
+    pub fn depth(&self) -> u8 { self.depth }
+}
+impl Lz77Encode for ChainLz77Encoder {
+    fn encode<S: Sink>(&mut self, _buf: &[u8], _sink: S) { panic!("libflate-amd: ChainLz77Encoder runs inside the encoders only (EncodeOptions::with_lz77)") }
+    fn flush<S: Sink>(&mut self, _sink: S) { panic!("libflate-amd: ChainLz77Encoder runs inside the encoders only (EncodeOptions::with_lz77)") }
+    fn compression_level(&self) -> CompressionLevel { CompressionLevel::Best }
+    fn window_size(&self) -> u16 { self.window_size }
 }
 
 /// `libflate_lz77::NoCompressionLz77Encoder` (lib.rs:111-145): every byte a literal (still Huffman coded)
