@@ -42,7 +42,7 @@ enum {
 /* libflate_lz77::CompressionLevel (libflate_lz77/src/lib.rs:44-58) */
 enum { LFX_LEVEL_NONE = 0, LFX_LEVEL_FAST = 1, LFX_LEVEL_BALANCE = 2, LFX_LEVEL_BEST = 3 };
 /* which Lz77Encode implementation (lib.rs:83-145, default.rs:14-51) */
-enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1, LFX_LZ77_CHAIN = 2 };
+enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1, LFX_LZ77_CHAIN = 2, LFX_LZ77_LAZY = 3 };
 /* LFX_LZ77_CHAIN — ChainLz77Encoder(depth K, window_size W, max_length M), an Lz77Encode of this library's own (the reference
  * takes any through EncodeOptions::with_lz77, encode.rs:59-65): DefaultLz77Encoder with the longest of K chained candidates
  * instead of the one most recent.  Opt-in; the default stays bit-exact with the reference.
@@ -63,6 +63,19 @@ enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1, LFX_LZ77_CHAIN = 2 };
  * it) and from the N-GPU encode (lfx_encode_shard_prepare, lfx_sharded_encode_begin); the lfx_lz77 plug-in handle takes no
  * options and stays DefaultLz77Encoder. */
 #define LFX_LZ77_CHAIN_DEPTH(k) (LFX_LZ77_CHAIN | (k) << 8)
+/* LFX_LZ77_LAZY — LazyLz77Encoder(depth K, window_size W, max_length M): ChainLz77Encoder with zlib's lazy rule (deflate_slow)
+ * on top.  Opt-in, a kind of its own.
+ *  - Buffering and candidates are ChainLz77Encoder's.  For a position p < end with candidates, L(p) and D(p) are the length
+ *    and the distance of the candidate ChainLz77Encoder emits there (the longest of the first K, among equal lengths the
+ *    nearest); L(p) = 0 where there is no candidate, and for every p >= end.  Both are functions of the position alone: every
+ *    position < end is inserted once, in order, whatever the walk visits.
+ *  - The walk at a visited i < end: L(i) != 0 and L(i + 1) <= L(i): Pointer{L(i), D(i)}, i += L(i).  Otherwise
+ *    Literal(buf[i]), i += 1.  The tail is the reference's (default.rs:105-107).  There is no max_lazy, no good_length and no
+ *    TOO_FAR: a run of deferrals is as long as the lengths keep rising.
+ *  - compression_level() is Best, with the FLEVEL / XFL rules of LFX_LZ77_CHAIN.
+ * Bits 8..15 hold the depth K, 1..255; depth 0 or any bit above 15 set: LFX_E_ARG.  Served and refused (LFX_E_UNSUPPORTED)
+ * by the same entry points as LFX_LZ77_CHAIN. */
+#define LFX_LZ77_LAZY_DEPTH(k) (LFX_LZ77_LAZY | (k) << 8)
 /* zlib::FlushMode (src/zlib.rs:184-195) */
 enum { LFX_FLUSH_NONE = 0, LFX_FLUSH_SYNC = 2 };
 

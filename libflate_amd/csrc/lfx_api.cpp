@@ -239,10 +239,11 @@ static void dict_header(int format, const lfx_dict *dict, std::vector<uint8_t> &
     hdr[1] = flg;
     for (int sh = 24; sh >= 0; sh -= 8) hdr.push_back((uint8_t)(dict->id >> sh));
 }
-// ChainLz77Encoder has no chain behind a dictionary candidate (Limits)
+// ChainLz77Encoder and LazyLz77Encoder have no chain behind a dictionary candidate (Limits)
 static int chain_dict_refused(Ctx *c, const lfx_dict *dict, const lfx_encode_opts &d) {
-    if (!dict || lz77_kind_of(d) != LFX_LZ77_CHAIN) return LFX_OK;
-    c->set_error("lz77_kind: LFX_LZ77_CHAIN with a preset dictionary is not supported");
+    if (!dict || !lz77_chained(lz77_kind_of(d))) return LFX_OK;
+    c->set_error(lazy_of(d) ? "lz77_kind: LFX_LZ77_LAZY with a preset dictionary is not supported"
+                            : "lz77_kind: LFX_LZ77_CHAIN with a preset dictionary is not supported");
     return LFX_E_UNSUPPORTED;
 }
 // the stream's first LZ77 flush unit is the one the dictionary primes — where the options match at all and the dictionary
@@ -622,6 +623,7 @@ extern "C" int lfx_encode_shard_prepare(lfx_ctx *cc, int format, const lfx_encod
     if (rc) return rc;
     if (d.no_compression) { c->set_error("sharded encode of stored blocks is not supported (their size depends on the bit phase)"); return LFX_E_UNSUPPORTED; }
     if (lz77_kind_of(d) == LFX_LZ77_CHAIN) { c->set_error("lz77_kind: the N-GPU encode does not serve LFX_LZ77_CHAIN"); return LFX_E_UNSUPPORTED; }
+    if (lazy_of(d)) { c->set_error("lz77_kind: the N-GPU encode does not serve LFX_LZ77_LAZY"); return LFX_E_UNSUPPORTED; }
     PlanOpts po = plan_opts(format, d);
     Planner pl(po);
     apply_schedule(pl, s, n);

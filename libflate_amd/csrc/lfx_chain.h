@@ -44,11 +44,40 @@ inline void chain_items(const std::vector<ChunkDesc> &chunks, uint32_t tile, std
     }
 }
 
+// LazyLz77Encoder's demote kernel on one work item, in positions of the CALL's arrays (in_off + p: a chunk begins
+// anywhere, the per-position arrays are aligned as a whole).  The item's positions [g0, g1) are cut on the grid of 16: the
+// whole groups [a, b) take 16-byte accesses, [g0, a) and [b, g1) — under 16 positions each, or all of an item that holds no
+// whole group, under 31 — share their group with a neighbouring item or chunk and go one position at a time.  gend: where the
+// chunk's visited range ends; a position g is demoted only with g + 1 < gend.
+constexpr uint32_t DEMOTE_GROUP = 16;
+struct DemoteSpan {
+    uint64_t g0, a, b, g1, gend;
+};
+LFX_HD inline DemoteSpan demote_span(uint64_t in_off, uint64_t len, uint64_t p0, uint32_t tile) {
+    const uint64_t end = (len > 3 ? len : 3) - 3;                // default.rs:75
+    const uint64_t p1 = p0 + tile < end ? p0 + tile : end;
+    DemoteSpan s;
+    s.g0 = in_off + (p0 < p1 ? p0 : p1);
+    s.g1 = in_off + p1;
+    s.gend = in_off + end;
+    s.a = (s.g0 + DEMOTE_GROUP - 1) / DEMOTE_GROUP * DEMOTE_GROUP;
+    s.b = s.g1 / DEMOTE_GROUP * DEMOTE_GROUP;
+    if (s.a >= s.b) s.a = s.b = s.g1;                            // no whole group: [g0, g1) by hand
+    return s;
+}
+
 #ifdef __HIPCC__
 // behind the match stage: cd2[p] ← the distance of the longest of the first `depth` candidates on p's chain through cd (ties: the
 // nearest) for every listed position p < end with cd[p] != 0, and 0 where cd[p] == 0.  cd is only read.
+// len (LazyLz77Encoder; nullptr: ChainLz77Encoder's one launch, unchanged): a byte per position of scratch.  The
+// chain kernel's variant also leaves each listed position's length there (L - 3; 0 without a candidate), for launch_demote.
 int launch_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, const ChainItem *items,
-                 uint32_t nitems, bool small, uint32_t window, uint32_t max_len, uint32_t depth, const uint16_t *cd, uint16_t *cd2);
+                 uint32_t nitems, bool small, uint32_t window, uint32_t max_len, uint32_t depth, const uint16_t *cd, uint16_t *cd2,
+                 uint8_t *len = nullptr);
+// LazyLz77Encoder, behind launch_chain on the same stream and over the same work list: cd2[p] ← 0 for every listed position p
+// with p + 1 < end and len[p + 1] > len[p].  len is only read; nothing but the listed positions' cd2 is written.
+int launch_demote(hipStream_t st, const ChunkDesc *chunks, const ChainItem *items, uint32_t nitems, bool small, const uint8_t *len,
+                  uint16_t *cd2);
 #endif
 
 }  // namespace lfx

@@ -1,4 +1,5 @@
-// lfx_chain.hip — ChainLz77Encoder's candidate refinement (LFX_LZ77_CHAIN), for gfx950.
+// lfx_chain.hip — ChainLz77Encoder's candidate refinement (LFX_LZ77_CHAIN) and LazyLz77Encoder's demotion on top
+// of it (LFX_LZ77_LAZY, §20: demote_kernel below), for gfx950.
 //
 // The match stage leaves cd[p] = distance to the most recent earlier occurrence of p's 3-byte prefix inside p's chunk, 0 where
 // there is none within window_size — for EVERY position p < end, whatever the parse will visit (DefaultLz77Encoder::flush
@@ -40,10 +41,21 @@ __device__ __forceinline__ uint64_t lds8(const uint32_t *w, uint32_t off) {
 }
 __device__ __forceinline__ uint32_t lds1(const uint32_t *w, uint32_t off) { return (w[off >> 2] >> ((off & 3) * 8)) & 0xFFu; }
 
-template <uint32_t TILE, uint32_t WCAP, uint32_t THREADS>
+// LEN (LazyLz77Encoder): the length of the candidate written, which this kernel holds anyway, goes to a byte per
+// position as well — L - 3, and 0 where there is no candidate ("none" and L = 3 share the 0: only a strictly longer successor
+// demotes a position, and a position without a candidate is no match anyway; 257 and 258 stay apart).  Without LEN the
+// kernel is ChainLz77Encoder's, instruction for instruction, with its arguments: the length array is a parameter pack of
+// none (chain_kernel<TILE, WCAP, THREADS>) or of one uint8_t * (chain_kernel<TILE, WCAP, THREADS, uint8_t *>).
+__device__ __forceinline__ uint8_t *len_of() { return nullptr; }
+__device__ __forceinline__ uint8_t *len_of(uint8_t *len) { return len; }
+
+template <uint32_t TILE, uint32_t WCAP, uint32_t THREADS, typename... Len>
 __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restrict__ in, const ChunkDesc *__restrict__ chunks,
                                                         const ChainItem *__restrict__ items, uint32_t window, uint32_t max_len,
-                                                        uint32_t depth, const uint16_t *__restrict__ cd, uint16_t *__restrict__ cd2) {
+                                                        uint32_t depth, const uint16_t *__restrict__ cd, uint16_t *__restrict__ cd2,
+                                                        Len... len) {
+    constexpr bool LEN = sizeof...(Len) != 0;
+    static_assert(sizeof...(Len) <= 1, "no length array or one");
     // bytes [lo, hi): at most WCAP + TILE + MAX_LENGTH, + the byte phase of lo on the dword grid (3), + what the last compare
     // step and its three-dword read reach past the last byte that counts (11)
     constexpr uint32_t BW = (WCAP + TILE + MAX_LENGTH + 3 + 11 + 3) / 4 + 1;
@@ -80,6 +92,7 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
     const uint16_t *c16 = (const uint16_t *)s_c;
     const uint32_t boff = sh - lo, coff = csh - lo;              // (unsigned wrap: q + boff = q - lo + sh)
     uint16_t *out = cd2 + ch.in_off;
+    uint8_t *lout = LEN ? len_of(len...) + ch.in_off : nullptr;
 
     enum : uint32_t { FETCH = 0, COMPARE = 1, HOP = 2 };
     uint32_t state = FETCH;
@@ -91,6 +104,7 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
             const uint32_t d = c16[p + coff];
             if (d == 0 || d > p) {                                // no candidate (d > p: never, a distance stays inside the chunk)
                 out[p] = 0;
+                if (LEN) lout[p] = 0;
                 p += THREADS;
                 continue;
             }
@@ -101,7 +115,11 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
             cur = 3;
             lim = n - p < max_len ? n - p : max_len;              // (>= 4: p < end)
             state = c >= lo ? COMPARE : FETCH;
-            if (state == FETCH) { out[p] = (uint16_t)d; p += THREADS; }   // (never: the first candidate is within the window staged)
+            if (state == FETCH) {                                 // (never: the first candidate is within the window staged)
+                out[p] = (uint16_t)d;
+                if (LEN) lout[p] = 0;
+                p += THREADS;
+            }
             continue;
         }
         if (state == COMPARE) {
@@ -132,24 +150,94 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
         }
         if (fin) {
             out[p] = (uint16_t)bestd;
+            if (LEN) lout[p] = (uint8_t)(best - 3);               // (3 <= best <= 258: every walk that ends here compared once)
             p += THREADS;
             state = FETCH;
         }
     }
 }
 
+// LazyLz77Encoder's demotion, a launch of its own behind the chain kernel: len[p + 1] at a tile's last position
+// is another workgroup's.  For every listed position p < end: cd2[p] = 0 when p + 1 < end and len[p + 1] > len[p] — zlib's
+// deflate_slow rule as a function of the position alone; L(end) = 0 by contract, so nothing is read across a chunk.  Reads len,
+// writes only cd2[p] of its own positions: in place, no race (a neighbour's cd2 is never read for "has a candidate").
+//
+// Bandwidth-bound: 1 byte of len and 2 + 2 bytes of cd2 per position.  A chunk begins anywhere, so the tile's positions
+// [g0, g1) of the call's arrays are cut on the grid of 16: a lane takes 16 positions of the aligned middle with one 16-byte
+// load of len, one byte of the next group, and two 16-byte loads and stores of cd2 (adjacent lanes, adjacent groups); the up
+// to 15 positions in front and behind, which share their group with another tile or chunk, go one 2-byte store each
+// (demote_span, lfx_chain.h).
+constexpr uint32_t DEMOTE_THREADS = 256;
+static_assert(DEMOTE_GROUP == 16, "a lane's uint4 of lengths");
+__device__ __forceinline__ uint32_t demote_keep(uint32_t l, uint32_t nx, uint32_t k) {   // 0xFFFF: position k of the dword stays
+    return ((nx >> (8 * k)) & 0xFFu) > ((l >> (8 * k)) & 0xFFu) ? 0u : 0xFFFFu;
+}
+__global__ __launch_bounds__(DEMOTE_THREADS) void demote_kernel(const ChunkDesc *__restrict__ chunks, const ChainItem *__restrict__ items,
+                                                                uint32_t tile, const uint8_t *__restrict__ len, uint16_t *cd2) {
+    const ChainItem it = items[blockIdx.x];
+    const ChunkDesc ch = chunks[it.chunk];
+    const DemoteSpan s = demote_span(ch.in_off, ch.len, it.p0, tile);
+    const uint64_t g0 = s.g0, a = s.a, b = s.b, g1 = s.g1, gend = s.gend;
+    if (g0 >= g1) return;                                         // (never listed)
+    const uint32_t tid = threadIdx.x;
+    // the edges: [g0, a) and [b, g1), under 16 positions each — or the whole of an item under 31
+    if (tid < 32) {
+        const uint64_t g = g0 + tid;
+        if (g < a && g + 1 < gend && len[g + 1] > len[g]) cd2[g] = 0;
+    } else if (tid < 48) {
+        const uint64_t g = b + (tid - 32);
+        if (g < g1 && g + 1 < gend && len[g + 1] > len[g]) cd2[g] = 0;
+    }
+    for (uint64_t g = a + 16 * (uint64_t)tid; g < b; g += 16 * DEMOTE_THREADS) {
+        const uint4 l = *(const uint4 *)(len + g);
+        const uint32_t nb = g + 16 < gend ? len[g + 16] : 0u;    // (g + 16 == gend: position end - 1 stays, L(end) = 0)
+        uint4 *c = (uint4 *)(cd2 + g);
+        uint4 c0 = c[0], c1 = c[1];
+        const uint32_t lw[5] = {l.x, l.y, l.z, l.w, nb};
+        uint32_t keep[8];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint32_t nx = __builtin_amdgcn_alignbyte(lw[j + 1], lw[j], 1);   // the lengths one position on
+            keep[2 * j] = demote_keep(lw[j], nx, 0) | demote_keep(lw[j], nx, 1) << 16;
+            keep[2 * j + 1] = demote_keep(lw[j], nx, 2) | demote_keep(lw[j], nx, 3) << 16;
+        }
+        c0.x &= keep[0]; c0.y &= keep[1]; c0.z &= keep[2]; c0.w &= keep[3];
+        c1.x &= keep[4]; c1.y &= keep[5]; c1.z &= keep[6]; c1.w &= keep[7];
+        c[0] = c0;
+        c[1] = c1;
+    }
+}
+
 }  // namespace
 
 int launch_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, const ChainItem *items,
-                 uint32_t nitems, bool small, uint32_t window, uint32_t max_len, uint32_t depth, const uint16_t *cd, uint16_t *cd2) {
+                 uint32_t nitems, bool small, uint32_t window, uint32_t max_len, uint32_t depth, const uint16_t *cd, uint16_t *cd2,
+                 uint8_t *len) {
     (void)in_bytes;
     if (!nitems) return 0;
+    if (len) {
+        if (small)
+            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE_SMALL, 0, 256, uint8_t *>), dim3(nitems), dim3(256), 0, st, in, chunks, items, window,
+                               max_len, depth, cd, cd2, len);
+        else
+            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024, uint8_t *>), dim3(nitems), dim3(1024), 0, st, in, chunks, items,
+                               window, max_len, depth, cd, cd2, len);
+        return (int)hipGetLastError();
+    }
     if (small)
         hipLaunchKernelGGL((chain_kernel<CHAIN_TILE_SMALL, 0, 256>), dim3(nitems), dim3(256), 0, st, in, chunks, items, window, max_len,
                            depth, cd, cd2);
     else
         hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024>), dim3(nitems), dim3(1024), 0, st, in, chunks, items, window,
                            max_len, depth, cd, cd2);
+    return (int)hipGetLastError();
+}
+
+int launch_demote(hipStream_t st, const ChunkDesc *chunks, const ChainItem *items, uint32_t nitems, bool small, const uint8_t *len,
+                  uint16_t *cd2) {
+    if (!nitems) return 0;
+    hipLaunchKernelGGL(demote_kernel, dim3(nitems), dim3(DEMOTE_THREADS), 0, st, chunks, items, small ? CHAIN_TILE_SMALL : CHAIN_TILE,
+                       len, cd2);
     return (int)hipGetLastError();
 }
 

@@ -72,22 +72,26 @@ inline lfx_encode_opts norm_opts(const lfx_encode_opts *o) {
     if (d.max_length > MAX_LENGTH) d.max_length = MAX_LENGTH;    // default.rs:240
     return d;
 }
-// lz77_kind: the kind in bits 0..7; LFX_LZ77_CHAIN carries its depth in bits 8..15 (include/lfx.h).  The bits above bit 7 are
-// not read for the other kinds.
+// lz77_kind: the kind in bits 0..7; LFX_LZ77_CHAIN and LFX_LZ77_LAZY carry their depth in bits 8..15 (include/lfx.h).  The bits
+// above bit 7 are not read for the other kinds.
 inline int lz77_kind_of(const lfx_encode_opts &o) { return (int)((uint32_t)o.lz77_kind & 0xFFu); }
+// the kinds that run the chain stage
+inline bool lz77_chained(int kind) { return kind == LFX_LZ77_CHAIN || kind == LFX_LZ77_LAZY; }
 inline uint32_t chain_depth_of(const lfx_encode_opts &o) {
-    return lz77_kind_of(o) == LFX_LZ77_CHAIN ? ((uint32_t)o.lz77_kind >> 8) & 0xFFu : 0u;
+    return lz77_chained(lz77_kind_of(o)) ? ((uint32_t)o.lz77_kind >> 8) & 0xFFu : 0u;
 }
+// LazyLz77Encoder: the chain stage also demotes a position whose successor matches longer
+inline bool lazy_of(const lfx_encode_opts &o) { return lz77_kind_of(o) == LFX_LZ77_LAZY; }
 inline int check_opts(const lfx_encode_opts &o) {
     if (o.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
     if (o.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
-    if (lz77_kind_of(o) == LFX_LZ77_CHAIN && (chain_depth_of(o) == 0 || ((uint32_t)o.lz77_kind >> 16) != 0)) return LFX_E_ARG;
+    if (lz77_chained(lz77_kind_of(o)) && (chain_depth_of(o) == 0 || ((uint32_t)o.lz77_kind >> 16) != 0)) return LFX_E_ARG;
     return LFX_OK;
 }
-// E::compression_level() as lz77_level holds it (1 + LFX_LEVEL_*, 0: the kind's own): ChainLz77Encoder is Best unless the caller
-// says otherwise; no_compression() resets the header's level like any other (zlib.rs:471-475, gzip.rs:703)
+// E::compression_level() as lz77_level holds it (1 + LFX_LEVEL_*, 0: the kind's own): ChainLz77Encoder and LazyLz77Encoder are
+// Best unless the caller says otherwise; no_compression() resets the header's level like any other (zlib.rs:471-475, gzip.rs:703)
 inline uint8_t lz77_level_of(const lfx_encode_opts &o) {
-    if (o.lz77_level == 0 && lz77_kind_of(o) == LFX_LZ77_CHAIN && !o.no_compression) return 1 + LFX_LEVEL_BEST;
+    if (o.lz77_level == 0 && lz77_chained(lz77_kind_of(o)) && !o.no_compression) return 1 + LFX_LEVEL_BEST;
     return o.lz77_level;
 }
 inline PlanOpts plan_opts(int format, const lfx_encode_opts &o) {

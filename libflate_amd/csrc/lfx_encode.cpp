@@ -63,7 +63,8 @@ struct EncCall {
     const HostCodes *hc;
     const lfx_dict *dict;         // a preset dictionary with a usable tail, or nullptr
     bool match_v1;                // the first-generation match kernel: it once saw a lane-order violation (or LFX_MATCH_V1 is set)
-    uint32_t chain_depth;         // ChainLz77Encoder's depth; 0: any other kind — no chain stage, no second candidate buffer
+    uint32_t chain_depth;         // ChainLz77Encoder's or LazyLz77Encoder's depth; 0: any other kind — no chain stage, no second candidate buffer
+    bool lazy;                    // LazyLz77Encoder: the chain stage keeps the lengths and demotes behind them (§20)
     EncodeGeom g;
     uint64_t nspans = 0;          // partial results of the checksum kernels
     bool forked = false;          // the first half of the checksum's sweep is on the side stream already
@@ -166,6 +167,7 @@ int reserve_scratch(Ctx *c, EncCall &k) {
     if ((rc = c->d_pwgs.reserve(sizeof(ParseWg) * std::max<size_t>(k.g.pwgs.size(), 1)))) return rc;
     if (!hc && (rc = c->d_cd.reserve(2 * n + 64))) return rc;                   // candidate distances, 16 bits per position
     if (!hc && k.chain_depth && (rc = c->d_cd2.reserve(2 * n + 64))) return rc;  // ... and the chain stage's, which the parse then reads
+    if (!hc && k.chain_depth && k.lazy && (rc = c->d_len.reserve(n + 64))) return rc;   // ... and LazyLz77Encoder's length byte per position
     if (!hc && !match_v1 && (rc = c->d_glnk.reserve(264 * std::max<uint64_t>(lnk_units, 1)))) return rc;   // lfx_match7: link records (4 bytes) + ballot words (8 bytes per 64); lfx_match5: links (2 bytes)
     if (!hc && !match_v1 && (rc = c->d_ucount.reserve(4 * std::max<size_t>(nsegs, 1)))) return rc;   // lfx_match7: unresolved positions per segment
     if (!hc && match_v1 && (rc = c->d_md.reserve(4 * std::max<uint64_t>(n, 1)))) return rc;   // first-generation kernel: (length, distance) words
@@ -321,6 +323,8 @@ int stage_dict(Ctx *c, const EncCall &k) {
 
 // ChainLz77Encoder, behind the match stage whichever generation ran: the longest of the first chain_depth
 // candidates on every position's chain through cd → cd2, which the parse reads from here on.  One launch for all chunks.
+// LazyLz77Encoder (§20): the same launch also keeps the lengths, and a second one over the same work list takes the candidate
+// from every position whose successor's is longer.
 int stage_chain(Ctx *c, EncCall &k) {
     hipStream_t st = c->stream;
     const bool small = chain_small(k.plan.chunks);
@@ -331,10 +335,16 @@ int stage_chain(Ctx *c, EncCall &k) {
         if (int rc = c->d_chain_items.reserve(bytes)) return rc;
         HIP_TRY(hipMemcpyAsync(c->d_chain_items.p, c->chain_items.data(), bytes, hipMemcpyHostToDevice, st));
         LAUNCH_TRY(launch_chain(st, k.d_in, k.n, k.v.chunks, (const ChainItem *)c->d_chain_items.p, (uint32_t)c->chain_items.size(), small,
-                                k.po.window_size, k.po.max_length, k.chain_depth, k.v.cd, cd2));
+                                k.po.window_size, k.po.max_length, k.chain_depth, k.v.cd, cd2, k.lazy ? (uint8_t *)c->d_len.p : nullptr));
     }
     k.v.cd = cd2;
     c->phase("lz77_chain_cand");
+    if (k.lazy) {
+        if (!c->chain_items.empty())
+            LAUNCH_TRY(launch_demote(st, k.v.chunks, (const ChainItem *)c->d_chain_items.p, (uint32_t)c->chain_items.size(), small,
+                                     (const uint8_t *)c->d_len.p, cd2));
+        c->phase("lz77_lazy_demote");
+    }
     return LFX_OK;
 }
 
@@ -402,11 +412,11 @@ int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *
     c->n_ev = 0;
     c->phase("start");
     EncCall k{plan, po, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
-              po.lz77_kind == LFX_LZ77_CHAIN && !hc ? chain_depth : 0u,
+              (po.lz77_kind == LFX_LZ77_CHAIN || po.lz77_kind == LFX_LZ77_LAZY) && !hc ? chain_depth : 0u, po.lz77_kind == LFX_LZ77_LAZY,
               encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
-    if (k.chain_depth && k.dict) { c->set_error("LFX_LZ77_CHAIN with a preset dictionary is not supported"); return LFX_E_UNSUPPORTED; }
-    if (po.lz77_kind == LFX_LZ77_CHAIN && !hc && !chain_depth) { c->set_error("LFX_LZ77_CHAIN: this entry point does not serve it"); return LFX_E_UNSUPPORTED; }
+    if (k.chain_depth && k.dict) { c->set_error("LFX_LZ77_CHAIN / LFX_LZ77_LAZY with a preset dictionary is not supported"); return LFX_E_UNSUPPORTED; }
+    if ((po.lz77_kind == LFX_LZ77_CHAIN || po.lz77_kind == LFX_LZ77_LAZY) && !hc && !chain_depth) { c->set_error("LFX_LZ77_CHAIN / LFX_LZ77_LAZY: this entry point does not serve it"); return LFX_E_UNSUPPORTED; }
     if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)
     c->cur_nchunks = (uint32_t)plan.chunks.size();
     c->cur_nblocks = (uint32_t)plan.blocks.size();

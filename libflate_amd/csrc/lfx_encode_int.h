@@ -23,8 +23,9 @@ struct HostCodes {
 // caller folds either).  Leaves everything the emit stage needs in the context.
 // dict: a preset dictionary — the plan's CH_DICT chunks take their open candidates from it and the parse reads
 // its window; nullptr: the kernels and launches of a dictionary-less call, unchanged.
-// chain_depth: with po.lz77_kind == LFX_LZ77_CHAIN the depth the options name (chain_depth_of) — the chain stage
-// runs between the match and the parse; any other kind: not read, no stage, no second candidate buffer.
+// chain_depth: with po.lz77_kind == LFX_LZ77_CHAIN or LFX_LZ77_LAZY the depth the options name (chain_depth_of, DESIGN.md §19,
+// §20) — the chain stage runs between the match and the parse, for LFX_LZ77_LAZY with its demotion; any other kind: not read,
+// no stage, no second candidate buffer.
 int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *d_in, uint64_t n, int ck_mode,
                    const HostCodes *hc = nullptr, const lfx_dict *dict = nullptr, uint32_t chain_depth = 0);
 // Stage B: offsets → pack → framing.  `prefix` bytes are placed at the start of d_out; the DEFLATE bits start at bit
@@ -63,7 +64,7 @@ struct BatchCall {
     uint8_t *d_out;
     uint64_t out_lo, out_hi;      // the span of d_out the streams' ranges lie in
     const lfx_dict *dict = nullptr;   // lfx_encode_batch_dict_device: primes every stream's first chunk
-    uint32_t chain_depth = 0;         // LFX_LZ77_CHAIN: its depth
+    uint32_t chain_depth = 0;         // LFX_LZ77_CHAIN, LFX_LZ77_LAZY: the depth
 };
 int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &b, std::vector<uint64_t> &h_len,
                  std::vector<int32_t> &h_status, EncodeResult &res);
@@ -76,7 +77,7 @@ struct MembersCall {
     uint64_t cap, fill;           // fill: bytes of d_out to zero, min(cap, bound)
     lfx_member *members;
     uint32_t n_rec;               // records the caller has room for
-    uint32_t chain_depth = 0;     // LFX_LZ77_CHAIN: its depth
+    uint32_t chain_depth = 0;     // LFX_LZ77_CHAIN, LFX_LZ77_LAZY: the depth
 };
 int encode_members(Ctx *c, const Plan &plan, const PlanOpts &po, const MembersCall &m, EncodeResult &res);
 

@@ -21,7 +21,7 @@ struct GpuBatches {
     Ctx *c = nullptr;
     int format = 0;
     PlanOpts po;
-    uint32_t chain_depth = 0;           // LFX_LZ77_CHAIN: its depth (bytes mode; a coded batch brings its own code words)
+    uint32_t chain_depth = 0;           // LFX_LZ77_CHAIN, LFX_LZ77_LAZY: the depth (bytes mode; a coded batch brings its own code words)
     DevBuf d_in, d_out;
     PinVec h_out;                       // a batch's output lands here (page-locked) and goes to the sink from here: no copy between
     PinVec h_res;                       // result slot + the shared byte

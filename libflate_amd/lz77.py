@@ -137,6 +137,16 @@ class ChainLz77Encoder:
                 "window_size": self._window, "max_length": self._max_length}
 
 
+class LazyLz77Encoder(ChainLz77Encoder):
+    """This library's own Lz77Encode (LFX_LZ77_LAZY): ChainLz77Encoder's buffering and candidates with zlib's lazy
+    rule on top — a visited position whose successor has a longer match becomes a literal and the walk decides again one byte
+    on.  Smaller output than ChainLz77Encoder at the same `depth` (1..255), for one more pass over the candidates.  Accepted
+    wherever ChainLz77Encoder is; like it, it has no encode / flush of its own."""
+
+    def _opts(self):
+        return dict(super()._opts(), lz77_kind=_ffi.LZ77_LAZY | (self._depth if 0 <= self._depth <= 255 else 256) << 8)
+
+
 class NoCompressionLz77Encoder:
     """lib.rs:111-145: every byte a literal (still Huffman coded by the block encoder)."""
 

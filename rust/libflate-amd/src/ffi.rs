@@ -29,6 +29,9 @@ pub const LFX_LZ77_NOCOMPRESSION: i32 = 1;
 /// ChainLz77Encoder (include/lfx.h): the kind in bits 0..7, its depth (1..255) in bits 8..15
 pub const LFX_LZ77_CHAIN: i32 = 2;
 pub const fn lfx_lz77_chain_depth(depth: u8) -> i32 { LFX_LZ77_CHAIN | (depth as i32) << 8 }
+/// LazyLz77Encoder (include/lfx.h): ChainLz77Encoder with lazy matching; the depth (1..255) in bits 8..15 as well
+pub const LFX_LZ77_LAZY: i32 = 3;
+pub const fn lfx_lz77_lazy_depth(depth: u8) -> i32 { LFX_LZ77_LAZY | (depth as i32) << 8 }
 pub const LFX_FLUSH_NONE: i32 = 0;
 pub const LFX_FLUSH_SYNC: i32 = 2;
 pub const LFX_DEC_MULTI: u32 = 1;

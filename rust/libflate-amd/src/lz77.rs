@@ -106,6 +106,11 @@ impl<E: Lz77Encode + 'static> GpuLz77 for E {
             o.window_size = c.window_size as u32;
             o.max_length = c.max_length as u32;
             true
+        } else if let Some(c) = any.downcast_ref::<LazyLz77Encoder>() {
+            o.lz77_kind = ffi::lfx_lz77_lazy_depth(c.depth);      // (depth 0: LFX_E_ARG from the encoder's constructor)
+            o.window_size = c.window_size as u32;
+            o.max_length = c.max_length as u32;
+            true
         } else {
             // only the container header looks at these two (zlib.rs:212-220, gzip.rs:684)
             o.lz77_kind = ffi::LFX_LZ77_DEFAULT;
@@ -235,6 +240,26 @@ impl ChainLz77Encoder {
 impl Lz77Encode for ChainLz77Encoder {
     fn encode<S: Sink>(&mut self, _buf: &[u8], _sink: S) { panic!("libflate-amd: ChainLz77Encoder runs inside the encoders only (EncodeOptions::with_lz77)") }
     fn flush<S: Sink>(&mut self, _sink: S) { panic!("libflate-amd: ChainLz77Encoder runs inside the encoders only (EncodeOptions::with_lz77)") }
+    fn compression_level(&self) -> CompressionLevel { CompressionLevel::Best }
+    fn window_size(&self) -> u16 { self.window_size }
+}
+
+/// This library's own `Lz77Encode` (`LFX_LZ77_LAZY`, include/lfx.h): `ChainLz77Encoder`'s buffering and
+/// candidates with zlib's lazy rule on top — a visited position whose successor has a longer match becomes a literal, and the
+/// walk decides again one byte on.  Smaller output than `ChainLz77Encoder` at the same depth.  Like it, it only configures the
+/// device pipeline as the `E` of this crate's encoders; `Lz77Encode::encode` / `flush` panic.
+#[derive(Debug, Clone)]
+pub struct LazyLz77Encoder { depth: u8, window_size: u16, max_length: u16 }
+impl LazyLz77Encoder {
+    /// `depth`: 1..=255 candidates per position (0 is refused when the encoder is made: `LFX_E_ARG`)
+    pub fn new(depth: u8) -> Self { LazyLz77Encoder { depth, window_size: MAX_WINDOW_SIZE, max_length: MAX_LENGTH } }
+    pub fn with_window_size(self, window_size: u16) -> Self { LazyLz77Encoder { window_size: std::cmp::min(window_size, MAX_WINDOW_SIZE), ..self } }
+    pub fn with_max_length(self, max_length: u16) -> Self { LazyLz77Encoder { max_length: std::cmp::min(max_length, MAX_LENGTH), ..self } }
+    pub fn depth(&self) -> u8 { self.depth }
+}
+impl Lz77Encode for LazyLz77Encoder {
+    fn encode<S: Sink>(&mut self, _buf: &[u8], _sink: S) { panic!("libflate-amd: LazyLz77Encoder runs inside the encoders only (EncodeOptions::with_lz77)") }
+    fn flush<S: Sink>(&mut self, _sink: S) { panic!("libflate-amd: LazyLz77Encoder runs inside the encoders only (EncodeOptions::with_lz77)") }
     fn compression_level(&self) -> CompressionLevel { CompressionLevel::Best }
     fn window_size(&self) -> u16 { self.window_size }
 }
