@@ -59,7 +59,8 @@ enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1, LFX_LZ77_CHAIN = 2, LFX
  * lz77_kind & 0xFF is the kind; for LFX_LZ77_CHAIN bits 8..15 hold the depth K, 1..255 — there is no default depth.  Depth 0 or
  * any bit above 15 set: LFX_E_ARG.  For the kinds 0 and 1 the bits above bit 7 are not read.
  * Served by lfx_encode_device / _host, lfx_encode_batch_device, lfx_encoder_* (bytes mode), lfx_encode_members_* (BGZF too) and
- * lfx_encode_index_device.  LFX_E_UNSUPPORTED from the dictionary encode calls (a dictionary candidate has no chain behind
+ * lfx_encode_index_device; by the dictionary encode calls with a chain dictionary (lfx_dict_new_chain, below).
+ * LFX_E_UNSUPPORTED from the dictionary encode calls with a plain dictionary (a dictionary candidate has no chain behind
  * it) and from the N-GPU encode (lfx_encode_shard_prepare, lfx_sharded_encode_begin); the lfx_lz77 plug-in handle takes no
  * options and stays DefaultLz77Encoder. */
 #define LFX_LZ77_CHAIN_DEPTH(k) (LFX_LZ77_CHAIN | (k) << 8)
@@ -725,6 +726,32 @@ int lfx_encode_dict_host(lfx_ctx *c, int format, const lfx_encode_opts *o, const
 int lfx_encode_batch_dict_device(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
                                  uint32_t count, const void *d_in, const uint64_t *in_off, const uint64_t *in_len, void *d_out,
                                  const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status);
+
+/* ---- a chain dictionary: LFX_LZ77_CHAIN and LFX_LZ77_LAZY through a preset dictionary ----
+ * lfx_dict_new_chain makes a dictionary that also carries the hash chain of its own tail.  With it lfx_encode_dict_device,
+ * lfx_encode_dict_host and lfx_encode_batch_dict_device serve LFX_LZ77_CHAIN_DEPTH(K) and LFX_LZ77_LAZY_DEPTH(K); a dictionary
+ * made by lfx_dict_new keeps LFX_E_UNSUPPORTED for them.  For the kinds 0 and 1 and for every decode call a chain dictionary
+ * is a plain one.  Arguments, status and lifetime are lfx_dict_new's.
+ *
+ *  Let T be the usable tail (at most 32768 bytes), buf the stream's first chunk as above, b = T ‖ buf, n = |b| and
+ *  end = max(3, n) - 3.
+ *    - Every position < end counts as inserted once, in order: every position of T, and with them |T|-2 and |T|-1, whose
+ *      3-byte prefix runs into buf.
+ *    - The candidates of a chunk position i >= |T|, i < end, are the first K earlier occurrences of b[i..i+3] in b, most
+ *      recent first, cut off at the first one farther than window_size from i: the chunk's own occurrences, then |T|-1 and
+ *      |T|-2 where their prefix matches, then the dictionary's, youngest first.
+ *    - L(c) = 3 + the common prefix behind the three bytes, capped by max_length and by the end of b.  The longest wins,
+ *      among equal lengths the nearest (LFX_LZ77_CHAIN's rule).
+ *    - LFX_LZ77_CHAIN walks greedily from |T|.  LFX_LZ77_LAZY applies its rule there: position i is a literal when
+ *      L(i + 1) > L(i), with L = 0 for positions >= end.  Positions < |T| are never visited; the positions from
+ *      max(end, |T|) on are literals.
+ *  Later chunks are not primed: they are what LFX_LZ77_CHAIN / LFX_LZ77_LAZY make of them without a dictionary.  The container
+ *  is the one above (FDICT, DICTID, Adler-32 of the input only) with FLEVEL as the kinds 2 and 3 set it; LFX_GZIP stays
+ *  LFX_E_ARG; an empty dictionary primes nothing; no_compression is as above.
+ *  The chain is complete — it covers the whole tail, whatever window_size a call uses; the cut-off is applied from the chunk
+ *  position — takes 64 KiB of device memory, and is built by the first chained encode that takes the dictionary, on the
+ *  context's stream, and freed with the lfx_dict.  Nothing of a call stays in the context. */
+lfx_dict *lfx_dict_new_chain(lfx_ctx *c, const void *bytes, uint64_t len, int on_device, int *status);
 
 /* ---- plug-in: libflate_lz77::Lz77Encode (libflate_lz77/src/lib.rs:83-107) -----------------
  * Codes are delivered in batches: word = (val << 16) | dist; dist == 0 → Code::Literal(val),

@@ -44,6 +44,7 @@ EXPORTS = [
     "lfx_dict_new", "lfx_dict_id", "lfx_dict_free", "lfx_decode_dict_device", "lfx_decode_dict_host",
     "lfx_decode_batch_dict_device", "lfx_decoder_set_dict",
     "lfx_encode_dict_bound", "lfx_encode_dict_device", "lfx_encode_dict_host", "lfx_encode_batch_dict_device",
+    "lfx_dict_new_chain",
 ]
 
 
@@ -197,6 +198,8 @@ def lib():
     L.lfx_decode_batch_device.argtypes = [vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lfx_dict_new.restype = vp
     L.lfx_dict_new.argtypes = [vp, vp, u64, i32, C.POINTER(i32)]
+    L.lfx_dict_new_chain.restype = vp
+    L.lfx_dict_new_chain.argtypes = [vp, vp, u64, i32, C.POINTER(i32)]
     L.lfx_dict_id.restype = u32
     L.lfx_dict_id.argtypes = [vp]
     L.lfx_dict_free.argtypes = [vp]

@@ -421,21 +421,25 @@ class Context:
 class Dictionary:
     """A preset dictionary (lfx_dict): what zlib.compressobj(zdict=...) was given.  The last 32 KiB are the
     usable history; `id` is the Adler-32 of all bytes (RFC 1950's DICTID).  `data`: bytes-like, or a contiguous CUDA uint8
-    tensor.  Belongs to its Context and counts itself in and out of it like the other native handles."""
+    tensor.  Belongs to its Context and counts itself in and out of it like the other native handles.  chain=True
+    (lfx_dict_new_chain): the dictionary also carries the hash chain of its own tail, and the encode_dict_* calls
+    serve lz77.ChainLz77Encoder / LazyLz77Encoder with it; for everything else it is the same dictionary."""
 
-    def __init__(self, data, context=None):
+    def __init__(self, data, context=None, chain=False):
         self._h = None
         self._ctx = context if context is not None else default_context()
+        self.chain = bool(chain)
+        new = _ffi.lib().lfx_dict_new_chain if chain else _ffi.lib().lfx_dict_new
         st = C.c_int(0)
         if hasattr(data, "data_ptr"):
             if not data.is_cuda or data.dtype.itemsize != 1 or not data.is_contiguous():
                 raise TypeError("Dictionary: a tensor must be a contiguous CUDA uint8 tensor")
             import torch
             torch.cuda.current_stream(data.device).synchronize()
-            self._h = _ffi.lib().lfx_dict_new(self._ctx.handle, data.data_ptr(), data.numel(), 1, C.byref(st))
+            self._h = new(self._ctx.handle, data.data_ptr(), data.numel(), 1, C.byref(st))
         else:
             data = bytes(data)
-            self._h = _ffi.lib().lfx_dict_new(self._ctx.handle, data, len(data), 0, C.byref(st))
+            self._h = new(self._ctx.handle, data, len(data), 0, C.byref(st))
         if not self._h:
             raise (_ffi.DeviceError if st.value == _ffi.E_DEVICE else _ffi.LfxError)(st.value, self._ctx.last_error())
         self._ctx._retain()

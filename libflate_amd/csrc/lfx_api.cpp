@@ -239,11 +239,12 @@ static void dict_header(int format, const lfx_dict *dict, std::vector<uint8_t> &
     hdr[1] = flg;
     for (int sh = 24; sh >= 0; sh -= 8) hdr.push_back((uint8_t)(dict->id >> sh));
 }
-// ChainLz77Encoder and LazyLz77Encoder have no chain behind a dictionary candidate (Limits)
+// ChainLz77Encoder and LazyLz77Encoder have no chain behind a plain dictionary's candidate (Limits); a chain
+// dictionary (lfx_dict_new_chain, §21) brings its own
 static int chain_dict_refused(Ctx *c, const lfx_dict *dict, const lfx_encode_opts &d) {
-    if (!dict || !lz77_chained(lz77_kind_of(d))) return LFX_OK;
-    c->set_error(lazy_of(d) ? "lz77_kind: LFX_LZ77_LAZY with a preset dictionary is not supported"
-                            : "lz77_kind: LFX_LZ77_CHAIN with a preset dictionary is not supported");
+    if (!dict || dict->chain || !lz77_chained(lz77_kind_of(d))) return LFX_OK;
+    c->set_error(lazy_of(d) ? "lz77_kind: LFX_LZ77_LAZY with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"
+                            : "lz77_kind: LFX_LZ77_CHAIN with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)");
     return LFX_E_UNSUPPORTED;
 }
 // the stream's first LZ77 flush unit is the one the dictionary primes — where the options match at all and the dictionary

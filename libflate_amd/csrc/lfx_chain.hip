@@ -28,6 +28,7 @@
 
 #include "lfx_chain.h"
 #include "lfx_common.h"
+#include "lfx_dict_tab.h"
 
 namespace lfx {
 
@@ -46,20 +47,41 @@ __device__ __forceinline__ uint32_t lds1(const uint32_t *w, uint32_t off) { retu
 // demotes a position, and a position without a candidate is no match anyway; 257 and 258 stay apart).  Without LEN the
 // kernel is ChainLz77Encoder's, instruction for instruction, with its arguments: the length array is a parameter pack of
 // none (chain_kernel<TILE, WCAP, THREADS>) or of one uint8_t * (chain_kernel<TILE, WCAP, THREADS, uint8_t *>).
+//
+// DICT (a chain dictionary): the same pack begins with a ChainDict (chain_kernel<..., ChainDict> and
+// chain_kernel<..., ChainDict, uint8_t *>).  The tile belongs to a primed chunk and begins within window_size of its start: the
+// dictionary's tail T and its chain lie in front of position 0 in LDS — position -1 is T's last byte, through the unsigned
+// wrap the parse's dictionary instance uses — and a chain that reaches position 0 goes on into T.  Without the ChainDict
+// every `DICT ? :` below folds to what stood there before.
+template <typename... Extra> constexpr bool chain_has_dict = false;
+template <typename... Rest> constexpr bool chain_has_dict<ChainDict, Rest...> = true;
 __device__ __forceinline__ uint8_t *len_of() { return nullptr; }
 __device__ __forceinline__ uint8_t *len_of(uint8_t *len) { return len; }
+__device__ __forceinline__ uint8_t *len_of(const ChainDict &) { return nullptr; }
+__device__ __forceinline__ uint8_t *len_of(const ChainDict &, uint8_t *len) { return len; }
+__device__ __forceinline__ ChainDict dict_of() { return ChainDict{nullptr, nullptr, nullptr, 0u}; }
+__device__ __forceinline__ ChainDict dict_of(uint8_t *) { return ChainDict{nullptr, nullptr, nullptr, 0u}; }
+__device__ __forceinline__ ChainDict dict_of(const ChainDict &d) { return d; }
+__device__ __forceinline__ ChainDict dict_of(const ChainDict &d, uint8_t *) { return d; }
 
-template <uint32_t TILE, uint32_t WCAP, uint32_t THREADS, typename... Len>
+// 4 bytes from byte 4 * wi + ph (ph 0..3) of an array of ndw aligned dwords; what lies outside the array reads as 0
+__device__ __forceinline__ uint32_t dword_at(const uint32_t *__restrict__ w, int32_t wi, uint32_t ph, int32_t ndw) {
+    const uint32_t a = wi >= 0 && wi < ndw ? w[wi] : 0u;
+    const uint32_t b = ph != 0 && wi + 1 >= 0 && wi + 1 < ndw ? w[wi + 1] : 0u;
+    return __builtin_amdgcn_alignbyte(b, a, ph);
+}
+
+template <uint32_t TILE, uint32_t WCAP, uint32_t THREADS, typename... Extra>
 __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restrict__ in, const ChunkDesc *__restrict__ chunks,
                                                         const ChainItem *__restrict__ items, uint32_t window, uint32_t max_len,
                                                         uint32_t depth, const uint16_t *__restrict__ cd, uint16_t *__restrict__ cd2,
-                                                        Len... len) {
-    constexpr bool LEN = sizeof...(Len) != 0;
-    static_assert(sizeof...(Len) <= 1, "no length array or one");
-    // bytes [lo, hi): at most WCAP + TILE + MAX_LENGTH, + the byte phase of lo on the dword grid (3), + what the last compare
-    // step and its three-dword read reach past the last byte that counts (11)
-    constexpr uint32_t BW = (WCAP + TILE + MAX_LENGTH + 3 + 11 + 3) / 4 + 1;
-    constexpr uint32_t CW = (WCAP + TILE + 1 + 1) / 2 + 1;          // candidates [lo, p1), + their phase on the dword grid
+                                                        Extra... extra) {
+    constexpr bool DICT = chain_has_dict<Extra...>;
+    constexpr bool LEN = sizeof...(Extra) != (DICT ? 1 : 0);
+    static_assert(sizeof...(Extra) <= (DICT ? 2 : 1), "a chain dictionary or none, then no length array or one");
+    static_assert(!DICT || WCAP == MAX_WINDOW, "the dictionary's tail takes the room of the window in front of position 0");
+    constexpr uint32_t BW = chain_lds_bytes_dw(TILE, WCAP);
+    constexpr uint32_t CW = chain_lds_cand_dw(TILE, WCAP);
     static_assert(4 * (BW + CW) <= 160 * 1024, "one workgroup's LDS");
     __shared__ uint32_t s_b[BW];
     __shared__ uint32_t s_c[CW];
@@ -75,6 +97,10 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
     const uint32_t p1 = p0 + TILE < end ? p0 + TILE : end;        // positions [p0, p1)
     const uint32_t hi = (uint64_t)p0 + TILE + max_len < n ? p0 + TILE + max_len : n;
     const uint32_t tid = threadIdx.x;
+    // DICT: T's last n_t bytes in front of the chunk (lo == 0: p0 < window <= WCAP); a tile that is not listed for this
+    // instance (never) has n_t == 0 and runs as the instance without a dictionary does
+    const ChainDict dict = dict_of(extra...);
+    const ChainDictFill df = DICT && (ch.flags & CH_DICT) && lo == 0 ? chain_dict_fill(dict.usable, window, p0) : ChainDictFill{0u, 0u, 0u};
     // ---- stage the bytes and the candidates on their own dword grids: position q's byte sits at LDS byte q - lo + sh, its
     //      candidate at entry q - lo + csh.  (The dwords that hold the first and the last byte may reach up to three bytes
     //      outside [lo, hi), as the parse's reads do; a dword that holds no byte of it is not read.)
@@ -82,17 +108,58 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
     const uint32_t sh = (uint32_t)a0 & 3;
     const uint32_t *gw = (const uint32_t *)(a0 - sh);
     const uint32_t ndw = (hi - lo + sh + 3) >> 2;
-    for (uint32_t k = tid; k < ndw && k < BW; k += THREADS) s_b[k] = gw[k];
+    if (DICT) { for (uint32_t k = tid; k < ndw && df.dw_t + k < BW; k += THREADS) s_b[df.dw_t + k] = gw[k]; }
+    else for (uint32_t k = tid; k < ndw && k < BW; k += THREADS) s_b[k] = gw[k];
     const uint64_t e0 = ch.in_off + lo;
     const uint32_t csh = (uint32_t)e0 & 1;
     const uint32_t *gc = (const uint32_t *)(cd + (e0 - csh));
     const uint32_t ncw = (p1 - lo + csh + 1) >> 1;
-    for (uint32_t k = tid; k < ncw && k < CW; k += THREADS) s_c[k] = gc[k];
+    if (DICT) { for (uint32_t k = tid; k < ncw && df.dw_c + k < CW; k += THREADS) s_c[df.dw_c + k] = gc[k]; }
+    else for (uint32_t k = tid; k < ncw && k < CW; k += THREADS) s_c[k] = gc[k];
+    if (DICT && df.n_t) {
+        // T and its chain, whole dwords in front of the chunk's first one: LDS dword m of the bytes holds the window's bytes
+        // from MAX_WINDOW + 4 * (m - dw_t) - sh on, LDS dword m of the candidates the window's entries from
+        // MAX_WINDOW + 2 * (m - dw_c) - csh on — off the source's dword grid by the chunk's own phase.  The chunk's first dword
+        // keeps T's last sh bytes, and the two positions whose prefix runs into the chunk have no entry in cdt: all of that is
+        // patched behind the barrier.
+        const uint32_t *tw = (const uint32_t *)dict.win;
+        const uint32_t *tc = (const uint32_t *)dict.cdt;
+        const int32_t wb = (int32_t)(MAX_WINDOW / 4) - (int32_t)df.dw_t - (sh ? 1 : 0);
+        const int32_t wc = (int32_t)(MAX_WINDOW / 2) - (int32_t)df.dw_c - (int32_t)csh;
+        for (uint32_t m = tid; m < df.dw_t; m += THREADS) s_b[m] = dword_at(tw, wb + (int32_t)m, (4 - sh) & 3, MAX_WINDOW / 4);
+        for (uint32_t m = tid; m < df.dw_c; m += THREADS) s_c[m] = dword_at(tc, wc + (int32_t)m, csh ? 2u : 0u, MAX_WINDOW / 2);
+        __syncthreads();
+        if (tid < sh) ((uint8_t *)s_b)[4 * df.dw_t + tid] = dict.win[MAX_WINDOW - sh + tid];
+        if (tid == 64) {
+            // The links of |T|-1 and |T|-2 (n >= 4 here: both are inserted, and their prefixes are whole).  |T|-1 links to |T|-2
+            // if their prefixes agree, otherwise to the table's last position of its prefix; |T|-2 to the table's.
+            const uint32_t t = dict.usable;
+            const uint8_t *b = in + ch.in_off, *te = dict.win + MAX_WINDOW;
+            const uint32_t pre1 = (uint32_t)te[-1] | (uint32_t)b[0] << 8 | (uint32_t)b[1] << 16;
+            const uint32_t pre2 = t >= 2 ? (uint32_t)te[-2] | (uint32_t)te[-1] << 8 | (uint32_t)b[0] << 16 : 0xFFFFFFFFu;
+            uint32_t l1 = 0, l2 = 0;
+            if (t >= 3) {
+                const uint32_t j2 = tab_lookup(dict.tab, pre2);
+                if (j2 != 0xFFFFFFFFu) l2 = t - 2 - j2;
+            }
+            if (pre1 == pre2) l1 = 1;
+            else if (t >= 3) {
+                const uint32_t j1 = tab_lookup(dict.tab, pre1);
+                if (j1 != 0xFFFFFFFFu) l1 = t - 1 - j1;
+            }
+            uint16_t *cw = (uint16_t *)s_c;
+            const uint32_t z = 2 * df.dw_c + csh;                 // position 0's entry (>= 1: n_t >= 1)
+            cw[z - 1] = (uint16_t)l1;
+            if (z >= 2) cw[z - 2] = (uint16_t)l2;                 // (z == 1: n_t == 1, there is no |T|-2 in reach)
+        }
+    }
     __syncthreads();
     const uint16_t *c16 = (const uint16_t *)s_c;
-    const uint32_t boff = sh - lo, coff = csh - lo;              // (unsigned wrap: q + boff = q - lo + sh)
+    // (unsigned wrap: q + boff = q - lo + sh; DICT: + the dwords in front, and q may be a wrapped position in front of 0)
+    const uint32_t boff = DICT ? sh - lo + 4 * df.dw_t : sh - lo, coff = DICT ? csh - lo + 2 * df.dw_c : csh - lo;
+    const uint32_t lo_t = lo - df.n_t;                            // DICT: the first position staged, wrapped
     uint16_t *out = cd2 + ch.in_off;
-    uint8_t *lout = LEN ? len_of(len...) + ch.in_off : nullptr;
+    uint8_t *lout = LEN ? len_of(extra...) + ch.in_off : nullptr;
 
     enum : uint32_t { FETCH = 0, COMPARE = 1, HOP = 2 };
     uint32_t state = FETCH;
@@ -102,7 +169,7 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
         if (state == FETCH) {
             if (p >= p1) break;
             const uint32_t d = c16[p + coff];
-            if (d == 0 || d > p) {                                // no candidate (d > p: never, a distance stays inside the chunk)
+            if (d == 0 || (!DICT && d > p)) {                     // no candidate (d > p: never, a distance stays inside the chunk — or, DICT, reaches into T)
                 out[p] = 0;
                 if (LEN) lout[p] = 0;
                 p += THREADS;
@@ -114,7 +181,7 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
             bestd = d;
             cur = 3;
             lim = n - p < max_len ? n - p : max_len;              // (>= 4: p < end)
-            state = c >= lo ? COMPARE : FETCH;
+            state = (DICT ? (int32_t)(c - lo_t) >= 0 : c >= lo) ? COMPARE : FETCH;
             if (state == FETCH) {                                 // (never: the first candidate is within the window staged)
                 out[p] = (uint16_t)d;
                 if (LEN) lout[p] = 0;
@@ -136,10 +203,11 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
         bool fin = best >= lim || left == 0;
         if (!fin) {
             const uint32_t dq = c16[c + coff];
-            fin = dq == 0 || dq > c;
+            fin = dq == 0 || (!DICT && dq > c);
             if (!fin) {
                 const uint32_t c2 = c - dq;
-                fin = p - c2 > window || c2 < lo;                 // (c2 < lo: never, lo <= p0 - min(window, WCAP))
+                // (c2 in front of what is staged: never, lo <= p0 - min(window, WCAP) — DICT: T's last window - p0 bytes)
+                fin = p - c2 > window || (DICT ? (int32_t)(c2 - lo_t) < 0 : c2 < lo);
                 if (!fin) {
                     c = c2;
                     // longer than `best` only if the byte at that index matches too (best < lim: p + best < n)
@@ -212,24 +280,45 @@ __global__ __launch_bounds__(DEMOTE_THREADS) void demote_kernel(const ChunkDesc 
 
 int launch_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, const ChainItem *items,
                  uint32_t nitems, bool small, uint32_t window, uint32_t max_len, uint32_t depth, const uint16_t *cd, uint16_t *cd2,
-                 uint8_t *len) {
+                 uint8_t *len, uint32_t n_plain, const ChainDict *dict) {
     (void)in_bytes;
     if (!nitems) return 0;
-    if (len) {
-        if (small)
-            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE_SMALL, 0, 256, uint8_t *>), dim3(nitems), dim3(256), 0, st, in, chunks, items, window,
-                               max_len, depth, cd, cd2, len);
+    if (!dict || n_plain > nitems) n_plain = nitems;
+    if (n_plain) {
+        if (len) {
+            if (small)
+                hipLaunchKernelGGL((chain_kernel<CHAIN_TILE_SMALL, 0, 256, uint8_t *>), dim3(n_plain), dim3(256), 0, st, in, chunks, items, window,
+                                   max_len, depth, cd, cd2, len);
+            else
+                hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024, uint8_t *>), dim3(n_plain), dim3(1024), 0, st, in, chunks, items,
+                                   window, max_len, depth, cd, cd2, len);
+        } else if (small)
+            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE_SMALL, 0, 256>), dim3(n_plain), dim3(256), 0, st, in, chunks, items, window, max_len,
+                               depth, cd, cd2);
         else
-            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024, uint8_t *>), dim3(nitems), dim3(1024), 0, st, in, chunks, items,
-                               window, max_len, depth, cd, cd2, len);
-        return (int)hipGetLastError();
+            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024>), dim3(n_plain), dim3(1024), 0, st, in, chunks, items, window,
+                               max_len, depth, cd, cd2);
+        if (const int rc = (int)hipGetLastError()) return rc;
     }
-    if (small)
-        hipLaunchKernelGGL((chain_kernel<CHAIN_TILE_SMALL, 0, 256>), dim3(nitems), dim3(256), 0, st, in, chunks, items, window, max_len,
-                           depth, cd, cd2);
-    else
-        hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024>), dim3(nitems), dim3(1024), 0, st, in, chunks, items, window,
-                           max_len, depth, cd, cd2);
+    // the tiles that reach a chain dictionary: the dictionary instance, with the tail's 32 KiB and its chain's
+    // 64 KiB in front of the chunk — one workgroup of 16 wavefronts per CU, for a batch of small records as well
+    const uint32_t nd = nitems - n_plain;
+    if (nd) {
+        const ChainItem *di = items + n_plain;
+        if (len) {
+            if (small)
+                hipLaunchKernelGGL((chain_kernel<CHAIN_TILE_SMALL, MAX_WINDOW, 1024, ChainDict, uint8_t *>), dim3(nd), dim3(1024), 0, st, in, chunks,
+                                   di, window, max_len, depth, cd, cd2, *dict, len);
+            else
+                hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024, ChainDict, uint8_t *>), dim3(nd), dim3(1024), 0, st, in, chunks, di,
+                                   window, max_len, depth, cd, cd2, *dict, len);
+        } else if (small)
+            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE_SMALL, MAX_WINDOW, 1024, ChainDict>), dim3(nd), dim3(1024), 0, st, in, chunks, di, window,
+                               max_len, depth, cd, cd2, *dict);
+        else
+            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024, ChainDict>), dim3(nd), dim3(1024), 0, st, in, chunks, di, window,
+                               max_len, depth, cd, cd2, *dict);
+    }
     return (int)hipGetLastError();
 }
 

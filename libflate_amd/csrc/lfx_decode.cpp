@@ -253,7 +253,7 @@ extern "C" int lfx_decode_dict_host(lfx_ctx *cc, int format, const lfx_dict *dic
 // A dictionary belongs to its context.  The id is computed on the device (the checksum kernels of the trailer check) over ALL
 // bytes; the last min(len, 32768) of them are kept: at the end of a 32 KiB device window, and on the host (stream decoders).
 extern "C" void lfx_dict_free(lfx_dict *d);
-extern "C" lfx_dict *lfx_dict_new(lfx_ctx *cc, const void *bytes, uint64_t len, int on_device, int *status) try {
+static lfx_dict *dict_new(lfx_ctx *cc, const void *bytes, uint64_t len, int on_device, int *status, bool chain) {
     if (status) *status = LFX_OK;
     if (!cc) { if (status) *status = LFX_E_DEVICE; return nullptr; }
     if (!bytes && len) { if (status) *status = LFX_E_ARG; return nullptr; }
@@ -263,6 +263,7 @@ extern "C" lfx_dict *lfx_dict_new(lfx_ctx *cc, const void *bytes, uint64_t len, 
     hipStream_t st = c->stream;
     lfx_dict *d = new lfx_dict();
     d->c = c;
+    d->chain = chain;
     auto fail = [&](int rc) -> lfx_dict * { if (status) *status = rc; lfx_dict_free(d); return nullptr; };
     if (hipMalloc((void **)&d->d_win, MAX_WINDOW) != hipSuccess) { d->d_win = nullptr; return fail(LFX_E_OOM); }
     if (hipMemsetAsync(d->d_win, 0, MAX_WINDOW, st) != hipSuccess) return fail(LFX_E_DEVICE);
@@ -288,6 +289,13 @@ extern "C" lfx_dict *lfx_dict_new(lfx_ctx *cc, const void *bytes, uint64_t len, 
     if (hipStreamSynchronize(st) != hipSuccess) return fail(LFX_E_DEVICE);
     if (len) d->id = ((const EncodeResult *)c->h_res)->adler32;
     return d;
+}
+extern "C" lfx_dict *lfx_dict_new(lfx_ctx *cc, const void *bytes, uint64_t len, int on_device, int *status) try {
+    return dict_new(cc, bytes, len, on_device, status, false);
+} LFX_ABI_CATCH_NEW
+// a chain dictionary: the same object, marked; its chain is the first chained encode's to build
+extern "C" lfx_dict *lfx_dict_new_chain(lfx_ctx *cc, const void *bytes, uint64_t len, int on_device, int *status) try {
+    return dict_new(cc, bytes, len, on_device, status, true);
 } LFX_ABI_CATCH_NEW
 extern "C" uint32_t lfx_dict_id(const lfx_dict *d) { return d ? d->id : 1; }
 extern "C" void lfx_dict_free(lfx_dict *d) {
@@ -298,6 +306,7 @@ extern "C" void lfx_dict_free(lfx_dict *d) {
         (void)hipStreamSynchronize(d->c->stream);
         (void)hipFree(d->d_win);
         if (d->d_tab) (void)hipFree(d->d_tab);      // (the encode's prefix table)
+        if (d->d_cdt) (void)hipFree(d->d_cdt);      // (a chain dictionary's chain)
     }
     delete d;
 }

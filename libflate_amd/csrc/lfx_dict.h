@@ -1,5 +1,5 @@
 // lfx_dict.h — a preset dictionary (C ABI: lfx_dict_*) as the decode paths see it, and the prefix table the
-// encode paths add to it on their first use (DESIGN §18).  Internal.
+// encode paths add to it on their first use (DESIGN §18, §21).  Internal.
 #pragma once
 #include <stdint.h>
 
@@ -22,5 +22,10 @@ struct lfx_dict {
     // (under the context's lock) and kept; lfx_dict_new and the decode paths never touch it
     mutable uint64_t *d_tab = nullptr;
     mutable bool tab_built = false;
+    // a chain dictionary (lfx_dict_new_chain): the tail's own hash chain, 16 bits per position of d_win
+    // (lfx_dict_enc.hip), built by the first chained encode that takes this dictionary and kept, as d_tab is
+    bool chain = false;
+    mutable uint16_t *d_cdt = nullptr;
+    mutable bool cdt_built = false;
     const uint8_t *d_end() const { return d_win + lfx::MAX_WINDOW; }
 };

@@ -16,6 +16,9 @@ constexpr uint32_t DICT_TAB_BITS = 16;
 constexpr uint32_t DICT_TAB_SLOTS = 1u << DICT_TAB_BITS;
 constexpr size_t DICT_TAB_BYTES = 8ull * DICT_TAB_SLOTS;
 
+// the hash chain of a chain dictionary's tail: 16 bits per position of the 32 KiB window d_win (64 KiB)
+constexpr size_t DICT_CHAIN_BYTES = 2ull * MAX_WINDOW;
+
 // one workgroup of the dictionary candidate kernel: positions [p0, p0 + 256) of a primed chunk
 struct DictItem {
     uint32_t chunk;
@@ -37,6 +40,9 @@ inline void dict_items(const std::vector<ChunkDesc> &chunks, uint32_t window, st
 
 // the table of the tail that ends the window d_win (lfx_dict::d_win) → tab (DICT_TAB_BYTES, cleared here)
 int launch_dict_table(hipStream_t st, const uint8_t *d_win, uint32_t usable, uint64_t *tab);
+// the chain of the same tail → cdt (DICT_CHAIN_BYTES, cleared here): cdt[MAX_WINDOW - usable + j] = the distance from the tail's
+// position j to the most recent earlier one with the same 3 bytes, 0 where there is none or j > usable - 3
+int launch_dict_chain(hipStream_t st, const uint8_t *d_win, uint32_t usable, uint16_t *cdt);
 // behind the match stage: cd[p] of the items' positions where it is 0 ← the distance to the most recent occurrence in the
 // dictionary, if that is within `window`
 int launch_dict_cand(hipStream_t st, const uint8_t *in, const ChunkDesc *chunks, const DictItem *items, uint32_t nitems,

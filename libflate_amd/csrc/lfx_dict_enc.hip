@@ -17,13 +17,11 @@
 
 #include "lfx_common.h"
 #include "lfx_dict_enc.h"
+#include "lfx_dict_tab.h"
 
 namespace lfx {
 
 namespace {
-
-constexpr uint64_t TAB_USED = 1ull << 56;
-__device__ __forceinline__ uint32_t tab_hash(uint32_t prefix) { return (prefix * 0x9E3779B1u) >> (32 - DICT_TAB_BITS); }
 
 // one thread per position j <= usable - 3 of the tail (win + MAX_WINDOW - usable is its first byte)
 __global__ __launch_bounds__(256) void dict_table_kernel(const uint8_t *__restrict__ win, uint32_t usable, unsigned long long *__restrict__ tab) {
@@ -41,16 +39,30 @@ __global__ __launch_bounds__(256) void dict_table_kernel(const uint8_t *__restri
     }
 }
 
-// → the last position j <= |T|-3 of the tail that holds `prefix`, or 0xFFFFFFFF
-__device__ __forceinline__ uint32_t tab_lookup(const unsigned long long *__restrict__ tab, uint32_t prefix) {
-    const uint32_t key = (uint32_t)(TAB_USED >> 32) | prefix;
-    uint32_t h = tab_hash(prefix);
-    for (uint32_t probe = 0; probe < DICT_TAB_SLOTS; ++probe, h = (h + 1) & (DICT_TAB_SLOTS - 1)) {
-        const unsigned long long cur = tab[h];
-        if (cur == 0) return 0xFFFFFFFFu;
-        if ((uint32_t)(cur >> 32) == key) return (uint32_t)cur;
-    }
-    return 0xFFFFFFFFu;
+// The dictionary's own hash chain: cdt[MAX_WINDOW - usable + j] = the distance from position j <= usable - 3
+// of the tail to the most recent earlier position with the same 3 bytes, 0 where there is none — on the grid of d_win, so
+// that a chunk position's offset in front of the chunk indexes the bytes and the links alike.  Complete: no window cuts it.
+// Built once per dictionary, so the plainest exact method serves: a workgroup keeps the prefixes of every position up to its
+// own 1024 in LDS, and each thread scans back from its position to the first equal one.
+constexpr uint32_t DICT_CHAIN_THREADS = 1024;
+__global__ __launch_bounds__(DICT_CHAIN_THREADS) void dict_chain_kernel(const uint8_t *__restrict__ win, uint32_t usable,
+                                                                        uint16_t *__restrict__ cdt) {
+    __shared__ uint32_t s_key[MAX_WINDOW];
+    if (usable < 3) return;
+    const uint32_t npos = usable - 2;                              // positions [0, usable - 3]
+    const uint32_t j0 = blockIdx.x * DICT_CHAIN_THREADS;
+    const uint32_t jtop = j0 + DICT_CHAIN_THREADS < npos ? j0 + DICT_CHAIN_THREADS : npos;
+    const uint8_t *t = win + (MAX_WINDOW - usable);
+    for (uint32_t k = threadIdx.x; k < jtop; k += DICT_CHAIN_THREADS)
+        s_key[k] = (uint32_t)t[k] | (uint32_t)t[k + 1] << 8 | (uint32_t)t[k + 2] << 16;   // (k + 2 <= usable - 1)
+    __syncthreads();
+    const uint32_t j = j0 + threadIdx.x;
+    if (j >= npos) return;
+    const uint32_t key = s_key[j];
+    uint32_t d = 0;
+    for (uint32_t k = j; k-- > 0;)
+        if (s_key[k] == key) { d = j - k; break; }
+    cdt[MAX_WINDOW - usable + j] = (uint16_t)d;                    // (d <= 32765)
 }
 
 // One workgroup per item: 256 positions of one primed chunk, from p0 on.
@@ -84,6 +96,14 @@ int launch_dict_table(hipStream_t st, const uint8_t *d_win, uint32_t usable, uin
     if (hipMemsetAsync(tab, 0, DICT_TAB_BYTES, st) != hipSuccess) return (int)hipGetLastError();
     if (usable < 3) return 0;
     hipLaunchKernelGGL(dict_table_kernel, dim3((usable - 2 + 255) / 256), dim3(256), 0, st, d_win, usable, (unsigned long long *)tab);
+    return (int)hipGetLastError();
+}
+
+int launch_dict_chain(hipStream_t st, const uint8_t *d_win, uint32_t usable, uint16_t *cdt) {
+    if (hipMemsetAsync(cdt, 0, DICT_CHAIN_BYTES, st) != hipSuccess) return (int)hipGetLastError();
+    if (usable < 3) return 0;
+    hipLaunchKernelGGL(dict_chain_kernel, dim3((usable - 2 + DICT_CHAIN_THREADS - 1) / DICT_CHAIN_THREADS), dim3(DICT_CHAIN_THREADS), 0, st,
+                       d_win, usable, cdt);
     return (int)hipGetLastError();
 }
 

@@ -325,17 +325,37 @@ int stage_dict(Ctx *c, const EncCall &k) {
 // candidates on every position's chain through cd → cd2, which the parse reads from here on.  One launch for all chunks.
 // LazyLz77Encoder (§20): the same launch also keeps the lengths, and a second one over the same work list takes the candidate
 // from every position whose successor's is longer.
+//
+// A chain dictionary (§21): stage_dict has run in front and left, in cd, every primed position's first dictionary candidate.
+// The tiles of the primed chunks within window_size of their start form a second run of the work list and go to the
+// dictionary instance, which follows the chain on into the dictionary's tail — through the tail's own chain, built here the
+// first time the dictionary serves a chained encode, and kept.
 int stage_chain(Ctx *c, EncCall &k) {
     hipStream_t st = c->stream;
+    const lfx_dict *d = k.dict;
     const bool small = chain_small(k.plan.chunks);
-    chain_items(k.plan.chunks, small ? CHAIN_TILE_SMALL : CHAIN_TILE, c->chain_items);
+    uint32_t n_plain = 0;
+    chain_items_dict(k.plan.chunks, small ? CHAIN_TILE_SMALL : CHAIN_TILE, k.po.window_size, d != nullptr, c->chain_items, n_plain);
     uint16_t *cd2 = (uint16_t *)c->d_cd2.p;
+    ChainDict cdict{nullptr, nullptr, nullptr, 0u};
+    if (n_plain < c->chain_items.size()) {
+        if (!d->d_cdt) {
+            if (hipMalloc((void **)&d->d_cdt, DICT_CHAIN_BYTES) != hipSuccess) { d->d_cdt = nullptr; c->set_error("out of device memory"); return LFX_E_OOM; }
+            d->cdt_built = false;
+        }
+        if (!d->cdt_built) {
+            LAUNCH_TRY(launch_dict_chain(st, d->d_win, d->usable, d->d_cdt));
+            d->cdt_built = true;
+        }
+        cdict = ChainDict{d->d_win, d->d_cdt, (const unsigned long long *)d->d_tab, d->usable};   // (d_tab: stage_dict's, the chunks are the same)
+    }
     if (!c->chain_items.empty()) {
         const size_t bytes = sizeof(ChainItem) * c->chain_items.size();
         if (int rc = c->d_chain_items.reserve(bytes)) return rc;
         HIP_TRY(hipMemcpyAsync(c->d_chain_items.p, c->chain_items.data(), bytes, hipMemcpyHostToDevice, st));
         LAUNCH_TRY(launch_chain(st, k.d_in, k.n, k.v.chunks, (const ChainItem *)c->d_chain_items.p, (uint32_t)c->chain_items.size(), small,
-                                k.po.window_size, k.po.max_length, k.chain_depth, k.v.cd, cd2, k.lazy ? (uint8_t *)c->d_len.p : nullptr));
+                                k.po.window_size, k.po.max_length, k.chain_depth, k.v.cd, cd2, k.lazy ? (uint8_t *)c->d_len.p : nullptr,
+                                n_plain, cdict.win ? &cdict : nullptr));
     }
     k.v.cd = cd2;
     c->phase("lz77_chain_cand");
@@ -415,7 +435,7 @@ int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *
               (po.lz77_kind == LFX_LZ77_CHAIN || po.lz77_kind == LFX_LZ77_LAZY) && !hc ? chain_depth : 0u, po.lz77_kind == LFX_LZ77_LAZY,
               encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
-    if (k.chain_depth && k.dict) { c->set_error("LFX_LZ77_CHAIN / LFX_LZ77_LAZY with a preset dictionary is not supported"); return LFX_E_UNSUPPORTED; }
+    if (k.chain_depth && k.dict && !k.dict->chain) { c->set_error("LFX_LZ77_CHAIN / LFX_LZ77_LAZY with a preset dictionary is not supported: the dictionary has no chain (lfx_dict_new_chain)"); return LFX_E_UNSUPPORTED; }
     if ((po.lz77_kind == LFX_LZ77_CHAIN || po.lz77_kind == LFX_LZ77_LAZY) && !hc && !chain_depth) { c->set_error("LFX_LZ77_CHAIN / LFX_LZ77_LAZY: this entry point does not serve it"); return LFX_E_UNSUPPORTED; }
     if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)
     c->cur_nchunks = (uint32_t)plan.chunks.size();

@@ -77,7 +77,10 @@ def _compress(fmt, data, zdict, options, context, lz77=None):
     if zdict is None:
         return ctx.encode_host(fmt, data, opts)
     own = not hasattr(zdict, "handle")
-    d = Dictionary(zdict, ctx) if own else zdict
+    # (bytes: the dictionary is made here, with a chain of its own when the parse is a chained one; a caller's
+    # Dictionary is taken as it was made)
+    chained = opts is not None and (opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY)
+    d = Dictionary(zdict, ctx, chain=chained) if own else zdict
     try:
         return ctx.encode_dict_host(fmt, d, data, opts)
     finally:
