@@ -77,6 +77,26 @@ enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1, LFX_LZ77_CHAIN = 2, LFX
  * Bits 8..15 hold the depth K, 1..255; depth 0 or any bit above 15 set: LFX_E_ARG.  Served and refused (LFX_E_UNSUPPORTED)
  * by the same entry points as LFX_LZ77_CHAIN. */
 #define LFX_LZ77_LAZY_DEPTH(k) (LFX_LZ77_LAZY | (k) << 8)
+/* lfx_encode_opts::dynamic_huffman.  0: fixed codes for every block (fixed_huffman_codes(), encode.rs:107-110).  1, and every
+ * value other than 0 and 2: dynamic codes for every block (the reference's default).
+ * LFX_HUFFMAN_AUTO (2) — opt-in, not a reference option: per block the smallest of the dynamic, the fixed and
+ * the stored form.  (Until this value was defined, 2 was read as "non-zero, so dynamic": it no longer is.)
+ *  - The plan, the LZ77 code words, the block boundaries and the container header (FLEVEL, XFL) are those of
+ *    dynamic_huffman = 1, for every lz77_kind.
+ *  - Every block that plan makes a dynamic block is a candidate; its stored blocks (no_compression, the zlib sync marker) are
+ *    not touched.  For a candidate, D = the bits of its dynamic form (3 + header + symbols); F = 3 + the sum over its own symbol
+ *    counts, EndOfBlock included, of count * (fixed code width + extra bits); S = 8 * in_len + 42, the stored form at its worst
+ *    alignment, so that the choice does not depend on the bit phase.  S is eligible only when the block has input bytes behind
+ *    it — bytes mode, not lfx_encoder_write_codes — and 1 <= in_len <= 65535.
+ *  - Stored, when S is eligible and S < min(D, F); otherwise fixed, when F <= D; otherwise dynamic.
+ *  - A block chosen dynamic carries exactly the bits it has in the dynamic_huffman = 1 encode of the same call, a block chosen
+ *    fixed those of the = 0 encode, each shifted to where it lands.  The output is never longer than either of those encodes:
+ *    lfx_encode_bound and its siblings hold as they are.  With a preset dictionary a stored block holds the record's bytes alone.
+ * Served by lfx_encode_device / _host, lfx_encode_batch_device, the dictionary encode calls (plain and chain dictionaries),
+ * lfx_encoder_* (codes mode: fixed or dynamic only) and lfx_encode_members_* (BGZF: the 64 KiB fallback is evaluated on the
+ * chosen sizes), with the lz77 kinds 0, 2 and 3.  LFX_E_UNSUPPORTED from lfx_encode_index_device and from the N-GPU encode
+ * (lfx_encode_shard_prepare, lfx_sharded_encode_begin): a stored block's size depends on the bit phase there. */
+enum { LFX_HUFFMAN_FIXED = 0, LFX_HUFFMAN_DYNAMIC = 1, LFX_HUFFMAN_AUTO = 2 };
 /* zlib::FlushMode (src/zlib.rs:184-195) */
 enum { LFX_FLUSH_NONE = 0, LFX_FLUSH_SYNC = 2 };
 
@@ -85,7 +105,7 @@ enum { LFX_FLUSH_NONE = 0, LFX_FLUSH_SYNC = 2 };
  * zlib::EncodeOptions.flush_mode (src/zlib.rs:414-518). */
 typedef struct lfx_encode_opts {
     uint64_t block_size;       /* encode.rs:11   default 1 MiB (hint; a block holds whole writes) */
-    int32_t dynamic_huffman;   /* encode.rs:107  default 1; 0 = fixed_huffman_codes() */
+    int32_t dynamic_huffman;   /* encode.rs:107  default 1; 0 = fixed_huffman_codes(); LFX_HUFFMAN_AUTO (2) = the smallest form per block */
     int32_t no_compression;    /* encode.rs:77   stored blocks */
     int32_t lz77_kind;         /* LFX_LZ77_*     with_lz77(...) */
     uint32_t window_size;      /* default.rs:226 default 32768 (clamped) */

@@ -1,10 +1,10 @@
 /* lfx_testhooks.h — host-only test hooks exported by liblfx.so.
  *
- * NOT part of the drop-in boundary (include/lfx.h is).  These four entry points run, on the HOST, the very sources
+ * NOT part of the drop-in boundary (include/lfx.h is).  The lfx_debug_huff_block / _plan / _plan_incremental / _symbols entry points run, on the HOST, the very sources
  * the device kernels compile (lfx_huff.h: code-length builder, canonical codes, block header; lfx_plan.h: the write
  * schedule → chunk/block planner) so that `pytest -m "not gpu"` can check that logic (against the CPU restatement under tests) on a machine
  * without a GPU.  No compression or decompression of data can be reached through them; the product entry points in
- * lfx.h never call them.  tests/test_host_pipeline.py is their only user; tests/test_abi.py checks that the library
+ * lfx.h never call them.  (lfx_debug_block_choices, at the end, reads a result array of the last encode back from the device.)  tests/test_host_pipeline.py is their only user; tests/test_abi.py checks that the library
  * exports exactly lfx.h ∪ lfx_testhooks.h.
  */
 #ifndef LFX_TESTHOOKS_H
@@ -36,6 +36,11 @@ int lfx_debug_plan_incremental(int format, const lfx_encode_opts *o, const lfx_s
 /* Symbol::code / extra bits / distance closed forms (src/deflate/symbol.rs:343-386):
  * out6 = {len symbol, extra width, extra value, dist symbol, extra width, extra value}. */
 void lfx_debug_symbols(uint32_t length, uint32_t distance, uint32_t *out6);
+
+/* LFX_HUFFMAN_AUTO: the type (0 stored, 1 fixed, 2 dynamic) every block of the context's last encode pass left
+ * block_choose_kernel with, in plan order.  *n_blocks = the blocks of that pass — 0 when it was not an LFX_HUFFMAN_AUTO one;
+ * at most max_blocks entries are written.  Reads results back; starts no compression work. */
+int lfx_debug_block_choices(lfx_ctx *c, uint8_t *out, size_t max_blocks, size_t *n_blocks);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ SO_PATH = os.environ.get("LFX_SO") or os.path.join(_HERE, "liblfx.so")     # (LF
 DEFLATE, ZLIB, GZIP = 0, 1, 2
 OK, E_INVALID_DATA, E_UNEXPECTED_EOF, E_IO, E_OOM, E_DEVICE, E_ARG, E_NOSPACE, E_UNSUPPORTED, E_WOULD_BLOCK = range(10)
 LZ77_DEFAULT, LZ77_NOCOMPRESSION, LZ77_CHAIN, LZ77_LAZY = 0, 1, 2, 3     # (LZ77_CHAIN and LZ77_LAZY carry their depth: kind | depth << 8)
+HUFFMAN_FIXED, HUFFMAN_DYNAMIC, HUFFMAN_AUTO = 0, 1, 2     # lfx_encode_opts.dynamic_huffman; AUTO: the smallest form per block
 FLUSH_NONE, FLUSH_SYNC = 0, 2
 SCHED_SINGLE, SCHED_FIXED, SCHED_LIST = 0, 1, 2
 SCHED_FLUSH = (1 << 64) - 1
@@ -321,6 +322,7 @@ def lib():
     L.lfx_debug_plan_incremental.argtypes = [i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), u64, u32, vp, C.c_size_t,
                                              C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lfx_debug_symbols.argtypes = [u32, u32, vp]
+    L.lfx_debug_block_choices.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = L
     return L
 

@@ -625,6 +625,7 @@ extern "C" int lfx_encode_shard_prepare(lfx_ctx *cc, int format, const lfx_encod
     if (d.no_compression) { c->set_error("sharded encode of stored blocks is not supported (their size depends on the bit phase)"); return LFX_E_UNSUPPORTED; }
     if (lz77_kind_of(d) == LFX_LZ77_CHAIN) { c->set_error("lz77_kind: the N-GPU encode does not serve LFX_LZ77_CHAIN"); return LFX_E_UNSUPPORTED; }
     if (lazy_of(d)) { c->set_error("lz77_kind: the N-GPU encode does not serve LFX_LZ77_LAZY"); return LFX_E_UNSUPPORTED; }
+    if (auto_blocks_of(d)) { c->set_error("dynamic_huffman: the N-GPU encode does not serve LFX_HUFFMAN_AUTO (a stored block's size depends on the bit phase)"); return LFX_E_UNSUPPORTED; }
     PlanOpts po = plan_opts(format, d);
     Planner pl(po);
     apply_schedule(pl, s, n);
@@ -859,6 +860,19 @@ extern "C" int lfx_debug_plan_incremental(int format, const lfx_encode_opts *o, 
         block_out[6 * i + 4] = blocks[i].in_off; block_out[6 * i + 5] = blocks[i].in_len;
     }
     return 0;
+} LFX_ABI_CATCH
+// the types block_choose_kernel left the blocks of the context's last encode_prepare with (LFX_HUFFMAN_AUTO)
+extern "C" int lfx_debug_block_choices(lfx_ctx *cc, uint8_t *out, size_t max_blocks, size_t *n_blocks) try {
+    if (!cc || !n_blocks) return LFX_E_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    *n_blocks = c->n_choices;
+    const size_t n = std::min<size_t>(c->n_choices, max_blocks);
+    if (n && !out) return LFX_E_ARG;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n) HIP_TRY(hipMemcpy(out, c->d_choice.p, n, hipMemcpyDeviceToHost));
+    return LFX_OK;
 } LFX_ABI_CATCH
 extern "C" void lfx_debug_symbols(uint32_t length, uint32_t distance, uint32_t *out6) {
     out6[0] = len_symbol(length, out6[1], out6[2]);

@@ -75,6 +75,10 @@ int launch_histogram(hipStream_t st, const ChunkDesc *chunks, uint32_t nchunks, 
                      const uint32_t *codes, const uint32_t *ncodes, uint32_t *hist);
 int launch_huffman(hipStream_t st, const BlockDesc *blocks, uint32_t nblocks, const uint32_t *hist,
                    BlockCodes *bc, uint64_t *dbg = nullptr);
+// LFX_HUFFMAN_AUTO: every BT_DYNAMIC block of the device table becomes the smallest of its dynamic, fixed and —
+// stored_ok — stored form; choice[b] = the type block b leaves with
+int launch_block_choose(hipStream_t st, BlockDesc *blocks, uint32_t nblocks, const uint32_t *hist, BlockCodes *bc, bool stored_ok,
+                        uint8_t *choice);
 int launch_offsets(hipStream_t st, const BlockDesc *blocks, uint32_t nblocks, const BlockCodes *bc,
                    uint64_t start_bit, uint64_t cap_bits, uint64_t *block_start, EncodeResult *res);
 int launch_offsets_batch(hipStream_t st, const BatchStream *streams, uint32_t count, const BlockDesc *blocks, const BlockCodes *bc,

@@ -82,6 +82,9 @@ inline uint32_t chain_depth_of(const lfx_encode_opts &o) {
 }
 // LazyLz77Encoder: the chain stage also demotes a position whose successor matches longer
 inline bool lazy_of(const lfx_encode_opts &o) { return lz77_kind_of(o) == LFX_LZ77_LAZY; }
+// LFX_HUFFMAN_AUTO: the plan of dynamic_huffman = 1, every dynamic block's form chosen on the device.  Stored
+// blocks have no form to choose: no_compression leaves the flag without effect.
+inline bool auto_blocks_of(const lfx_encode_opts &o) { return o.dynamic_huffman == LFX_HUFFMAN_AUTO && !o.no_compression; }
 inline int check_opts(const lfx_encode_opts &o) {
     if (o.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
     if (o.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
@@ -98,6 +101,7 @@ inline PlanOpts plan_opts(int format, const lfx_encode_opts &o) {
     PlanOpts p;
     p.block_size = o.block_size;
     p.dynamic_huffman = o.dynamic_huffman != 0;
+    p.auto_blocks = auto_blocks_of(o);
     p.no_compression = o.no_compression != 0;
     p.lz77_kind = lz77_kind_of(o);     // (without the depth)
     p.window_size = o.window_size;

@@ -65,6 +65,7 @@ struct EncCall {
     bool match_v1;                // the first-generation match kernel: it once saw a lane-order violation (or LFX_MATCH_V1 is set)
     uint32_t chain_depth;         // ChainLz77Encoder's or LazyLz77Encoder's depth; 0: any other kind — no chain stage, no second candidate buffer
     bool lazy;                    // LazyLz77Encoder: the chain stage keeps the lengths and demotes behind them (§20)
+    bool auto_blocks;             // LFX_HUFFMAN_AUTO (§22): block_choose_kernel behind the Huffman kernel; any other call: no launch, no buffer
     EncodeGeom g;
     uint64_t nspans = 0;          // partial results of the checksum kernels
     bool forked = false;          // the first half of the checksum's sweep is on the side stream already
@@ -180,6 +181,7 @@ int reserve_scratch(Ctx *c, EncCall &k) {
     if ((rc = c->d_hist.reserve(4ull * 320 * std::max<size_t>(nblocks, 1)))) return rc;
     if ((rc = c->d_bc.reserve(sizeof(BlockCodes) * std::max<size_t>(nblocks, 1)))) return rc;
     if ((rc = c->d_block_start.reserve(8 * std::max<size_t>(nblocks, 1)))) return rc;
+    if (k.auto_blocks && (rc = c->d_choice.reserve(std::max<size_t>(nblocks, 1)))) return rc;   // LFX_HUFFMAN_AUTO: the chosen type per block
     if ((rc = c->d_tile_bits.reserve(4 * std::max<uint64_t>(plan.n_tiles, 1)))) return rc;
     if ((rc = c->d_tile_start.reserve(8 * std::max<uint64_t>(plan.n_tiles, 1)))) return rc;
     k.nspans = ck_nspans(n);
@@ -421,6 +423,17 @@ int stage_huffman(Ctx *c, const EncCall &k) {
     LAUNCH_TRY(launch_huffman(st, v.blocks, c->cur_nblocks, v.hist, (BlockCodes *)c->d_bc.p, v.mdbg ? v.mdbg + 512 : nullptr));
     c->phase("huffman");
     if (v.mdbg) dbg_huffman(k);
+    if (k.auto_blocks) {
+        // LFX_HUFFMAN_AUTO: in front of everything that reads a block's size or type — tile_bits, the offset
+        // folds, the members' sizes.  Stored is a candidate only where the blocks have input bytes behind them (not for a
+        // caller's own code words).  The device's block table no longer equals its shadow: the next prepare uploads it, whatever
+        // its plan (as behind a BGZF fallback, encode_members).
+        LAUNCH_TRY(launch_block_choose(st, (BlockDesc *)c->d_blocks.p, c->cur_nblocks, v.hist, (BlockCodes *)c->d_bc.p, k.hc == nullptr,
+                                       (uint8_t *)c->d_choice.p));
+        c->up_dev[1] = 0;
+        c->n_choices = c->cur_nblocks;
+        c->phase("block_choose");
+    }
     return LFX_OK;
 }
 
@@ -433,6 +446,7 @@ int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *
     c->phase("start");
     EncCall k{plan, po, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
               (po.lz77_kind == LFX_LZ77_CHAIN || po.lz77_kind == LFX_LZ77_LAZY) && !hc ? chain_depth : 0u, po.lz77_kind == LFX_LZ77_LAZY,
+              po.auto_blocks && !po.no_compression,
               encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
     if (k.chain_depth && k.dict && !k.dict->chain) { c->set_error("LFX_LZ77_CHAIN / LFX_LZ77_LAZY with a preset dictionary is not supported: the dictionary has no chain (lfx_dict_new_chain)"); return LFX_E_UNSUPPORTED; }
@@ -443,6 +457,7 @@ int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *
     c->cur_ntiles = plan.n_tiles;
     c->cur_n = n;
     c->cur_in = d_in;
+    c->n_choices = 0;
     int rc;
     if ((rc = reserve_scratch(c, k))) return rc;
     if ((rc = upload_tables(c, k))) return rc;

@@ -459,6 +459,60 @@ __global__ __launch_bounds__(HUFF_THREADS) void huffman_kernel(const BlockDesc *
 }
 
 // ------------------------------------------------------------------------------------------------
+// LFX_HUFFMAN_AUTO: behind huffman_kernel, one wavefront per block picks the smallest of the block's dynamic
+// form (D = bc[b].body_bits), its fixed form (F = 3 + Σ count · (fixed width + extra bits) over the block's own counts) and —
+// stored_ok: the block has input bytes behind it — its stored form at the worst alignment (S = 8 · in_len + 42).  Stored wins
+// when 1 <= in_len <= 65535 and S < min(D, F); otherwise fixed when F <= D; otherwise dynamic.  Everything behind it reads the
+// block's type from the device table and its size and codes from bc[]: a block turned fixed gets FixedHuffmanCodec's tables
+// (the BT_FIXED branch of huff_block_build), body_bits = F and no header; a block turned stored only its type.  choice[b] = the
+// type the block leaves with.  No LDS, no scratch, no atomics: the 320 counters are five coalesced loads per lane, F a shuffle
+// reduction.
+__device__ __forceinline__ uint32_t fixed_lit_width(uint32_t s) { return s < 144 ? 8u : s < 256 ? 9u : s < 280 ? 7u : 8u; }
+__global__ __launch_bounds__(64) void block_choose_kernel(BlockDesc *__restrict__ blocks, uint32_t nblocks,
+                                                          const uint32_t *__restrict__ hist, BlockCodes *__restrict__ bc,
+                                                          uint32_t stored_ok, uint8_t *__restrict__ choice) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (b >= nblocks) return;
+    const BlockDesc bd = blocks[b];                      // (uniform: every lane reads the same 40 bytes)
+    if (bd.type != BT_DYNAMIC) {
+        if (lane == 0) choice[b] = (uint8_t)bd.type;
+        return;
+    }
+    const uint32_t *h = hist + (uint64_t)b * HIST_STRIDE;
+    uint32_t cnt[HIST_STRIDE / 64];
+#pragma unroll
+    for (uint32_t q = 0; q < HIST_STRIDE / 64; ++q) cnt[q] = h[q * 64 + lane];
+    uint64_t part = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < HIST_STRIDE / 64; ++q) {
+        const uint32_t s = q * 64 + lane;
+        uint32_t w = 0;                                  // (slots 286, 287, 318, 319 hold no symbol)
+        if (s < 286) w = fixed_lit_width(s) + (s > 256 ? len_extra_bits_of_symbol(s) : 0u);
+        else if (s >= 288 && s < 318) w = 5u + dist_extra_bits_of_symbol(s - 288);
+        part += (uint64_t)cnt[q] * w;
+    }
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+    const uint64_t F = 3 + part, D = bc[b].body_bits, S = 8 * bd.in_len + 42;
+    const uint64_t best = F <= D ? F : D;
+    uint32_t pick = F <= D ? BT_FIXED : BT_DYNAMIC;
+    if (stored_ok && bd.in_len >= 1 && bd.in_len <= 65535 && S < best) pick = BT_RAW;
+    if (pick == BT_FIXED) {
+        BlockCodes *out = &bc[b];
+        for (uint32_t s = lane; s < 288; s += 64) {
+            const uint32_t w = fixed_lit_width(s);
+            const uint32_t c = s < 144 ? 0x30 + s : s < 256 ? 0x190 + (s - 144) : s < 280 ? s - 256 : 0xC0 + (s - 280);
+            out->lit[s] = bitrev(c, w) | (w << 16);
+        }
+        if (lane < 32) out->dist[lane] = lane < 30 ? (bitrev(lane, 5) | (5u << 16)) : 0u;
+        if (lane == 0) { out->body_bits = F; out->hdr_bits = 0; }
+    }
+    if (lane == 0) {
+        if (pick != BT_DYNAMIC) blocks[b].type = pick;
+        choice[b] = (uint8_t)pick;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // block start bits: a serial fold (stored blocks byte-align, the final block byte-aligns)
 __global__ __launch_bounds__(256) void offsets_kernel(const BlockDesc *__restrict__ blocks, uint32_t nblocks,
                                                       const BlockCodes *__restrict__ bc, uint64_t start_bit,
@@ -1252,6 +1306,13 @@ int launch_huffman(hipStream_t st, const BlockDesc *blocks, uint32_t nblocks, co
                    BlockCodes *bc, uint64_t *dbg) {
     if (nblocks == 0) return 0;
     hipLaunchKernelGGL(huffman_kernel, dim3(nblocks), dim3(HUFF_THREADS), 0, st, blocks, hist, bc, dbg);
+    LFX_LAUNCH_CHECK();
+    return 0;
+}
+int launch_block_choose(hipStream_t st, BlockDesc *blocks, uint32_t nblocks, const uint32_t *hist, BlockCodes *bc, bool stored_ok,
+                        uint8_t *choice) {
+    if (nblocks == 0) return 0;
+    hipLaunchKernelGGL(block_choose_kernel, dim3(nblocks), dim3(64), 0, st, blocks, nblocks, hist, bc, stored_ok ? 1u : 0u, choice);
     LFX_LAUNCH_CHECK();
     return 0;
 }

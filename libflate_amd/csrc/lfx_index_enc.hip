@@ -21,6 +21,7 @@
 #include "lfx_abi_guard.h"
 #include "lfx_common.h"
 #include "lfx_ctx.h"
+#include "lfx_enc_frame.h"
 #include "lfx_huff.h"
 #include "lfx_index.h"
 #include "lfx_plan.h"
@@ -345,6 +346,10 @@ extern "C" int lfx_encode_index_device(lfx_ctx *cc, int format, const lfx_encode
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     if (!idx) { c->set_error("lfx_encode_index_device: idx is NULL"); return LFX_E_ARG; }
     if (spacing < 4096) { c->set_error("lfx_encode_index_device: spacing " + std::to_string(spacing) + " is below 4096"); return LFX_E_ARG; }
+    if (o && auto_blocks_of(norm_opts(o))) {
+        c->set_error("dynamic_huffman: lfx_encode_index_device does not serve LFX_HUFFMAN_AUTO (the candidates are laid out from the host plan's block types)");
+        return LFX_E_UNSUPPORTED;
+    }
     IdxCollect col;
     col.spacing = spacing;
     uint64_t ol = 0;

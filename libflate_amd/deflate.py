@@ -45,6 +45,12 @@ class EncodeOptions:
         self._kw["dynamic_huffman"] = 0
         return self
 
+    def auto_huffman_codes(self):
+        """not a reference option (LFX_HUFFMAN_AUTO): per block the smallest of the dynamic, the fixed and the
+        stored form; the blocks and the LZ77 code words stay those of the default options"""
+        self._kw["dynamic_huffman"] = _ffi.HUFFMAN_AUTO
+        return self
+
     def _to_c(self):
         return _ffi.make_opts(**self._kw)
 

@@ -16,6 +16,7 @@ where
 {
     pub(crate) block_size: usize,
     pub(crate) dynamic_huffman: bool,
+    pub(crate) auto_huffman: bool,     // LFX_HUFFMAN_AUTO (not a reference option): wins over dynamic_huffman
     pub(crate) lz77: Option<E>,        // None = stored blocks (encode.rs:77-80)
 }
 impl Default for EncodeOptions<DefaultLz77Encoder> {
@@ -24,7 +25,7 @@ impl Default for EncodeOptions<DefaultLz77Encoder> {
 impl EncodeOptions<DefaultLz77Encoder> {
     /// encode.rs:45-51
     pub fn new() -> Self {
-        EncodeOptions { block_size: DEFAULT_BLOCK_SIZE, dynamic_huffman: true, lz77: Some(DefaultLz77Encoder::new()) }
+        EncodeOptions { block_size: DEFAULT_BLOCK_SIZE, dynamic_huffman: true, auto_huffman: false, lz77: Some(DefaultLz77Encoder::new()) }
     }
 }
 impl<E> EncodeOptions<E>
@@ -32,20 +33,23 @@ where
     E: GpuLz77,
 {
     /// encode.rs:59-65
-    pub fn with_lz77(lz77: E) -> Self { EncodeOptions { block_size: DEFAULT_BLOCK_SIZE, dynamic_huffman: true, lz77: Some(lz77) } }
+    pub fn with_lz77(lz77: E) -> Self { EncodeOptions { block_size: DEFAULT_BLOCK_SIZE, dynamic_huffman: true, auto_huffman: false, lz77: Some(lz77) } }
     /// encode.rs:77-80
     pub fn no_compression(mut self) -> Self { self.lz77 = None; self }
     /// encode.rs:92-95
     pub fn block_size(mut self, size: usize) -> Self { self.block_size = size; self }
     /// encode.rs:107-110
-    pub fn fixed_huffman_codes(mut self) -> Self { self.dynamic_huffman = false; self }
+    pub fn fixed_huffman_codes(mut self) -> Self { self.dynamic_huffman = false; self.auto_huffman = false; self }
+    /// Not a reference option (`LFX_HUFFMAN_AUTO`, include/lfx.h): every block in the smallest of its dynamic,
+    /// fixed and stored form; the blocks and the LZ77 code words stay those of the default options.
+    pub fn auto_huffman_codes(mut self) -> Self { self.dynamic_huffman = true; self.auto_huffman = true; self }
 
     /// → the C options and whether the whole path runs on the device for this `E` (else `E` runs on the caller's side)
     pub(crate) fn to_ffi(&self) -> (ffi::lfx_encode_opts, bool) {
         let mut o: ffi::lfx_encode_opts = unsafe { std::mem::zeroed() };
         unsafe { ffi::lfx_encode_opts_default(&mut o) };
         o.block_size = self.block_size as u64;
-        o.dynamic_huffman = self.dynamic_huffman as i32;
+        o.dynamic_huffman = if self.auto_huffman { ffi::LFX_HUFFMAN_AUTO } else { self.dynamic_huffman as i32 };
         let on_device = match self.lz77 {
             Some(ref e) => e.configure(&mut o),
             None => { o.no_compression = 1; true }      // RawBuf never calls the Lz77Encode (encode.rs:348-383)

@@ -138,6 +138,8 @@ impl<E: GpuLz77> EncodeOptions<E> {
     pub fn header(mut self, header: Header) -> Self { self.header = header; self }
     pub fn block_size(mut self, size: usize) -> Self { self.inner = self.inner.block_size(size); self }
     pub fn fixed_huffman_codes(mut self) -> Self { self.inner = self.inner.fixed_huffman_codes(); self }
+    /// `LFX_HUFFMAN_AUTO`: see `deflate::EncodeOptions::auto_huffman_codes`
+    pub fn auto_huffman_codes(mut self) -> Self { self.inner = self.inner.auto_huffman_codes(); self }
 }
 
 /// `gzip::Encoder<W, E>` (gzip.rs:754-908)

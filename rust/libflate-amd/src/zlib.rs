@@ -44,6 +44,8 @@ impl<E: GpuLz77> EncodeOptions<E> {
     pub fn no_compression(mut self) -> Self { self.inner = self.inner.no_compression(); self }
     pub fn block_size(mut self, size: usize) -> Self { self.inner = self.inner.block_size(size); self }
     pub fn fixed_huffman_codes(mut self) -> Self { self.inner = self.inner.fixed_huffman_codes(); self }
+    /// `LFX_HUFFMAN_AUTO`: see `deflate::EncodeOptions::auto_huffman_codes`
+    pub fn auto_huffman_codes(mut self) -> Self { self.inner = self.inner.auto_huffman_codes(); self }
     pub fn flush_mode(mut self, mode: FlushMode) -> Self { self.flush_mode = mode; self }
     fn to_ffi(&self) -> (ffi::lfx_encode_opts, bool) {
         let (mut o, on_device) = self.inner.to_ffi();
