@@ -412,7 +412,8 @@ void lfx_index_free(lfx_index *idx);
 /* ---- sharded encode: independent block ranges per rank, one gzip/zlib/deflate member
  * (SURVEY §8e).  prepare() runs match finding → Huffman build and the checksums and reports the
  * shard's bit length; after the ranks exchanged lfx_shard_info (RCCL all-gather), emit() packs the
- * shard at its global bit offset.  The byte at each shard boundary is shared (OR the halves). */
+ * shard at its global bit offset.  The byte at each shard boundary is shared (OR the halves).
+ * no_compression: LFX_E_UNSUPPORTED (a stored block's size depends on the bit phase). */
 typedef struct lfx_shard_info {
     uint64_t total_bits; /* DEFLATE bits of this shard (incl. final byte alignment on the last) */
     uint64_t n_bytes;    /* uncompressed bytes */

@@ -35,8 +35,9 @@ extern "C" uint32_t lfx_version(void) { return LFX_VERSION; }
 
 extern "C" uint64_t lfx_container_header_len(int format, const lfx_encode_opts *o) {
     std::vector<uint8_t> b;
-    lfx_encode_opts d = norm_opts(o);
-    container_header(format, d, b);
+    EncodeSpec sp;
+    (void)encode_spec(format, o, &sp);      // (the header of the normalised options, whatever their domain)
+    container_header(format, sp.o, b);
     return b.size();
 }
 
@@ -62,9 +63,10 @@ static void apply_schedule(Planner &pl, const lfx_schedule *s, uint64_t n) {
 }
 
 extern "C" uint64_t lfx_encode_bound(uint64_t n, const lfx_encode_opts *o, const lfx_schedule *s) {
-    lfx_encode_opts d = norm_opts(o);
-    if (check_opts(d)) return 0;
-    Planner pl(plan_opts(LFX_ZLIB, d));
+    EncodeSpec sp;
+    if (encode_spec(LFX_ZLIB, o, &sp)) return 0;
+    const lfx_encode_opts &d = sp.o;
+    Planner pl(sp.plan);
     apply_schedule(pl, s, n);
     Plan &p = pl.finish();
     // a dynamic block never costs more than ~9 bits per literal + its header; stored: 5 bytes per block
@@ -239,14 +241,6 @@ static void dict_header(int format, const lfx_dict *dict, std::vector<uint8_t> &
     hdr[1] = flg;
     for (int sh = 24; sh >= 0; sh -= 8) hdr.push_back((uint8_t)(dict->id >> sh));
 }
-// ChainLz77Encoder and LazyLz77Encoder have no chain behind a plain dictionary's candidate (Limits); a chain
-// dictionary (lfx_dict_new_chain, §21) brings its own
-static int chain_dict_refused(Ctx *c, const lfx_dict *dict, const lfx_encode_opts &d) {
-    if (!dict || dict->chain || !lz77_chained(lz77_kind_of(d))) return LFX_OK;
-    c->set_error(lazy_of(d) ? "lz77_kind: LFX_LZ77_LAZY with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"
-                            : "lz77_kind: LFX_LZ77_CHAIN with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)");
-    return LFX_E_UNSUPPORTED;
-}
 // the stream's first LZ77 flush unit is the one the dictionary primes — where the options match at all and the dictionary
 // has bytes to offer
 static void dict_prime(const lfx_dict *dict, Plan &p) {
@@ -258,14 +252,13 @@ static int encode_device_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o,
     if (!cc) return LFX_E_DEVICE;
     Ctx *c = reinterpret_cast<Ctx *>(cc);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    lfx_encode_opts d = norm_opts(o);
-    int rc = check_opts(d);
+    EncodeSpec sp;
+    int rc = encode_spec(format, o, &sp);
     if (rc) { c->set_error("option outside the reference's domain"); return rc; }
-    if ((rc = chain_dict_refused(c, dict, d))) return rc;
+    if ((rc = served(c, dict ? ENC_DICT_DEVICE : ENC_DEVICE, sp, dict))) return rc;
     std::vector<uint8_t> hdr;
-    if ((rc = container_header(format, d, hdr))) { c->set_error("bad container options"); return rc; }
-    PlanOpts po = plan_opts(format, d);
-    Planner pl(po);
+    if ((rc = container_header(format, sp.o, hdr))) { c->set_error("bad container options"); return rc; }
+    Planner pl(sp.plan);
     apply_schedule(pl, s, n);
     Plan &plan = pl.finish();
     if (dict) { dict_header(format, dict, hdr); dict_prime(dict, plan); }
@@ -274,7 +267,7 @@ static int encode_device_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o,
     if (fill_ok) (void)hipSetDevice(c->device);
     c->prezero.start(d_out, fill_ok ? cap / 4 * 4 : 0);
     rc = with_match_fallback(c, res, [&]() -> int {
-        if (int rc2 = encode_prepare(c, plan, po, (const uint8_t *)d_in, n, ck_mode_of(format), nullptr, dict, chain_depth_of(d))) return rc2;
+        if (int rc2 = encode_prepare(c, plan, sp, (const uint8_t *)d_in, n, ck_mode_of(format), nullptr, dict)) return rc2;
         return encode_emit(c, format, true, 0, true, n, hdr.data(), (uint32_t)hdr.size(), 8 * (uint64_t)hdr.size(),
                            (uint8_t *)d_out, cap, &res);
     });
@@ -314,22 +307,21 @@ static int encode_batch_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o, 
     Ctx *c = reinterpret_cast<Ctx *>(cc);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     if (format < 0 || format > 2 || (count && (!in_off || !in_len || !out_off || !out_cap))) return LFX_E_ARG;
-    lfx_encode_opts d = norm_opts(o);
-    int rc = check_opts(d);
+    EncodeSpec sp;
+    int rc = encode_spec(format, o, &sp);
     if (rc) { c->set_error("option outside the reference's domain"); return rc; }
-    if ((rc = chain_dict_refused(c, dict, d))) return rc;
+    if ((rc = served(c, dict ? ENC_DICT_BATCH : ENC_BATCH, sp, dict))) return rc;
     std::vector<uint8_t> hdr;
-    if ((rc = container_header(format, d, hdr))) { c->set_error("bad container options"); return rc; }
+    if ((rc = container_header(format, sp.o, hdr))) { c->set_error("bad container options"); return rc; }
     if (dict) dict_header(format, dict, hdr);
     if (!count) return LFX_OK;
-    const PlanOpts po = plan_opts(format, d);
     // ---- the merged plan: every stream planned alone, its descriptors shifted into the shared index spaces
     Plan plan;
     std::vector<BatchStream> streams(count);
     uint64_t in_extent = 0, out_lo = ~0ull, out_hi = 0;
     for (uint32_t i = 0; i < count; i++) {
         if (out_off[i] & 3) { c->set_error("output offsets must be 4-byte aligned"); return LFX_E_ARG; }
-        Planner pl(po);
+        Planner pl(sp.plan);
         apply_schedule(pl, s, in_len[i]);
         Plan &p = pl.finish();
         if (dict) dict_prime(dict, p);
@@ -353,8 +345,8 @@ static int encode_batch_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o, 
     std::vector<uint64_t> h_len;
     std::vector<int32_t> h_status;
     EncodeResult res{};
-    const BatchCall call{format, streams, hdr, (const uint8_t *)d_in, in_extent, (uint8_t *)d_out, out_lo, out_hi, dict, chain_depth_of(d)};
-    if ((rc = encode_batch(c, plan, po, call, h_len, h_status, res))) return rc;
+    const BatchCall call{format, streams, hdr, (const uint8_t *)d_in, in_extent, (uint8_t *)d_out, out_lo, out_hi, dict};
+    if ((rc = encode_batch(c, plan, sp, call, h_len, h_status, res))) return rc;
     for (uint32_t i = 0; i < count; i++) {
         if (status) status[i] = res.status ? h_status[i] : LFX_OK;     // (a voided call: non-zero for exactly the streams that were too small)
         if (out_len) out_len[i] = res.status ? 0 : h_len[i];
@@ -432,12 +424,14 @@ static const uint8_t BGZF_EXTRA[6] = {0x42, 0x43, 0x02, 0x00, 0x00, 0x00};   // 
 static const uint32_t BGZF_MAX_MEMBER = 65536, BGZF_EOF_LEN = 28;
 static const uint64_t BGZF_MAX_SLICE = 65505;                               // 18 + 5 + 65505 + 8 = 65536: one stored block still fits
 // the options and the schedule of a members call: *why names the field that is out of its domain
-static int members_check(uint64_t member_size, uint32_t flags, const lfx_encode_opts *o, const lfx_schedule *s, lfx_encode_opts *d,
+static int members_check(uint64_t member_size, uint32_t flags, const lfx_encode_opts *o, const lfx_schedule *s, EncodeSpec *sp,
                          const char **why) {
-    *d = norm_opts(o);
+    const int domain = encode_spec(LFX_GZIP, o, sp);
+    lfx_encode_opts *d = &sp->o;
     if (flags & ~(uint32_t)LFX_MEMBERS_BGZF) { *why = "flags: unknown bit"; return LFX_E_ARG; }
     if (member_size == 0) { *why = "member_size: must not be 0"; return LFX_E_ARG; }
-    if (check_opts(*d)) { *why = "block_size / max_length: outside the reference's domain"; return LFX_E_ARG; }
+    if (domain) { *why = "block_size / max_length: outside the reference's domain"; return LFX_E_ARG; }
+    if (int rc = encode_served(ENC_MEMBERS, *sp, DICT_NONE, why)) return rc;
     if (!(flags & LFX_MEMBERS_BGZF)) return LFX_OK;
     if (member_size > BGZF_MAX_SLICE) { *why = "member_size: a BGZF member holds at most 65505 bytes"; return LFX_E_ARG; }
     if (d->extra) { *why = "extra: BGZF carries its own BC subfield"; return LFX_E_ARG; }
@@ -464,9 +458,9 @@ static MemberSlices member_slices(uint64_t n, uint64_t member_size, uint32_t fla
 
 extern "C" uint64_t lfx_encode_members_bound(uint64_t n, uint64_t member_size, uint32_t flags, const lfx_encode_opts *o,
                                              const lfx_schedule *s) try {
-    lfx_encode_opts d;
+    EncodeSpec sp;
     const char *why = nullptr;
-    if (members_check(member_size, flags, o, s, &d, &why)) return 0;
+    if (members_check(member_size, flags, o, s, &sp, &why)) return 0;
     const bool bgzf = (flags & LFX_MEMBERS_BGZF) != 0;
     const MemberSlices ms = member_slices(n, member_size, flags);
     // (BGZF: the caller's options, without the BC subfield — lfx_encode_bound leaves 64 bytes for the 10 fixed ones of a header)
@@ -524,14 +518,14 @@ extern "C" int lfx_encode_members_device(lfx_ctx *cc, const lfx_encode_opts *o, 
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     if (out_len) *out_len = 0;
     if (n_members) *n_members = 0;
-    lfx_encode_opts d;
+    EncodeSpec sp;
     const char *why = nullptr;
-    int rc = members_check(member_size, flags, o, s, &d, &why);
+    int rc = members_check(member_size, flags, o, s, &sp, &why);
     if (rc) { c->set_error(why); return rc; }
     if (((uintptr_t)d_out & 3) != 0) { c->set_error("output buffer must be 4-byte aligned"); return LFX_E_ARG; }
     const bool bgzf = (flags & LFX_MEMBERS_BGZF) != 0;
     std::vector<uint8_t> hdr;
-    if ((rc = container_header(LFX_GZIP, d, hdr))) { c->set_error("extra: longer than 65535 bytes"); return rc; }
+    if ((rc = container_header(LFX_GZIP, sp.o, hdr))) { c->set_error("extra: longer than 65535 bytes"); return rc; }
     const MemberSlices ms = member_slices(n, member_size, flags);
     if (ms.count() >= 0xFFFFFFFFull) { c->set_error("member_size: more than 2^32 - 2 members"); return LFX_E_ARG; }
     const uint32_t count = (uint32_t)ms.count();
@@ -547,10 +541,9 @@ extern "C" int lfx_encode_members_device(lfx_ctx *cc, const lfx_encode_opts *o, 
         if (out_len) *out_len = BGZF_EOF_LEN;
         return LFX_OK;
     }
-    const PlanOpts po = plan_opts(LFX_GZIP, d);
     Plan plan;
     uint32_t bpm[2];
-    if ((rc = members_plan(po, s, ms, member_size, bgzf, plan, bpm, &why))) { c->set_error(why); return rc; }
+    if ((rc = members_plan(sp.plan, s, ms, member_size, bgzf, plan, bpm, &why))) { c->set_error(why); return rc; }
     MembersGeom g{};
     g.n = n; g.member_size = member_size; g.count = count;
     g.bpm = bpm[0]; g.bpm_last = bpm[1];
@@ -558,8 +551,8 @@ extern "C" int lfx_encode_members_device(lfx_ctx *cc, const lfx_encode_opts *o, 
     const uint64_t bound = lfx_encode_members_bound(n, member_size, flags, o, s);
     EncodeResult res{};
     const MembersCall call{g, hdr, (const uint8_t *)d_in, (uint8_t *)d_out, cap, std::min(cap, bound), members,
-                           members ? std::min(count, max_members) : 0, chain_depth_of(d)};
-    if ((rc = encode_members(c, plan, po, call, res))) return rc;
+                           members ? std::min(count, max_members) : 0};
+    if ((rc = encode_members(c, plan, sp, call, res))) return rc;
     if (n_members) *n_members = count;
     if (res.status) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
     if (out_len) *out_len = res.out_bytes;
@@ -575,9 +568,9 @@ extern "C" int lfx_encode_members_host(lfx_ctx *cc, const lfx_encode_opts *o, co
     (void)hipSetDevice(c->device);
     if (out_len) *out_len = 0;
     if (n_members) *n_members = 0;
-    lfx_encode_opts d;
+    EncodeSpec sp;
     const char *why = nullptr;
-    int rc = members_check(member_size, flags, o, s, &d, &why);
+    int rc = members_check(member_size, flags, o, s, &sp, &why);
     if (rc) { c->set_error(why); return rc; }
     const uint64_t bound = lfx_encode_members_bound(n, member_size, flags, o, s);
     return encode_staged(c, in, n, std::max<uint64_t>(bound, 4), out, cap, out_len, [&](uint64_t &len) {
@@ -619,15 +612,11 @@ extern "C" int lfx_encode_shard_prepare(lfx_ctx *cc, int format, const lfx_encod
     if (!cc) return LFX_E_DEVICE;
     Ctx *c = reinterpret_cast<Ctx *>(cc);
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    lfx_encode_opts d = norm_opts(o);
-    int rc = check_opts(d);
+    EncodeSpec sp;
+    int rc = encode_spec(format, o, &sp);
     if (rc) return rc;
-    if (d.no_compression) { c->set_error("sharded encode of stored blocks is not supported (their size depends on the bit phase)"); return LFX_E_UNSUPPORTED; }
-    if (lz77_kind_of(d) == LFX_LZ77_CHAIN) { c->set_error("lz77_kind: the N-GPU encode does not serve LFX_LZ77_CHAIN"); return LFX_E_UNSUPPORTED; }
-    if (lazy_of(d)) { c->set_error("lz77_kind: the N-GPU encode does not serve LFX_LZ77_LAZY"); return LFX_E_UNSUPPORTED; }
-    if (auto_blocks_of(d)) { c->set_error("dynamic_huffman: the N-GPU encode does not serve LFX_HUFFMAN_AUTO (a stored block's size depends on the bit phase)"); return LFX_E_UNSUPPORTED; }
-    PlanOpts po = plan_opts(format, d);
-    Planner pl(po);
+    if ((rc = served(c, ENC_SHARD, sp))) return rc;
+    Planner pl(sp.plan);
     apply_schedule(pl, s, n);
     Plan *plan;
     if (is_last) {
@@ -647,13 +636,13 @@ extern "C" int lfx_encode_shard_prepare(lfx_ctx *cc, int format, const lfx_encod
         plan->n_tiles = plan->chunks.empty() ? 0 : plan->chunks.back().tile_base + div_up(plan->chunks.back().len + 1, PACK_TILE);
     }
     c->shard_hdr.clear();
-    if (is_first && (rc = container_header(format, d, c->shard_hdr))) return rc;
+    if (is_first && (rc = container_header(format, sp.o, c->shard_hdr))) return rc;
     c->shard_format = format;
     c->shard_last = is_last != 0;
     hipStream_t st = c->stream;
     EncodeResult r{};
     rc = with_match_fallback(c, r, [&]() -> int {
-        if (int rc2 = encode_prepare(c, *plan, po, (const uint8_t *)d_in, n, 3)) return rc2;
+        if (int rc2 = encode_prepare(c, *plan, sp, (const uint8_t *)d_in, n, 3)) return rc2;
         // total bits at bit phase 0 (compressed blocks only → independent of the phase)
         LAUNCH_TRY(launch_offsets(st, (const BlockDesc *)c->d_blocks.p, c->cur_nblocks, (const BlockCodes *)c->d_bc.p,
                                   0, ~0ull, (uint64_t *)c->d_block_start.p, (EncodeResult *)c->d_res.p));
@@ -736,9 +725,10 @@ extern "C" int lfx_lz77_flush(lfx_lz77 *z, lfx_sink_cb sink, void *user) try {
     (void)hipSetDevice(c->device);
     const uint64_t n = z->buf.size();
     if (n == 0) return LFX_OK;
-    PlanOpts po;
-    po.window_size = z->window;
-    po.max_length = z->max_len;
+    EncodeSpec sp;                 // DefaultLz77Encoder: the default options with the handle's window and length
+    (void)encode_spec(LFX_DEFLATE, nullptr, &sp);
+    sp.plan.window_size = z->window;
+    sp.plan.max_length = z->max_len;
     Plan plan;
     ChunkDesc ch{};
     ch.len = n;
@@ -757,7 +747,7 @@ extern "C" int lfx_lz77_flush(lfx_lz77 *z, lfx_sink_cb sink, void *user) try {
     HIP_TRY(hipMemcpyAsync(z->d_in.p, z->buf.data(), n, hipMemcpyHostToDevice, c->stream));
     EncodeResult r{};
     rc = with_match_fallback(c, r, [&]() -> int {
-        if (int rc2 = encode_prepare(c, plan, po, (const uint8_t *)z->d_in.p, n, 0)) return rc2;
+        if (int rc2 = encode_prepare(c, plan, sp, (const uint8_t *)z->d_in.p, n, 0)) return rc2;
         HIP_TRY(hipMemcpy(&r, c->d_res.p, sizeof r, hipMemcpyDeviceToHost));
         return LFX_OK;
     });
@@ -804,9 +794,9 @@ extern "C" int lfx_debug_plan(int format, const lfx_encode_opts *o, const lfx_sc
                               uint64_t *chunk_out /* in_off,len,block,flags per chunk */, size_t max_chunks,
                               size_t *n_chunks, uint64_t *block_out /* type,final,first,n,in_off,in_len */,
                               size_t max_blocks, size_t *n_blocks) try {
-    lfx_encode_opts d = norm_opts(o);
-    if (check_opts(d)) return LFX_E_ARG;
-    Planner pl(plan_opts(format, d));
+    EncodeSpec sp;
+    if (encode_spec(format, o, &sp)) return LFX_E_ARG;
+    Planner pl(sp.plan);
     apply_schedule(pl, s, n);
     Plan &p = pl.finish();
     *n_chunks = p.chunks.size();
@@ -827,9 +817,9 @@ extern "C" int lfx_debug_plan(int format, const lfx_encode_opts *o, const lfx_sc
 extern "C" int lfx_debug_plan_incremental(int format, const lfx_encode_opts *o, const lfx_schedule *s, uint64_t n,
                                           uint32_t take_every, uint64_t *chunk_out, size_t max_chunks, size_t *n_chunks,
                                           uint64_t *block_out, size_t max_blocks, size_t *n_blocks) try {
-    lfx_encode_opts d = norm_opts(o);
-    if (check_opts(d) || !s || s->kind != LFX_SCHED_LIST) return LFX_E_ARG;
-    Planner pl(plan_opts(format, d));
+    EncodeSpec sp;
+    if (encode_spec(format, o, &sp) || !s || s->kind != LFX_SCHED_LIST) return LFX_E_ARG;
+    Planner pl(sp.plan);
     Plan all;
     uint64_t byte0 = 0;
     auto stitch = [&](Plan &p, uint64_t bytes) { all.append(p, byte0); byte0 += bytes; };

@@ -1,6 +1,7 @@
 // lfx_enc_frame.h — host only, no HIP: what the encode entry points and the stream encoder's state machine (lfx_stream_enc.h,
-// built by a plain host compiler) share of the framing — the options' normal form and domain, the planner's options, the
-// container header, and the arithmetic that folds two checksums into one.  The C ABI's wrappers around it stay in lfx_api.cpp.
+// built by a plain host compiler) share of the framing — the options resolved once into an EncodeSpec, the table of which entry
+// point serves which spec, the container header, and the arithmetic that folds two checksums into one.  The C ABI's wrappers
+// around it stay in lfx_api.cpp.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -65,49 +66,69 @@ inline void encode_opts_default(lfx_encode_opts *o) {
     o->max_length = MAX_LENGTH;
     o->os = 3;
 }
-inline lfx_encode_opts norm_opts(const lfx_encode_opts *o) {
-    lfx_encode_opts d;
-    if (o) d = *o; else encode_opts_default(&d);
-    if (d.window_size > MAX_WINDOW) d.window_size = MAX_WINDOW;  // default.rs:228
-    if (d.max_length > MAX_LENGTH) d.max_length = MAX_LENGTH;    // default.rs:240
-    return d;
-}
 // lz77_kind: the kind in bits 0..7; LFX_LZ77_CHAIN and LFX_LZ77_LAZY carry their depth in bits 8..15 (include/lfx.h).  The bits
 // above bit 7 are not read for the other kinds.
 inline int lz77_kind_of(const lfx_encode_opts &o) { return (int)((uint32_t)o.lz77_kind & 0xFFu); }
 // the kinds that run the chain stage
 inline bool lz77_chained(int kind) { return kind == LFX_LZ77_CHAIN || kind == LFX_LZ77_LAZY; }
-inline uint32_t chain_depth_of(const lfx_encode_opts &o) {
-    return lz77_chained(lz77_kind_of(o)) ? ((uint32_t)o.lz77_kind >> 8) & 0xFFu : 0u;
-}
-// LazyLz77Encoder: the chain stage also demotes a position whose successor matches longer
-inline bool lazy_of(const lfx_encode_opts &o) { return lz77_kind_of(o) == LFX_LZ77_LAZY; }
-// LFX_HUFFMAN_AUTO: the plan of dynamic_huffman = 1, every dynamic block's form chosen on the device.  Stored
-// blocks have no form to choose: no_compression leaves the flag without effect.
-inline bool auto_blocks_of(const lfx_encode_opts &o) { return o.dynamic_huffman == LFX_HUFFMAN_AUTO && !o.no_compression; }
-inline int check_opts(const lfx_encode_opts &o) {
-    if (o.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
-    if (o.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
-    if (lz77_chained(lz77_kind_of(o)) && (chain_depth_of(o) == 0 || ((uint32_t)o.lz77_kind >> 16) != 0)) return LFX_E_ARG;
-    return LFX_OK;
-}
 // E::compression_level() as lz77_level holds it (1 + LFX_LEVEL_*, 0: the kind's own): ChainLz77Encoder and LazyLz77Encoder are
 // Best unless the caller says otherwise; no_compression() resets the header's level like any other (zlib.rs:471-475, gzip.rs:703)
 inline uint8_t lz77_level_of(const lfx_encode_opts &o) {
     if (o.lz77_level == 0 && lz77_chained(lz77_kind_of(o)) && !o.no_compression) return 1 + LFX_LEVEL_BEST;
     return o.lz77_level;
 }
-inline PlanOpts plan_opts(int format, const lfx_encode_opts &o) {
-    PlanOpts p;
-    p.block_size = o.block_size;
-    p.dynamic_huffman = o.dynamic_huffman != 0;
-    p.auto_blocks = auto_blocks_of(o);
-    p.no_compression = o.no_compression != 0;
-    p.lz77_kind = lz77_kind_of(o);     // (without the depth)
-    p.window_size = o.window_size;
-    p.max_length = o.max_length;
-    p.zlib_sync = format == LFX_ZLIB && o.zlib_flush_mode == LFX_FLUSH_SYNC;
-    return p;
+
+// What one encode call does, resolved ONCE from the caller's options (encode_spec) and handed on whole: the entry points plan
+// from `plan`, the encode core (encode_prepare) takes the rest.
+struct EncodeSpec {
+    lfx_encode_opts o;            // normalised: window_size and max_length clamped, the defaults for a NULL
+    PlanOpts plan;                // what the planner reads
+    uint32_t chain_depth = 0;     // ChainLz77Encoder's or LazyLz77Encoder's depth; 0: any other kind, no chain stage
+    bool lazy = false;            // LazyLz77Encoder: the chain stage also demotes a position whose successor matches longer (§20)
+    bool auto_blocks = false;     // LFX_HUFFMAN_AUTO (§22): every dynamic block's form chosen on the device; never under no_compression
+};
+// → LFX_OK, or LFX_E_ARG for options outside the domain.  *out is filled either way (lfx_encode_index_device asks
+// encode_served before it answers for the domain).
+inline int encode_spec(int format, const lfx_encode_opts *o, EncodeSpec *out) {
+    lfx_encode_opts &d = out->o;
+    if (o) d = *o; else encode_opts_default(&d);
+    if (d.window_size > MAX_WINDOW) d.window_size = MAX_WINDOW;  // default.rs:228
+    if (d.max_length > MAX_LENGTH) d.max_length = MAX_LENGTH;    // default.rs:240
+    const int kind = lz77_kind_of(d);
+    out->chain_depth = lz77_chained(kind) ? ((uint32_t)d.lz77_kind >> 8) & 0xFFu : 0u;
+    out->lazy = kind == LFX_LZ77_LAZY;
+    out->auto_blocks = d.dynamic_huffman == LFX_HUFFMAN_AUTO && !d.no_compression;
+    PlanOpts &p = out->plan;
+    p.block_size = d.block_size;
+    p.dynamic_huffman = d.dynamic_huffman != 0;
+    p.no_compression = d.no_compression != 0;
+    p.lz77_kind = kind;                // (without the depth)
+    p.window_size = d.window_size;
+    p.max_length = d.max_length;
+    p.zlib_sync = format == LFX_ZLIB && d.zlib_flush_mode == LFX_FLUSH_SYNC;
+    if (d.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
+    if (d.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
+    if (lz77_chained(kind) && (out->chain_depth == 0 || ((uint32_t)d.lz77_kind >> 16) != 0)) return LFX_E_ARG;
+    return LFX_OK;
+}
+
+// Which entry point serves which spec and dictionary: THE table (the public contract: include/lfx.h, and
+// tests/c/encode_spec.cpp holds one against the other).  Nothing else answers LFX_E_UNSUPPORTED for a combination of options
+// and dictionary.
+enum EncodeEntry { ENC_DEVICE, ENC_BATCH, ENC_DICT_DEVICE, ENC_DICT_BATCH, ENC_STREAM, ENC_MEMBERS, ENC_INDEX, ENC_SHARD, ENC_LZ77 };
+enum DictKind { DICT_NONE, DICT_PLAIN, DICT_CHAIN };     // lfx_dict_new / lfx_dict_new_chain (§18, §21)
+// → LFX_OK (*why = nullptr), or LFX_E_UNSUPPORTED with *why.  Where a call has two reasons, the first row wins.
+inline int encode_served(EncodeEntry e, const EncodeSpec &sp, DictKind dict, const char **why) {
+    const bool chained = lz77_chained(sp.plan.lz77_kind);
+    *why = e == ENC_SHARD && sp.o.no_compression ? "sharded encode of stored blocks is not supported (their size depends on the bit phase)"
+         : e == ENC_SHARD && chained ? (sp.lazy ? "lz77_kind: the N-GPU encode does not serve LFX_LZ77_LAZY" : "lz77_kind: the N-GPU encode does not serve LFX_LZ77_CHAIN")
+         : e == ENC_SHARD && sp.auto_blocks ? "dynamic_huffman: the N-GPU encode does not serve LFX_HUFFMAN_AUTO (a stored block's size depends on the bit phase)"
+         : e == ENC_INDEX && sp.auto_blocks ? "dynamic_huffman: lfx_encode_index_device does not serve LFX_HUFFMAN_AUTO (the candidates are laid out from the host plan's block types)"
+         // ChainLz77Encoder and LazyLz77Encoder have no chain behind a plain dictionary's candidate (§19); a chain dictionary brings its own
+         : dict == DICT_PLAIN && chained ? (sp.lazy ? "lz77_kind: LFX_LZ77_LAZY with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"
+                                                    : "lz77_kind: LFX_LZ77_CHAIN with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)")
+         : nullptr;
+    return *why ? LFX_E_UNSUPPORTED : LFX_OK;
 }
 
 // gzip Header::write_to gzip.rs:368-389 (+flags 343-355, crc16 356-367)

@@ -439,18 +439,16 @@ int stage_huffman(Ctx *c, const EncCall &k) {
 
 }  // namespace
 
-int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *d_in, uint64_t n, int ck_mode, const HostCodes *hc,
-                   const lfx_dict *dict, uint32_t chain_depth) {
+int encode_prepare(Ctx *c, const Plan &plan, const EncodeSpec &sp, const uint8_t *d_in, uint64_t n, int ck_mode, const HostCodes *hc,
+                   const lfx_dict *dict) {
     (void)hipSetDevice(c->device);
     c->n_ev = 0;
     c->phase("start");
-    EncCall k{plan, po, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
-              (po.lz77_kind == LFX_LZ77_CHAIN || po.lz77_kind == LFX_LZ77_LAZY) && !hc ? chain_depth : 0u, po.lz77_kind == LFX_LZ77_LAZY,
-              po.auto_blocks && !po.no_compression,
+    EncCall k{plan, sp.plan, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
+              hc ? 0u : sp.chain_depth,     // (a caller's own code words switch the chain stage off)
+              sp.lazy, sp.auto_blocks,
               encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
-    if (k.chain_depth && k.dict && !k.dict->chain) { c->set_error("LFX_LZ77_CHAIN / LFX_LZ77_LAZY with a preset dictionary is not supported: the dictionary has no chain (lfx_dict_new_chain)"); return LFX_E_UNSUPPORTED; }
-    if ((po.lz77_kind == LFX_LZ77_CHAIN || po.lz77_kind == LFX_LZ77_LAZY) && !hc && !chain_depth) { c->set_error("LFX_LZ77_CHAIN / LFX_LZ77_LAZY: this entry point does not serve it"); return LFX_E_UNSUPPORTED; }
     if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)
     c->cur_nchunks = (uint32_t)plan.chunks.size();
     c->cur_nblocks = (uint32_t)plan.blocks.size();
@@ -528,7 +526,7 @@ int encode_emit(Ctx *c, int format, bool with_trailer, uint32_t trailer_check, b
     return LFX_OK;
 }
 
-int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &b, std::vector<uint64_t> &h_len,
+int encode_batch(Ctx *c, const Plan &plan, const EncodeSpec &sp, const BatchCall &b, std::vector<uint64_t> &h_len,
                  std::vector<int32_t> &h_status, EncodeResult &res) {
     (void)hipSetDevice(c->device);
     hipStream_t st = c->stream;
@@ -547,7 +545,7 @@ int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &
     h_len.resize(count);
     h_status.resize(count);
     return with_match_fallback(c, res, [&]() -> int {
-        if (int rc = encode_prepare(c, plan, po, b.d_in, b.in_extent, 0, nullptr, b.dict, b.chain_depth)) return rc;
+        if (int rc = encode_prepare(c, plan, sp, b.d_in, b.in_extent, 0, nullptr, b.dict)) return rc;
         HIP_TRY(hipMemcpyAsync(d_streams, b.streams.data(), sz_streams, hipMemcpyHostToDevice, st));
         if (!b.hdr.empty()) HIP_TRY(hipMemcpyAsync(d_hdr, b.hdr.data(), b.hdr.size(), hipMemcpyHostToDevice, st));
         if (trailer)
@@ -573,7 +571,7 @@ int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &
     });
 }
 
-int encode_members(Ctx *c, const Plan &plan, const PlanOpts &po, const MembersCall &m, EncodeResult &res) {
+int encode_members(Ctx *c, const Plan &plan, const EncodeSpec &sp, const MembersCall &m, EncodeResult &res) {
     hipStream_t st = c->stream;
     const MembersGeom &g = m.g;
     const uint32_t count = g.count;
@@ -590,7 +588,7 @@ int encode_members(Ctx *c, const Plan &plan, const PlanOpts &po, const MembersCa
     // bound, and nothing is written when the total exceeds cap
     c->prezero.start(m.d_out, m.fill);
     const int rc = with_match_fallback(c, res, [&]() -> int {
-        if (int rc2 = encode_prepare(c, plan, po, m.d_in, g.n, 0, nullptr, nullptr, m.chain_depth)) return rc2;
+        if (int rc2 = encode_prepare(c, plan, sp, m.d_in, g.n, 0, nullptr, nullptr)) return rc2;
         HIP_TRY(hipMemcpyAsync(d_hdr, m.hdr.data(), m.hdr.size(), hipMemcpyHostToDevice, st));
         EncodeResult *dres = (EncodeResult *)c->d_res.p;
         LAUNCH_TRY(launch_members_layout(st, g, (BlockDesc *)c->d_blocks.p, (const BlockCodes *)c->d_bc.p, d_local, d_mlen, d_wg, m.cap,

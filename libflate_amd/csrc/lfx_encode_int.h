@@ -6,6 +6,7 @@
 #include "lfx_ctx.h"
 #include "lfx_device.h"
 #include "lfx_dict.h"
+#include "lfx_enc_frame.h"
 #include "lfx_plan.h"
 #include "lfx_try.h"
 #include "lfx_verdict.h"
@@ -19,15 +20,23 @@ struct HostCodes {
     const uint32_t *chunk_codes;  // codes per chunk of the plan
 };
 
+// an entry point asks the table (encode_served, lfx_enc_frame.h) about its call; the reason becomes the context's error
+inline int served(Ctx *c, EncodeEntry e, const EncodeSpec &sp, const lfx_dict *dict = nullptr) {
+    const char *why;
+    const int rc = encode_served(e, sp, !dict ? DICT_NONE : dict->chain ? DICT_CHAIN : DICT_PLAIN, &why);
+    if (rc) c->set_error(why);
+    return rc;
+}
+
 // Stage A: plan upload → match → parse → histogram → Huffman (+ checksum: ck_mode 1 CRC-32, 2 Adler-32, 3 both — a shard, whose
 // caller folds either).  Leaves everything the emit stage needs in the context.
 // dict: a preset dictionary — the plan's CH_DICT chunks take their open candidates from it and the parse reads
 // its window; nullptr: the kernels and launches of a dictionary-less call, unchanged.
-// chain_depth: with po.lz77_kind == LFX_LZ77_CHAIN or LFX_LZ77_LAZY the depth the options name (chain_depth_of, DESIGN.md §19,
-// §20) — the chain stage runs between the match and the parse, for LFX_LZ77_LAZY with its demotion; any other kind: not read,
-// no stage, no second candidate buffer.
-int encode_prepare(Ctx *c, const Plan &plan, const PlanOpts &po, const uint8_t *d_in, uint64_t n, int ck_mode,
-                   const HostCodes *hc = nullptr, const lfx_dict *dict = nullptr, uint32_t chain_depth = 0);
+// sp: the call's resolved options (encode_spec), which its entry point has asked encode_served about.  With a chain depth the
+// chain stage runs between the match and the parse, for LFX_LZ77_LAZY with its demotion (§20); without: no
+// stage, no second candidate buffer.
+int encode_prepare(Ctx *c, const Plan &plan, const EncodeSpec &sp, const uint8_t *d_in, uint64_t n, int ck_mode,
+                   const HostCodes *hc = nullptr, const lfx_dict *dict = nullptr);
 // Stage B: offsets → pack → framing.  `prefix` bytes are placed at the start of d_out; the DEFLATE bits start at bit
 // `start_bit` of d_out (prefix may end with a partial byte).
 // async_slot (page-locked, the caller's own): the result is copied there and the call returns WITHOUT waiting — the stream
@@ -64,9 +73,8 @@ struct BatchCall {
     uint8_t *d_out;
     uint64_t out_lo, out_hi;      // the span of d_out the streams' ranges lie in
     const lfx_dict *dict = nullptr;   // lfx_encode_batch_dict_device: primes every stream's first chunk
-    uint32_t chain_depth = 0;         // LFX_LZ77_CHAIN, LFX_LZ77_LAZY: the depth
 };
-int encode_batch(Ctx *c, const Plan &plan, const PlanOpts &po, const BatchCall &b, std::vector<uint64_t> &h_len,
+int encode_batch(Ctx *c, const Plan &plan, const EncodeSpec &sp, const BatchCall &b, std::vector<uint64_t> &h_len,
                  std::vector<int32_t> &h_status, EncodeResult &res);
 // lfx_encode_members_device behind its argument checks and the merged plan
 struct MembersCall {
@@ -77,8 +85,7 @@ struct MembersCall {
     uint64_t cap, fill;           // fill: bytes of d_out to zero, min(cap, bound)
     lfx_member *members;
     uint32_t n_rec;               // records the caller has room for
-    uint32_t chain_depth = 0;     // LFX_LZ77_CHAIN, LFX_LZ77_LAZY: the depth
 };
-int encode_members(Ctx *c, const Plan &plan, const PlanOpts &po, const MembersCall &m, EncodeResult &res);
+int encode_members(Ctx *c, const Plan &plan, const EncodeSpec &sp, const MembersCall &m, EncodeResult &res);
 
 }  // namespace lfx

@@ -346,14 +346,14 @@ extern "C" int lfx_encode_index_device(lfx_ctx *cc, int format, const lfx_encode
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     if (!idx) { c->set_error("lfx_encode_index_device: idx is NULL"); return LFX_E_ARG; }
     if (spacing < 4096) { c->set_error("lfx_encode_index_device: spacing " + std::to_string(spacing) + " is below 4096"); return LFX_E_ARG; }
-    if (o && auto_blocks_of(norm_opts(o))) {
-        c->set_error("dynamic_huffman: lfx_encode_index_device does not serve LFX_HUFFMAN_AUTO (the candidates are laid out from the host plan's block types)");
-        return LFX_E_UNSUPPORTED;
-    }
+    EncodeSpec sp;
+    (void)encode_spec(format, o, &sp);      // (the table answers before the domain does: lfx_encode_device checks that)
+    const char *why;
+    int rc = encode_served(ENC_INDEX, sp, DICT_NONE, &why);
+    if (rc) { c->set_error(why); return rc; }
     IdxCollect col;
     col.spacing = spacing;
     uint64_t ol = 0;
-    int rc;
     {
         EncIdxScope scope(c, &col);
         rc = lfx_encode_device(cc, format, o, s, d_in, n, d_out, cap, &ol);

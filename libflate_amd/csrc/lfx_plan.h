@@ -24,8 +24,6 @@ struct PlanOpts {
     uint32_t window_size = MAX_WINDOW;
     uint32_t max_length = MAX_LENGTH;
     bool zlib_sync = false;  // zlib FlushMode::Sync (only meaningful for the zlib container)
-    bool auto_blocks = false;  // LFX_HUFFMAN_AUTO: not read by the planner — the plan is dynamic_huffman's; the encode
-                               // core picks every dynamic block's form on the device, behind the Huffman kernel
 };
 
 struct Plan {

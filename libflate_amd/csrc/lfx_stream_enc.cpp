@@ -20,8 +20,7 @@ namespace {
 struct GpuBatches {
     Ctx *c = nullptr;
     int format = 0;
-    PlanOpts po;
-    uint32_t chain_depth = 0;           // LFX_LZ77_CHAIN, LFX_LZ77_LAZY: the depth (bytes mode; a coded batch brings its own code words)
+    const EncodeSpec *spec = nullptr;   // the encoder's (StreamEnc::spec)
     DevBuf d_in, d_out;
     PinVec h_out;                       // a batch's output lands here (page-locked) and goes to the sink from here: no copy between
     PinVec h_res;                       // result slot + the shared byte
@@ -33,7 +32,7 @@ struct GpuBatches {
     int encode(EncodeResult *res, EncodeResult *async_slot, std::string &err) {
         const uint8_t prefix[1] = {cur.carry};
         const HostCodes hc{cur.codes, cur.n_codes, cur.chunk_codes};
-        int rc = encode_prepare(c, cur.plan, po, (const uint8_t *)d_in.p, cur.n, ck_mode_of(format), cur.coded ? &hc : nullptr, nullptr, chain_depth);
+        int rc = encode_prepare(c, cur.plan, *spec, (const uint8_t *)d_in.p, cur.n, ck_mode_of(format), cur.coded ? &hc : nullptr);
         if (!rc) rc = encode_emit(c, LFX_DEFLATE, false, 0, true, 0, prefix, cur.carry_bits ? 1 : 0, cur.carry_bits, (uint8_t *)d_out.p,
                                   cur.bound & ~3ull, res, async_slot);
         if (rc) err = c->err;
@@ -113,14 +112,15 @@ extern "C" void lfx_encoder_free(lfx_encoder *e);
 extern "C" lfx_encoder *lfx_encoder_new(lfx_ctx *cc, int format, const lfx_encode_opts *o, lfx_write_cb w,
                                         lfx_flush_cb f, void *user, int *status) try {
     if (!cc || !w) { if (status) *status = cc ? LFX_E_ARG : LFX_E_DEVICE; return nullptr; }
-    lfx_encode_opts d = norm_opts(o);
-    int rc = check_opts(d);
+    EncodeSpec sp;
+    const char *why;
+    int rc = encode_spec(format, o, &sp);
+    if (!rc) rc = encode_served(ENC_STREAM, sp, DICT_NONE, &why);
     if (rc) { if (status) *status = rc; return nullptr; }
-    lfx_encoder *e = new lfx_encoder(format, d);
+    lfx_encoder *e = new lfx_encoder(format, sp);
     Ctx *c = e->backend.c = reinterpret_cast<Ctx *>(cc);
     e->backend.format = format;
-    e->backend.po = e->po;
-    e->backend.chain_depth = chain_depth_of(d);
+    e->backend.spec = &e->spec;
     if (c->diag.enc_batch_mb > 0) e->pol.batch_bytes = (uint64_t)c->diag.enc_batch_mb << 20;
     // (page-locked and device buffers of an earlier encoder of this context, when there are any)
     e->pending = c->take_pin();

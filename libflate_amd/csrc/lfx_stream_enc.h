@@ -113,11 +113,10 @@ struct StreamEnc {
     Backend backend;
     BatchPolicy pol;
     int format;
-    lfx_encode_opts o;                  // normalised; filename / comment / extra point into the copies below
+    EncodeSpec spec;                    // resolved (encode_spec); its options' filename / comment / extra point into the copies below
     std::string filename, comment;
     std::vector<uint8_t> extra;
-    PlanOpts po;
-    Planner pl;                         // incremental write-schedule state (chunks / blocks of `pending`)
+    Planner pl;                        // incremental write-schedule state (chunks / blocks of `pending`)
     lfx_write_cb w = nullptr;
     lfx_flush_cb f = nullptr;
     void *user = nullptr;
@@ -140,11 +139,12 @@ struct StreamEnc {
     uint64_t closed_codes = 0, open_codes = 0;
     bool final_closed = false;
 
-    // d: normalised and checked (norm_opts, check_opts)
-    StreamEnc(int format_, const lfx_encode_opts &d) : format(format_), o(d), po(plan_opts(format_, d)), pl(po) {
-        if (d.filename) { filename = d.filename; o.filename = filename.c_str(); }
-        if (d.comment) { comment = d.comment; o.comment = comment.c_str(); }
-        if (d.extra) { extra.assign(d.extra, d.extra + d.extra_len); o.extra = extra.data(); }
+    // sp: what encode_spec(format_, ...) resolved
+    StreamEnc(int format_, const EncodeSpec &sp) : format(format_), spec(sp), pl(spec.plan) {
+        lfx_encode_opts &o = spec.o;
+        if (o.filename) { filename = o.filename; o.filename = filename.c_str(); }
+        if (o.comment) { comment = o.comment; o.comment = comment.c_str(); }
+        if (o.extra) { extra.assign(o.extra, o.extra + o.extra_len); o.extra = extra.data(); }
     }
     StreamEnc(const StreamEnc &) = delete;
     StreamEnc &operator=(const StreamEnc &) = delete;
@@ -273,7 +273,7 @@ int enc_run(E *e, bool final, bool drain = true) {
 template <class E>
 int enc_open(E *e) {
     std::vector<uint8_t> hdr;
-    if (int rc = container_header(e->format, e->o, hdr)) return rc;
+    if (int rc = container_header(e->format, e->spec.o, hdr)) return rc;
     return enc_sink(e, hdr.data(), hdr.size());
 }
 
@@ -287,9 +287,9 @@ int64_t enc_write(E *e, const uint8_t *p, size_t n) {
     e->pending.insert(e->pending.end(), p, p + n);
     e->pl.write(n);
     e->total_in += n;
-    if (e->pl.closed_bytes() >= e->pol.batch_bytes || (e->po.no_compression && e->pl.closed_blocks() >= e->pol.raw_blocks)) {
+    if (e->pl.closed_bytes() >= e->pol.batch_bytes || (e->spec.plan.no_compression && e->pl.closed_blocks() >= e->pol.raw_blocks)) {
         // the batch is started; the next one — or flush / finish — collects it.  Stored blocks leave as they are closed.
-        int rc = enc_run(e, false, /*drain=*/e->po.no_compression);
+        int rc = enc_run(e, false, /*drain=*/e->spec.plan.no_compression);
         if (rc) { e->failed = true; return -(int64_t)rc; }
     }
     return (int64_t)n;  // encode.rs:243: always consumes everything
@@ -300,7 +300,7 @@ int enc_write_codes(E *e, const uint32_t *codes, size_t n_codes, const uint8_t *
     if (e->finished || e->final_closed || end_block < 0 || end_block > 2 || (n_codes && !codes) || (n_raw && !raw)) return LFX_E_ARG;
     if (e->failed) return LFX_E_IO;
     // stored blocks never run an Lz77Encode (RawBuf, encode.rs:348-383); bytes and codes cannot be mixed on one encoder
-    if (e->mode == 1 || e->po.no_compression) { e->err = "lfx_encoder_write_codes on an encoder that takes bytes"; return LFX_E_ARG; }
+    if (e->mode == 1 || e->spec.plan.no_compression) { e->err = "lfx_encoder_write_codes on an encoder that takes bytes"; return LFX_E_ARG; }
     for (size_t i = 0; i < n_codes; i++) {       // Code::Literal(u8) / Code::Pointer{3..=258, 1..=32768} (lib.rs:27-42)
         const uint32_t dist = codes[i] & 0xFFFFu, val = codes[i] >> 16;
         if (dist == 0 ? val > 255 : (val < 3 || val > MAX_LENGTH || dist > MAX_WINDOW)) { e->err = "code word outside Code's domain"; return LFX_E_ARG; }
@@ -312,7 +312,7 @@ int enc_write_codes(E *e, const uint32_t *codes, size_t n_codes, const uint8_t *
     e->total_in += n_raw;
     if (!end_block) return LFX_OK;
     e->codes.push_back(CODE_EOB);            // encode.rs:417
-    e->cblocks.push_back(CodeBlock{e->open_codes + 1, e->po.dynamic_huffman ? (uint32_t)BT_DYNAMIC : (uint32_t)BT_FIXED, end_block == 2 ? 1u : 0u});
+    e->cblocks.push_back(CodeBlock{e->open_codes + 1, e->spec.plan.dynamic_huffman ? (uint32_t)BT_DYNAMIC : (uint32_t)BT_FIXED, end_block == 2 ? 1u : 0u});
     e->closed_codes += e->open_codes + 1;
     e->open_codes = 0;
     if (end_block == 2) e->final_closed = true;
@@ -332,7 +332,7 @@ int enc_flush(E *e) {
     if (e->mode == 2) {
         // the caller closed the block with E::flush()'s codes (end_block = 1) — Encoder::flush is Block::flush (encode.rs:245-248)
         if (e->open_codes) { e->err = "close the open block first (end_block = 1)"; return LFX_E_ARG; }
-        if (e->po.zlib_sync) e->cblocks.push_back(CodeBlock{0, (uint32_t)BT_RAW, 0u});   // zlib_sync_flush encode.rs:225-234
+        if (e->spec.plan.zlib_sync) e->cblocks.push_back(CodeBlock{0, (uint32_t)BT_RAW, 0u});   // zlib_sync_flush encode.rs:225-234
     } else {
         e->pl.flush();
     }

@@ -132,7 +132,7 @@ class ChainLz77Encoder:
         return self._window
 
     def _opts(self):
-        # (a depth outside 1..255 reaches check_opts as it is: LFX_E_ARG, not a silently different depth)
+        # (a depth outside 1..255 reaches encode_spec as it is: LFX_E_ARG, not a silently different depth)
         return {"lz77_kind": _ffi.LZ77_CHAIN | (self._depth if 0 <= self._depth <= 255 else 256) << 8,
                 "window_size": self._window, "max_length": self._max_length}
 

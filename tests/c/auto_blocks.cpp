@@ -21,6 +21,9 @@ static lfx_encode_opts with_huffman(int32_t v) {
     o.dynamic_huffman = v;
     return o;
 }
+// the options resolved (encode_spec): the status beside the spec
+struct Resolved { int rc; EncodeSpec sp; };
+static Resolved resolve(int format, const lfx_encode_opts &o) { Resolved r; r.rc = encode_spec(format, &o, &r.sp); return r; }
 static bool same_plan(const Plan &a, const Plan &b) {
     if (a.chunks.size() != b.chunks.size() || a.blocks.size() != b.blocks.size() || a.n_codes_cap != b.n_codes_cap ||
         a.n_tiles != b.n_tiles || a.n_vis != b.n_vis || a.n_segs != b.n_segs) return false;
@@ -62,9 +65,9 @@ int main() {
     const int32_t values[5] = {0, 1, 2, 3, -1};
     for (int32_t v : values) {
         const lfx_encode_opts o = with_huffman(v);
-        CHECK(check_opts(o) == LFX_OK);
-        const PlanOpts p = plan_opts(LFX_ZLIB, o);
-        CHECK(p.dynamic_huffman == (v != 0) && p.auto_blocks == (v == 2) && auto_blocks_of(o) == (v == 2));
+        const Resolved r = resolve(LFX_ZLIB, o);
+        CHECK(r.rc == LFX_OK);
+        CHECK(r.sp.plan.dynamic_huffman == (v != 0) && r.sp.auto_blocks == (v == 2));
         std::vector<uint8_t> h1, hv;
         CHECK(container_header(LFX_ZLIB, with_huffman(1), h1) == LFX_OK && container_header(LFX_ZLIB, o, hv) == LFX_OK && h1 == hv);
         h1.clear(); hv.clear();
@@ -73,8 +76,8 @@ int main() {
     {
         lfx_encode_opts o = with_huffman(LFX_HUFFMAN_AUTO);
         o.no_compression = 1;                                      // stored blocks have no form to choose
-        CHECK(!auto_blocks_of(o) && !plan_opts(LFX_DEFLATE, o).auto_blocks);
-        CHECK(!PlanOpts().auto_blocks);
+        CHECK(resolve(LFX_DEFLATE, o).rc == LFX_OK && !resolve(LFX_DEFLATE, o).sp.auto_blocks);
+        CHECK(!EncodeSpec().auto_blocks);
     }
 
     // ---- seeded plans: the plan of 2 is the plan of 1; in_off / in_len of every compressed block; Plan::append; take_closed
@@ -86,7 +89,7 @@ int main() {
         o1.block_size = o2.block_size = 1 + rng() % (1u << (10 + rng() % 11));
         o1.lz77_kind = o2.lz77_kind = (int32_t)(rng() % 4 == 0 ? LFX_LZ77_LAZY_DEPTH(8) : rng() % 4 == 1 ? LFX_LZ77_CHAIN_DEPTH(8) : 0);
         o1.zlib_flush_mode = o2.zlib_flush_mode = rng() % 3 == 0 ? LFX_FLUSH_SYNC : LFX_FLUSH_NONE;
-        const PlanOpts p1 = plan_opts(LFX_ZLIB, o1), p2 = plan_opts(LFX_ZLIB, o2);
+        const PlanOpts p1 = resolve(LFX_ZLIB, o1).sp.plan, p2 = resolve(LFX_ZLIB, o2).sp.plan;
         Planner a(p1), b(p2), c(p2), d(p2);
         Plan stitched;
         uint64_t byte0 = 0;

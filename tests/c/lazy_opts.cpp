@@ -21,6 +21,9 @@ static lfx_encode_opts with_kind(int32_t kind) {
     o.lz77_kind = kind;
     return o;
 }
+// the options resolved (encode_spec): the status beside the spec
+struct Resolved { int rc; EncodeSpec sp; };
+static Resolved resolve(int format, const lfx_encode_opts &o) { Resolved r; r.rc = encode_spec(format, &o, &r.sp); return r; }
 static bool same_plan(const Plan &a, const Plan &b) {
     if (a.chunks.size() != b.chunks.size() || a.blocks.size() != b.blocks.size() || a.n_codes_cap != b.n_codes_cap ||
         a.n_tiles != b.n_tiles || a.n_vis != b.n_vis || a.n_segs != b.n_segs) return false;
@@ -38,24 +41,27 @@ int main() {
     CHECK(LFX_LZ77_LAZY == 3 && LFX_LZ77_LAZY_DEPTH(8) == (3 | 8 << 8));
     for (int k = 1; k <= 255; k++) {
         const lfx_encode_opts o = with_kind(LFX_LZ77_LAZY_DEPTH(k));
-        CHECK(check_opts(o) == LFX_OK && lz77_kind_of(o) == LFX_LZ77_LAZY && chain_depth_of(o) == (uint32_t)k && lazy_of(o));
-        CHECK(plan_opts(LFX_ZLIB, o).lz77_kind == 3);                       // the plan sees the kind without the depth
+        const Resolved r = resolve(LFX_ZLIB, o);
+        CHECK(r.rc == LFX_OK && lz77_kind_of(o) == LFX_LZ77_LAZY && r.sp.chain_depth == (uint32_t)k && r.sp.lazy);
+        CHECK(r.sp.plan.lz77_kind == 3);                                    // the plan sees the kind without the depth
     }
-    CHECK(check_opts(with_kind(LFX_LZ77_LAZY)) == LFX_E_ARG);               // depth 0: there is no default depth
-    CHECK(check_opts(with_kind(LFX_LZ77_LAZY_DEPTH(256))) == LFX_E_ARG);    // bit 16
-    for (int bit = 16; bit < 32; bit++) CHECK(check_opts(with_kind((int32_t)((uint32_t)LFX_LZ77_LAZY_DEPTH(8) | 1u << bit))) == LFX_E_ARG);
+    CHECK(resolve(LFX_ZLIB, with_kind(LFX_LZ77_LAZY)).rc == LFX_E_ARG);               // depth 0: there is no default depth
+    CHECK(resolve(LFX_ZLIB, with_kind(LFX_LZ77_LAZY_DEPTH(256))).rc == LFX_E_ARG);    // bit 16
+    for (int bit = 16; bit < 32; bit++) CHECK(resolve(LFX_ZLIB, with_kind((int32_t)((uint32_t)LFX_LZ77_LAZY_DEPTH(8) | 1u << bit))).rc == LFX_E_ARG);
     // the kinds 0, 1 and 2 answer as before
     for (int kind = 0; kind <= 1; kind++) {
         const lfx_encode_opts o = with_kind(kind | 0x1200);
-        CHECK(check_opts(o) == LFX_OK && lz77_kind_of(o) == kind && chain_depth_of(o) == 0 && !lazy_of(o) && plan_opts(LFX_GZIP, o).lz77_kind == kind);
+        const Resolved r = resolve(LFX_GZIP, o);
+        CHECK(r.rc == LFX_OK && lz77_kind_of(o) == kind && r.sp.chain_depth == 0 && !r.sp.lazy && r.sp.plan.lz77_kind == kind);
     }
     for (int k = 1; k <= 255; k++) {
         const lfx_encode_opts o = with_kind(LFX_LZ77_CHAIN_DEPTH(k));
-        CHECK(check_opts(o) == LFX_OK && lz77_kind_of(o) == LFX_LZ77_CHAIN && chain_depth_of(o) == (uint32_t)k && !lazy_of(o));
-        CHECK(plan_opts(LFX_ZLIB, o).lz77_kind == 2);
+        const Resolved r = resolve(LFX_ZLIB, o);
+        CHECK(r.rc == LFX_OK && lz77_kind_of(o) == LFX_LZ77_CHAIN && r.sp.chain_depth == (uint32_t)k && !r.sp.lazy);
+        CHECK(r.sp.plan.lz77_kind == 2);
     }
-    CHECK(check_opts(with_kind(LFX_LZ77_CHAIN)) == LFX_E_ARG);
-    for (int bit = 16; bit < 32; bit++) CHECK(check_opts(with_kind((int32_t)((uint32_t)LFX_LZ77_CHAIN_DEPTH(8) | 1u << bit))) == LFX_E_ARG);
+    CHECK(resolve(LFX_ZLIB, with_kind(LFX_LZ77_CHAIN)).rc == LFX_E_ARG);
+    for (int bit = 16; bit < 32; bit++) CHECK(resolve(LFX_ZLIB, with_kind((int32_t)((uint32_t)LFX_LZ77_CHAIN_DEPTH(8) | 1u << bit))).rc == LFX_E_ARG);
     CHECK(lz77_chained(2) && lz77_chained(3) && !lz77_chained(0) && !lz77_chained(1) && !lz77_chained(4));
 
     // ---- the container headers: Best unless the caller names a level; no_compression resets it

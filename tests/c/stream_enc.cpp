@@ -250,9 +250,9 @@ static Enc *make_enc(const Case &cs, Shared &sh, int *status) {
     o.dynamic_huffman = cs.dynamic;
     o.no_compression = cs.no_compression;
     o.zlib_flush_mode = cs.zsync ? LFX_FLUSH_SYNC : 0;
-    const lfx_encode_opts d = norm_opts(&o);
-    if ((*status = check_opts(d))) return nullptr;
-    Enc *e = new Enc(cs.format, d);
+    EncodeSpec sp;
+    if ((*status = encode_spec(cs.format, &o, &sp))) return nullptr;
+    Enc *e = new Enc(cs.format, sp);
     e->backend.sh = &sh;
     e->pol = cs.pol;
     e->w = sink_cb; e->f = flush_cb; e->user = &sh;
@@ -501,12 +501,14 @@ static void test_failures() {
         lfx_encode_opts o;
         encode_opts_default(&o);
         o.block_size = 0;
-        CHECK(check_opts(norm_opts(&o)) == LFX_E_ARG, "block_size 0");
+        EncodeSpec sp;
+        CHECK(encode_spec(LFX_GZIP, &o, &sp) == LFX_E_ARG, "block_size 0");
         Bytes big(70000, 1);
         encode_opts_default(&o);
         o.extra = big.data(); o.extra_len = 70000;
         Shared sh;
-        Enc *e = new Enc(LFX_GZIP, norm_opts(&o));
+        CHECK(encode_spec(LFX_GZIP, &o, &sp) == LFX_OK, "default options");
+        Enc *e = new Enc(LFX_GZIP, sp);
         e->backend.sh = &sh; e->w = sink_cb; e->user = &sh;
         CHECK(enc_open(e) == LFX_E_INVALID_DATA && sh.sink_calls == 0, "an extra field beyond 65535 bytes");
         free_enc(e, sh);

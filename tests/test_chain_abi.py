@@ -32,7 +32,7 @@ def test_constants_in_the_header_and_their_mirror(lfx):
 
 
 def test_the_option_check_through_encode_bound(lfx):
-    """lfx_encode_bound is 0 for options check_opts refuses"""
+    """lfx_encode_bound is 0 for options encode_spec refuses"""
     from libflate_amd import _ffi
     L = _ffi.lib()
     bound = lambda kind: L.lfx_encode_bound(1000, C.byref(_ffi.make_opts(lz77_kind=kind)), None)

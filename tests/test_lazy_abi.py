@@ -35,7 +35,7 @@ def test_constants_in_the_header_and_their_mirrors(lfx):
 
 
 def test_the_option_check_through_encode_bound(lfx):
-    """lfx_encode_bound is 0 for options check_opts refuses"""
+    """lfx_encode_bound is 0 for options encode_spec refuses"""
     from libflate_amd import _ffi
     L = _ffi.lib()
     bound = lambda kind: L.lfx_encode_bound(1000, C.byref(_ffi.make_opts(lz77_kind=kind)), None)
@@ -65,7 +65,7 @@ def test_python_encoder_options(lfx):
     o = lfx.deflate.EncodeOptions().with_lz77(lfx.lz77.LazyLz77Encoder(32))._to_c()
     assert o.lz77_kind == 3 | 32 << 8
     L = _ffi.lib()
-    for depth in (0, 256, -1):      # reaches check_opts unchanged: refused, not a silently different depth
+    for depth in (0, 256, -1):      # reaches encode_spec unchanged: refused, not a silently different depth
         assert L.lfx_encode_bound(10, C.byref(lfx.zlib.EncodeOptions(lz77=lfx.lz77.LazyLz77Encoder(depth))._to_c()), None) == 0
     for fmt in (0, 1, 2):
         assert L.lfx_container_header_len(fmt, C.byref(_ffi.make_opts(lz77_kind=3 | 8 << 8))) == L.lfx_container_header_len(fmt, None)
