@@ -77,6 +77,42 @@ enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1, LFX_LZ77_CHAIN = 2, LFX
  * Bits 8..15 hold the depth K, 1..255; depth 0 or any bit above 15 set: LFX_E_ARG.  Served and refused (LFX_E_UNSUPPORTED)
  * by the same entry points as LFX_LZ77_CHAIN. */
 #define LFX_LZ77_LAZY_DEPTH(k) (LFX_LZ77_LAZY | (k) << 8)
+/* LFX_LZ77_LEVEL — LevelLz77Encoder(level 1..9, window_size W, max_length M): the chained parse tuned the way zlib's deflate
+ * tunes its own, by one number.  Opt-in, a kind of its own; the output is NOT bit-exact with zlib's and does
+ * not claim to be.  The level resolves into five values, zlib's configuration_table without good_length:
+ *
+ *      level  walk     depth K   nice N   max_lazy Z   too_far F
+ *        1    greedy       4        8         -            -
+ *        2    greedy       8       16         -            -
+ *        3    greedy      32       32         -            -
+ *        4    lazy        16       16         4          4096
+ *        5    lazy        32       32        16          4096
+ *        6    lazy       128      128        16          4096
+ *        7    lazy       256      128        32          4096
+ *        8    lazy      1024      258       128          4096
+ *        9    lazy      4096      258       258          4096
+ *
+ *  - Buffering is ChainLz77Encoder's; window_size and max_length hold as for it.  lim = min(M, n - i) at a position i.
+ *  - Candidates: c1 .. cK as for LFX_LZ77_CHAIN (most recent first, cut off at the first one farther than W).  The walk along
+ *    them ends behind the first candidate whose length is >= min(N, lim); that candidate is included.  L(p), D(p): the greatest
+ *    length among the candidates walked and its distance, among equal lengths the nearest; L(p) = 0 without a candidate and for
+ *    every p >= end.
+ *  - Too far (the lazy levels only): L(p) == 3 and D(p) > F: the position has no candidate, L(p) = 0.
+ *  - The greedy walk (levels 1..3) is LFX_LZ77_CHAIN's over these L and D.
+ *  - The lazy walk (levels 4..9) at a visited i < end: Pointer{L(i), D(i)}, i += L(i) when L(i) != 0 and (L(i) >= Z or
+ *    L(i + 1) <= L(i)); otherwise Literal(buf[i]), i += 1.  A position is deferred exactly when L(i + 1) > L(i) and L(i) < Z.
+ *    The tail is the reference's (default.rs:105-107).
+ *  - L and D are functions of the position alone, as for the kinds 2 and 3.  zlib's good_length is NOT modelled: it shortens
+ *    the search at p + 1 to a quarter of the chain when the match at p has good_length bytes or more, which makes L(p + 1)
+ *    depend on what the walk did at p — there would be no per-position L to compute ahead of the walk.
+ *  - compression_level(), with lz77_level == 0: Fast for the levels 1..3 (zlib's FLEVEL 1, gzip's XFL 4), Balance for 4..6
+ *    (FLEVEL 2, XFL 0), Best for 7..9 (FLEVEL 3, XFL 2).  A caller's lz77_level wins; no_compression resets it, as for any kind.
+ * lz77_kind & 0xFF is the kind; bits 8..15 hold the level.  Level 0, a level above 9 or any bit above 15 set: LFX_E_ARG.
+ * Served and refused (LFX_E_UNSUPPORTED) by the same entry points as LFX_LZ77_CHAIN and LFX_LZ77_LAZY, LFX_HUFFMAN_AUTO and a
+ * chain dictionary included; through a chain dictionary the candidates run on into the dictionary's tail as theirs do, under
+ * the same rules. */
+enum { LFX_LZ77_LEVEL = 4 };
+#define LFX_LZ77_LEVEL_N(n) (LFX_LZ77_LEVEL | (n) << 8)
 /* lfx_encode_opts::dynamic_huffman.  0: fixed codes for every block (fixed_huffman_codes(), encode.rs:107-110).  1, and every
  * value other than 0 and 2: dynamic codes for every block (the reference's default).
  * LFX_HUFFMAN_AUTO (2) — opt-in, not a reference option: per block the smallest of the dynamic, the fixed and
@@ -95,7 +131,8 @@ enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1, LFX_LZ77_CHAIN = 2, LFX
  * Served by lfx_encode_device / _host, lfx_encode_batch_device, the dictionary encode calls (plain and chain dictionaries),
  * lfx_encoder_* (codes mode: fixed or dynamic only) and lfx_encode_members_* (BGZF: the 64 KiB fallback is evaluated on the
  * chosen sizes), with the lz77 kinds 0, 2 and 3.  LFX_E_UNSUPPORTED from lfx_encode_index_device and from the N-GPU encode
- * (lfx_encode_shard_prepare, lfx_sharded_encode_begin): a stored block's size depends on the bit phase there. */
+ * (lfx_encode_shard_prepare, lfx_sharded_encode_begin): a stored block's size depends on the bit phase there.  LFX_LZ77_LEVEL
+ * (kind 4) is served and refused with LFX_HUFFMAN_AUTO exactly as the kinds 2 and 3 are. */
 enum { LFX_HUFFMAN_FIXED = 0, LFX_HUFFMAN_DYNAMIC = 1, LFX_HUFFMAN_AUTO = 2 };
 /* zlib::FlushMode (src/zlib.rs:184-195) */
 enum { LFX_FLUSH_NONE = 0, LFX_FLUSH_SYNC = 2 };
@@ -750,7 +787,8 @@ int lfx_encode_batch_dict_device(lfx_ctx *c, int format, const lfx_encode_opts *
 
 /* ---- a chain dictionary: LFX_LZ77_CHAIN and LFX_LZ77_LAZY through a preset dictionary ----
  * lfx_dict_new_chain makes a dictionary that also carries the hash chain of its own tail.  With it lfx_encode_dict_device,
- * lfx_encode_dict_host and lfx_encode_batch_dict_device serve LFX_LZ77_CHAIN_DEPTH(K) and LFX_LZ77_LAZY_DEPTH(K); a dictionary
+ * lfx_encode_dict_host and lfx_encode_batch_dict_device serve LFX_LZ77_CHAIN_DEPTH(K), LFX_LZ77_LAZY_DEPTH(K) and
+ * LFX_LZ77_LEVEL_N(n) (its candidates, its nice cut and its too-far rule over the same chain); a dictionary
  * made by lfx_dict_new keeps LFX_E_UNSUPPORTED for them.  For the kinds 0 and 1 and for every decode call a chain dictionary
  * is a plain one.  Arguments, status and lifetime are lfx_dict_new's.
  *

@@ -103,6 +103,12 @@ LFX_HD inline DemoteSpan demote_span(uint64_t in_off, uint64_t len, uint64_t p0,
     return s;
 }
 
+// the tuned instances' arguments (LFX_LZ77_LEVEL): a chain walk ends behind the first candidate of
+// min(lim, nice) bytes or more, and a 3-byte match farther than too_far counts as no candidate (0xFFFFFFFF: none is)
+struct ChainTune {
+    uint32_t nice, too_far;
+};
+
 #ifdef __HIPCC__
 // the dictionary instance's arguments: lfx_dict's window (MAX_WINDOW bytes, the tail at their end), the tail's chain on the
 // same grid (launch_dict_chain), its prefix table and its length
@@ -118,13 +124,16 @@ struct ChainDict {
 // chain kernel's variant also leaves each listed position's length there (L - 3; 0 without a candidate), for launch_demote.
 // dict (a chain dictionary; nullptr: every item runs today's instance): the items from n_plain on are
 // chain_items_dict's second run and go, in a launch of their own, to the dictionary instance.
+// tune (LFX_LZ77_LEVEL; nullptr: the instances of the kinds 2 and 3, unchanged): the tuned instances, which
+// always write len (it must not be nullptr); depth is not bound by the 255 of the other kinds' bit field.
 int launch_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, const ChainItem *items,
                  uint32_t nitems, bool small, uint32_t window, uint32_t max_len, uint32_t depth, const uint16_t *cd, uint16_t *cd2,
-                 uint8_t *len = nullptr, uint32_t n_plain = 0xFFFFFFFFu, const ChainDict *dict = nullptr);
+                 uint8_t *len = nullptr, uint32_t n_plain = 0xFFFFFFFFu, const ChainDict *dict = nullptr, const ChainTune *tune = nullptr);
 // LazyLz77Encoder, behind launch_chain on the same stream and over the same work list: cd2[p] ← 0 for every listed position p
 // with p + 1 < end and len[p + 1] > len[p].  len is only read; nothing but the listed positions' cd2 is written.
+// max_lazy (LFX_LZ77_LEVEL; 0: LazyLz77Encoder's kernel, unchanged): only positions with a length below max_lazy are demoted.
 int launch_demote(hipStream_t st, const ChunkDesc *chunks, const ChainItem *items, uint32_t nitems, bool small, const uint8_t *len,
-                  uint16_t *cd2);
+                  uint16_t *cd2, uint32_t max_lazy = 0);
 #endif
 
 }  // namespace lfx

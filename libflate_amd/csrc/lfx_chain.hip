@@ -1,5 +1,5 @@
 // lfx_chain.hip — ChainLz77Encoder's candidate refinement (LFX_LZ77_CHAIN) and LazyLz77Encoder's demotion on top
-// of it (LFX_LZ77_LAZY, §20: demote_kernel below), for gfx950.
+// of it (LFX_LZ77_LAZY, §20: demote_kernel below), for gfx950; LevelLz77Encoder's tuned instances of both (LFX_LZ77_LEVEL, §23).
 //
 // The match stage leaves cd[p] = distance to the most recent earlier occurrence of p's 3-byte prefix inside p's chunk, 0 where
 // there is none within window_size — for EVERY position p < end, whatever the parse will visit (DefaultLz77Encoder::flush
@@ -53,6 +53,11 @@ __device__ __forceinline__ uint32_t lds1(const uint32_t *w, uint32_t off) { retu
 // dictionary's tail T and its chain lie in front of position 0 in LDS — position -1 is T's last byte, through the unsigned
 // wrap the parse's dictionary instance uses — and a chain that reaches position 0 goes on into T.  Without the ChainDict
 // every `DICT ? :` below folds to what stood there before.
+//
+// TUNE (LFX_LZ77_LEVEL): the pack ends with a ChainTune behind the length array (chain_kernel<..., uint8_t *,
+// ChainTune> and chain_kernel<..., ChainDict, uint8_t *, ChainTune>).  Two rules, both functions of the position alone: the
+// walk ends behind the first candidate of min(lim, nice) bytes or more instead of lim, and a 3-byte match farther than too_far
+// is stored as "no candidate" (its length byte is the 0 it was).  Without the ChainTune both fold away.
 template <typename... Extra> constexpr bool chain_has_dict = false;
 template <typename... Rest> constexpr bool chain_has_dict<ChainDict, Rest...> = true;
 __device__ __forceinline__ uint8_t *len_of() { return nullptr; }
@@ -63,6 +68,13 @@ __device__ __forceinline__ ChainDict dict_of() { return ChainDict{nullptr, nullp
 __device__ __forceinline__ ChainDict dict_of(uint8_t *) { return ChainDict{nullptr, nullptr, nullptr, 0u}; }
 __device__ __forceinline__ ChainDict dict_of(const ChainDict &d) { return d; }
 __device__ __forceinline__ ChainDict dict_of(const ChainDict &d, uint8_t *) { return d; }
+__device__ __forceinline__ uint8_t *len_of(uint8_t *len, const ChainTune &) { return len; }
+__device__ __forceinline__ uint8_t *len_of(const ChainDict &, uint8_t *len, const ChainTune &) { return len; }
+__device__ __forceinline__ ChainDict dict_of(uint8_t *, const ChainTune &) { return ChainDict{nullptr, nullptr, nullptr, 0u}; }
+__device__ __forceinline__ ChainDict dict_of(const ChainDict &d, uint8_t *, const ChainTune &) { return d; }
+template <typename... Extra> __device__ __forceinline__ ChainTune tune_of(Extra...) { return ChainTune{0xFFFFFFFFu, 0xFFFFFFFFu}; }
+__device__ __forceinline__ ChainTune tune_of(uint8_t *, const ChainTune &t) { return t; }
+__device__ __forceinline__ ChainTune tune_of(const ChainDict &, uint8_t *, const ChainTune &t) { return t; }
 
 // 4 bytes from byte 4 * wi + ph (ph 0..3) of an array of ndw aligned dwords; what lies outside the array reads as 0
 __device__ __forceinline__ uint32_t dword_at(const uint32_t *__restrict__ w, int32_t wi, uint32_t ph, int32_t ndw) {
@@ -78,7 +90,8 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
                                                         Extra... extra) {
     constexpr bool DICT = chain_has_dict<Extra...>;
     constexpr bool LEN = sizeof...(Extra) != (DICT ? 1 : 0);
-    static_assert(sizeof...(Extra) <= (DICT ? 2 : 1), "a chain dictionary or none, then no length array or one");
+    constexpr bool TUNE = sizeof...(Extra) == (DICT ? 3 : 2);
+    static_assert(sizeof...(Extra) <= (DICT ? 3 : 2), "a chain dictionary or none, then no length array or one, then no tuning or one");
     static_assert(!DICT || WCAP == MAX_WINDOW, "the dictionary's tail takes the room of the window in front of position 0");
     constexpr uint32_t BW = chain_lds_bytes_dw(TILE, WCAP);
     constexpr uint32_t CW = chain_lds_cand_dw(TILE, WCAP);
@@ -100,6 +113,7 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
     // DICT: T's last n_t bytes in front of the chunk (lo == 0: p0 < window <= WCAP); a tile that is not listed for this
     // instance (never) has n_t == 0 and runs as the instance without a dictionary does
     const ChainDict dict = dict_of(extra...);
+    const ChainTune tune = tune_of(extra...);
     const ChainDictFill df = DICT && (ch.flags & CH_DICT) && lo == 0 ? chain_dict_fill(dict.usable, window, p0) : ChainDictFill{0u, 0u, 0u};
     // ---- stage the bytes and the candidates on their own dword grids: position q's byte sits at LDS byte q - lo + sh, its
     //      candidate at entry q - lo + csh.  (The dwords that hold the first and the last byte may reach up to three bytes
@@ -200,7 +214,7 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
             state = HOP;
         }
         // HOP: the next older occurrence, unless the walk is over
-        bool fin = best >= lim || left == 0;
+        bool fin = best >= (TUNE && tune.nice < lim ? tune.nice : lim) || left == 0;
         if (!fin) {
             const uint32_t dq = c16[c + coff];
             fin = dq == 0 || (!DICT && dq > c);
@@ -217,6 +231,7 @@ __global__ __launch_bounds__(THREADS) void chain_kernel(const uint8_t *__restric
             }
         }
         if (fin) {
+            if (TUNE && best == 3 && bestd > tune.too_far) bestd = 0;   // too far: no candidate (its length byte is 0 as it is)
             out[p] = (uint16_t)bestd;
             if (LEN) lout[p] = (uint8_t)(best - 3);               // (3 <= best <= 258: every walk that ends here compared once)
             p += THREADS;
@@ -276,14 +291,65 @@ __global__ __launch_bounds__(DEMOTE_THREADS) void demote_kernel(const ChunkDesc 
     }
 }
 
+// LFX_LZ77_LEVEL's demotion: demote_kernel with max_lazy.  A position whose length is Z or more keeps its
+// candidate whatever follows — in the bytes of len, l >= zb = Z - 3 — so cd2[p] = 0 when p + 1 < end, len[p + 1] > len[p] and
+// len[p] < zb.  (A position without a candidate shares the byte 0 with L = 3 and may be "demoted": its cd2 is 0 already.)  The
+// same cut of the item, the same accesses.  A kernel of its own, and a template, for one reason: LazyLz77Encoder's kernel above
+// and the chain kernel's instances of the kinds 2 and 3 keep the code object text they had, label for label — the compiler
+// emits a template's instance where it is first used (launch_demote, at the end of this file), behind all of them.
+__device__ __forceinline__ uint32_t demote_keep_level(uint32_t l, uint32_t nx, uint32_t k, uint32_t zb) {
+    const uint32_t lk = (l >> (8 * k)) & 0xFFu;
+    return ((nx >> (8 * k)) & 0xFFu) > lk && lk < zb ? 0u : 0xFFFFu;
+}
+template <uint32_t THREADS>
+__global__ __launch_bounds__(THREADS) void demote_level_kernel(const ChunkDesc *__restrict__ chunks, const ChainItem *__restrict__ items,
+                                                               uint32_t tile, const uint8_t *__restrict__ len, uint16_t *cd2, uint32_t zb) {
+    const ChainItem it = items[blockIdx.x];
+    const ChunkDesc ch = chunks[it.chunk];
+    const DemoteSpan s = demote_span(ch.in_off, ch.len, it.p0, tile);
+    const uint64_t g0 = s.g0, a = s.a, b = s.b, g1 = s.g1, gend = s.gend;
+    if (g0 >= g1) return;                                         // (never listed)
+    const uint32_t tid = threadIdx.x;
+    if (tid < 32) {
+        const uint64_t g = g0 + tid;
+        if (g < a && g + 1 < gend && len[g + 1] > len[g] && len[g] < zb) cd2[g] = 0;
+    } else if (tid < 48) {
+        const uint64_t g = b + (tid - 32);
+        if (g < g1 && g + 1 < gend && len[g + 1] > len[g] && len[g] < zb) cd2[g] = 0;
+    }
+    for (uint64_t g = a + 16 * (uint64_t)tid; g < b; g += 16 * THREADS) {
+        const uint4 l = *(const uint4 *)(len + g);
+        const uint32_t nb = g + 16 < gend ? len[g + 16] : 0u;    // (g + 16 == gend: position end - 1 stays, L(end) = 0)
+        uint4 *c = (uint4 *)(cd2 + g);
+        uint4 c0 = c[0], c1 = c[1];
+        const uint32_t lw[5] = {l.x, l.y, l.z, l.w, nb};
+        uint32_t keep[8];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint32_t nx = __builtin_amdgcn_alignbyte(lw[j + 1], lw[j], 1);
+            keep[2 * j] = demote_keep_level(lw[j], nx, 0, zb) | demote_keep_level(lw[j], nx, 1, zb) << 16;
+            keep[2 * j + 1] = demote_keep_level(lw[j], nx, 2, zb) | demote_keep_level(lw[j], nx, 3, zb) << 16;
+        }
+        c0.x &= keep[0]; c0.y &= keep[1]; c0.z &= keep[2]; c0.w &= keep[3];
+        c1.x &= keep[4]; c1.y &= keep[5]; c1.z &= keep[6]; c1.w &= keep[7];
+        c[0] = c0;
+        c[1] = c1;
+    }
+}
+
+int launch_chain_level(hipStream_t st, const uint8_t *in, const ChunkDesc *chunks, const ChainItem *items, uint32_t nitems, bool small,
+                       uint32_t window, uint32_t max_len, uint32_t depth, const uint16_t *cd, uint16_t *cd2, uint8_t *len, uint32_t n_plain,
+                       const ChainDict *dict, const ChainTune &tune);
+
 }  // namespace
 
 int launch_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, const ChainItem *items,
                  uint32_t nitems, bool small, uint32_t window, uint32_t max_len, uint32_t depth, const uint16_t *cd, uint16_t *cd2,
-                 uint8_t *len, uint32_t n_plain, const ChainDict *dict) {
+                 uint8_t *len, uint32_t n_plain, const ChainDict *dict, const ChainTune *tune) {
     (void)in_bytes;
     if (!nitems) return 0;
     if (!dict || n_plain > nitems) n_plain = nitems;
+    if (tune) return launch_chain_level(st, in, chunks, items, nitems, small, window, max_len, depth, cd, cd2, len, n_plain, dict, *tune);
     if (n_plain) {
         if (len) {
             if (small)
@@ -323,11 +389,39 @@ int launch_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Chu
 }
 
 int launch_demote(hipStream_t st, const ChunkDesc *chunks, const ChainItem *items, uint32_t nitems, bool small, const uint8_t *len,
-                  uint16_t *cd2) {
+                  uint16_t *cd2, uint32_t max_lazy) {
     if (!nitems) return 0;
-    hipLaunchKernelGGL(demote_kernel, dim3(nitems), dim3(DEMOTE_THREADS), 0, st, chunks, items, small ? CHAIN_TILE_SMALL : CHAIN_TILE,
-                       len, cd2);
+    if (max_lazy)                                                 // LFX_LZ77_LEVEL: a length of max_lazy or more is not deferred
+        hipLaunchKernelGGL(demote_level_kernel<DEMOTE_THREADS>, dim3(nitems), dim3(DEMOTE_THREADS), 0, st, chunks, items,
+                           small ? CHAIN_TILE_SMALL : CHAIN_TILE, len, cd2, max_lazy > 3 ? max_lazy - 3 : 0u);
+    else
+        hipLaunchKernelGGL(demote_kernel, dim3(nitems), dim3(DEMOTE_THREADS), 0, st, chunks, items, small ? CHAIN_TILE_SMALL : CHAIN_TILE,
+                           len, cd2);
     return (int)hipGetLastError();
 }
+
+namespace {
+int launch_chain_level(hipStream_t st, const uint8_t *in, const ChunkDesc *chunks, const ChainItem *items, uint32_t nitems, bool small,
+                       uint32_t window, uint32_t max_len, uint32_t depth, const uint16_t *cd, uint16_t *cd2, uint8_t *len, uint32_t n_plain,
+                       const ChainDict *dict, const ChainTune &tune) {
+    // LFX_LZ77_LEVEL: three tuned instances, each with the length array — the greedy levels leave it unread.
+    // One dictionary instance serves both work lists: a call of the small list has one item per chunk, at p0 = 0 and of at
+    // most CHAIN_TILE_SMALL positions, which the window tile covers as it is (p1 and hi are cut at the chunk's end).
+    if (!len) return (int)hipErrorInvalidValue;
+    if (n_plain) {
+        if (small)
+            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE_SMALL, 0, 256, uint8_t *, ChainTune>), dim3(n_plain), dim3(256), 0, st, in, chunks, items,
+                               window, max_len, depth, cd, cd2, len, tune);
+        else
+            hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024, uint8_t *, ChainTune>), dim3(n_plain), dim3(1024), 0, st, in, chunks,
+                               items, window, max_len, depth, cd, cd2, len, tune);
+        if (const int rc = (int)hipGetLastError()) return rc;
+    }
+    if (nitems - n_plain)
+        hipLaunchKernelGGL((chain_kernel<CHAIN_TILE, MAX_WINDOW, 1024, ChainDict, uint8_t *, ChainTune>), dim3(nitems - n_plain), dim3(1024), 0, st,
+                           in, chunks, items + n_plain, window, max_len, depth, cd, cd2, *dict, len, tune);
+    return (int)hipGetLastError();
+}
+}  // namespace
 
 }  // namespace lfx

@@ -66,15 +66,49 @@ inline void encode_opts_default(lfx_encode_opts *o) {
     o->max_length = MAX_LENGTH;
     o->os = 3;
 }
-// lz77_kind: the kind in bits 0..7; LFX_LZ77_CHAIN and LFX_LZ77_LAZY carry their depth in bits 8..15 (include/lfx.h).  The bits
-// above bit 7 are not read for the other kinds.
+// lz77_kind: the kind in bits 0..7; LFX_LZ77_CHAIN and LFX_LZ77_LAZY carry their depth in bits 8..15, LFX_LZ77_LEVEL its level
+// (include/lfx.h).  The bits above bit 7 are not read for the kinds 0 and 1.
 inline int lz77_kind_of(const lfx_encode_opts &o) { return (int)((uint32_t)o.lz77_kind & 0xFFu); }
-// the kinds that run the chain stage
+// the kinds that carry a chain depth of the caller's in bits 8..15
 inline bool lz77_chained(int kind) { return kind == LFX_LZ77_CHAIN || kind == LFX_LZ77_LAZY; }
+// the kinds that run the chain stage: those, and LFX_LZ77_LEVEL, whose depth comes from the level table below (§23)
+inline bool lz77_chain_stage(int kind) { return lz77_chained(kind) || kind == LFX_LZ77_LEVEL; }
+
+// LFX_LZ77_LEVEL: what a level 1..9 resolves into — zlib's configuration_table (deflate.c) without good_length,
+// which makes a position's length depend on its predecessor's and stays out.  max_lazy and too_far are read by the lazy levels
+// alone; for the greedy ones they hold "never" (no position is kept for its length, no 3-byte match is dropped).
+struct LevelTune {
+    uint32_t depth;               // K: chain depth (1..4096: a kernel argument, not the bit field of the kinds 2 and 3)
+    bool lazy;                    // the lazy walk (levels 4..9) or ChainLz77Encoder's greedy one (1..3)
+    uint32_t nice;                // N: a chain walk ends behind the first candidate of min(N, lim) bytes or more
+    uint32_t max_lazy;            // Z: a position with L >= Z is not deferred
+    uint32_t too_far;             // F: a 3-byte match farther than F is dropped
+};
+constexpr uint32_t LEVEL_NEVER = 0xFFFFFFFFu;
+// level 1..9 → its tuning; any other level: depth 0
+inline LevelTune level_tune(uint32_t level) {
+    static const LevelTune T[10] = {{0, false, 0, 0, 0},
+                                    {4, false, 8, LEVEL_NEVER, LEVEL_NEVER},
+                                    {8, false, 16, LEVEL_NEVER, LEVEL_NEVER},
+                                    {32, false, 32, LEVEL_NEVER, LEVEL_NEVER},
+                                    {16, true, 16, 4, 4096},
+                                    {32, true, 32, 16, 4096},
+                                    {128, true, 128, 16, 4096},
+                                    {256, true, 128, 32, 4096},
+                                    {1024, true, 258, 128, 4096},
+                                    {4096, true, 258, 258, 4096}};
+    return T[level <= 9 ? level : 0];
+}
 // E::compression_level() as lz77_level holds it (1 + LFX_LEVEL_*, 0: the kind's own): ChainLz77Encoder and LazyLz77Encoder are
-// Best unless the caller says otherwise; no_compression() resets the header's level like any other (zlib.rs:471-475, gzip.rs:703)
+// Best unless the caller says otherwise, LFX_LZ77_LEVEL is Fast for the levels 1..3, Balance for 4..6 and Best for 7..9 (a level
+// outside 1..9 is refused by encode_spec: Balance here); no_compression() resets the header's level like any other
+// (zlib.rs:471-475, gzip.rs:703)
 inline uint8_t lz77_level_of(const lfx_encode_opts &o) {
     if (o.lz77_level == 0 && lz77_chained(lz77_kind_of(o)) && !o.no_compression) return 1 + LFX_LEVEL_BEST;
+    if (o.lz77_level == 0 && lz77_kind_of(o) == LFX_LZ77_LEVEL && !o.no_compression) {
+        const uint32_t level = ((uint32_t)o.lz77_kind >> 8) & 0xFFu;
+        return (uint8_t)(1 + (level <= 3 ? LFX_LEVEL_FAST : level >= 7 ? LFX_LEVEL_BEST : LFX_LEVEL_BALANCE));
+    }
     return o.lz77_level;
 }
 
@@ -85,6 +119,8 @@ struct EncodeSpec {
     PlanOpts plan;                // what the planner reads
     uint32_t chain_depth = 0;     // ChainLz77Encoder's or LazyLz77Encoder's depth; 0: any other kind, no chain stage
     bool lazy = false;            // LazyLz77Encoder: the chain stage also demotes a position whose successor matches longer (§20)
+    bool tuned = false;           // LFX_LZ77_LEVEL (§23): chain_depth and lazy come from the level, and the chain stage runs its tuned instances with ...
+    LevelTune tune{0, false, 0, 0, 0};   // ... this (tune.depth == chain_depth, tune.lazy == lazy); all 0 for any other kind
     bool auto_blocks = false;     // LFX_HUFFMAN_AUTO (§22): every dynamic block's form chosen on the device; never under no_compression
 };
 // → LFX_OK, or LFX_E_ARG for options outside the domain.  *out is filled either way (lfx_encode_index_device asks
@@ -95,8 +131,10 @@ inline int encode_spec(int format, const lfx_encode_opts *o, EncodeSpec *out) {
     if (d.window_size > MAX_WINDOW) d.window_size = MAX_WINDOW;  // default.rs:228
     if (d.max_length > MAX_LENGTH) d.max_length = MAX_LENGTH;    // default.rs:240
     const int kind = lz77_kind_of(d);
-    out->chain_depth = lz77_chained(kind) ? ((uint32_t)d.lz77_kind >> 8) & 0xFFu : 0u;
-    out->lazy = kind == LFX_LZ77_LAZY;
+    out->tuned = kind == LFX_LZ77_LEVEL;
+    out->tune = level_tune(out->tuned ? ((uint32_t)d.lz77_kind >> 8) & 0xFFu : 0u);
+    out->chain_depth = lz77_chained(kind) ? ((uint32_t)d.lz77_kind >> 8) & 0xFFu : out->tune.depth;
+    out->lazy = kind == LFX_LZ77_LAZY || out->tune.lazy;
     out->auto_blocks = d.dynamic_huffman == LFX_HUFFMAN_AUTO && !d.no_compression;
     PlanOpts &p = out->plan;
     p.block_size = d.block_size;
@@ -108,7 +146,7 @@ inline int encode_spec(int format, const lfx_encode_opts *o, EncodeSpec *out) {
     p.zlib_sync = format == LFX_ZLIB && d.zlib_flush_mode == LFX_FLUSH_SYNC;
     if (d.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
     if (d.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
-    if (lz77_chained(kind) && (out->chain_depth == 0 || ((uint32_t)d.lz77_kind >> 16) != 0)) return LFX_E_ARG;
+    if (lz77_chain_stage(kind) && (out->chain_depth == 0 || ((uint32_t)d.lz77_kind >> 16) != 0)) return LFX_E_ARG;
     return LFX_OK;
 }
 
@@ -119,12 +157,14 @@ enum EncodeEntry { ENC_DEVICE, ENC_BATCH, ENC_DICT_DEVICE, ENC_DICT_BATCH, ENC_S
 enum DictKind { DICT_NONE, DICT_PLAIN, DICT_CHAIN };     // lfx_dict_new / lfx_dict_new_chain (§18, §21)
 // → LFX_OK (*why = nullptr), or LFX_E_UNSUPPORTED with *why.  Where a call has two reasons, the first row wins.
 inline int encode_served(EncodeEntry e, const EncodeSpec &sp, DictKind dict, const char **why) {
-    const bool chained = lz77_chained(sp.plan.lz77_kind);
+    const bool chained = lz77_chain_stage(sp.plan.lz77_kind), level = sp.plan.lz77_kind == LFX_LZ77_LEVEL;
     *why = e == ENC_SHARD && sp.o.no_compression ? "sharded encode of stored blocks is not supported (their size depends on the bit phase)"
+         : e == ENC_SHARD && level ? "lz77_kind: the N-GPU encode does not serve LFX_LZ77_LEVEL"
          : e == ENC_SHARD && chained ? (sp.lazy ? "lz77_kind: the N-GPU encode does not serve LFX_LZ77_LAZY" : "lz77_kind: the N-GPU encode does not serve LFX_LZ77_CHAIN")
          : e == ENC_SHARD && sp.auto_blocks ? "dynamic_huffman: the N-GPU encode does not serve LFX_HUFFMAN_AUTO (a stored block's size depends on the bit phase)"
          : e == ENC_INDEX && sp.auto_blocks ? "dynamic_huffman: lfx_encode_index_device does not serve LFX_HUFFMAN_AUTO (the candidates are laid out from the host plan's block types)"
          // ChainLz77Encoder and LazyLz77Encoder have no chain behind a plain dictionary's candidate (§19); a chain dictionary brings its own
+         : dict == DICT_PLAIN && level ? "lz77_kind: LFX_LZ77_LEVEL with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"
          : dict == DICT_PLAIN && chained ? (sp.lazy ? "lz77_kind: LFX_LZ77_LAZY with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"
                                                     : "lz77_kind: LFX_LZ77_CHAIN with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)")
          : nullptr;

@@ -65,6 +65,8 @@ struct EncCall {
     bool match_v1;                // the first-generation match kernel: it once saw a lane-order violation (or LFX_MATCH_V1 is set)
     uint32_t chain_depth;         // ChainLz77Encoder's or LazyLz77Encoder's depth; 0: any other kind — no chain stage, no second candidate buffer
     bool lazy;                    // LazyLz77Encoder: the chain stage keeps the lengths and demotes behind them (§20)
+    bool tuned;                   // LFX_LZ77_LEVEL (§23): the chain stage's tuned instances, with ...
+    LevelTune tune;               // ... the level's nice, max_lazy and too_far (chain_depth and lazy above are the level's too)
     bool auto_blocks;             // LFX_HUFFMAN_AUTO (§22): block_choose_kernel behind the Huffman kernel; any other call: no launch, no buffer
     EncodeGeom g;
     uint64_t nspans = 0;          // partial results of the checksum kernels
@@ -168,7 +170,7 @@ int reserve_scratch(Ctx *c, EncCall &k) {
     if ((rc = c->d_pwgs.reserve(sizeof(ParseWg) * std::max<size_t>(k.g.pwgs.size(), 1)))) return rc;
     if (!hc && (rc = c->d_cd.reserve(2 * n + 64))) return rc;                   // candidate distances, 16 bits per position
     if (!hc && k.chain_depth && (rc = c->d_cd2.reserve(2 * n + 64))) return rc;  // ... and the chain stage's, which the parse then reads
-    if (!hc && k.chain_depth && k.lazy && (rc = c->d_len.reserve(n + 64))) return rc;   // ... and LazyLz77Encoder's length byte per position
+    if (!hc && k.chain_depth && (k.lazy || k.tuned) && (rc = c->d_len.reserve(n + 64))) return rc;   // ... and LazyLz77Encoder's length byte per position (the tuned instances write it at every level)
     if (!hc && !match_v1 && (rc = c->d_glnk.reserve(264 * std::max<uint64_t>(lnk_units, 1)))) return rc;   // lfx_match7: link records (4 bytes) + ballot words (8 bytes per 64); lfx_match5: links (2 bytes)
     if (!hc && !match_v1 && (rc = c->d_ucount.reserve(4 * std::max<size_t>(nsegs, 1)))) return rc;   // lfx_match7: unresolved positions per segment
     if (!hc && match_v1 && (rc = c->d_md.reserve(4 * std::max<uint64_t>(n, 1)))) return rc;   // first-generation kernel: (length, distance) words
@@ -332,6 +334,10 @@ int stage_dict(Ctx *c, const EncCall &k) {
 // The tiles of the primed chunks within window_size of their start form a second run of the work list and go to the
 // dictionary instance, which follows the chain on into the dictionary's tail — through the tail's own chain, built here the
 // first time the dictionary serves a chained encode, and kept.
+//
+// LFX_LZ77_LEVEL (§23): the same two launches over the same work list, through the tuned instances — the walk stops at a nice
+// match and drops a far 3-byte one, the demotion spares a length of max_lazy or more.  The greedy levels (1..3) run the
+// length-writing instance too, leave the lengths unread and launch no demotion.
 int stage_chain(Ctx *c, EncCall &k) {
     hipStream_t st = c->stream;
     const lfx_dict *d = k.dict;
@@ -340,6 +346,7 @@ int stage_chain(Ctx *c, EncCall &k) {
     chain_items_dict(k.plan.chunks, small ? CHAIN_TILE_SMALL : CHAIN_TILE, k.po.window_size, d != nullptr, c->chain_items, n_plain);
     uint16_t *cd2 = (uint16_t *)c->d_cd2.p;
     ChainDict cdict{nullptr, nullptr, nullptr, 0u};
+    const ChainTune ctune{k.tune.nice, k.tune.too_far};
     if (n_plain < c->chain_items.size()) {
         if (!d->d_cdt) {
             if (hipMalloc((void **)&d->d_cdt, DICT_CHAIN_BYTES) != hipSuccess) { d->d_cdt = nullptr; c->set_error("out of device memory"); return LFX_E_OOM; }
@@ -356,15 +363,16 @@ int stage_chain(Ctx *c, EncCall &k) {
         if (int rc = c->d_chain_items.reserve(bytes)) return rc;
         HIP_TRY(hipMemcpyAsync(c->d_chain_items.p, c->chain_items.data(), bytes, hipMemcpyHostToDevice, st));
         LAUNCH_TRY(launch_chain(st, k.d_in, k.n, k.v.chunks, (const ChainItem *)c->d_chain_items.p, (uint32_t)c->chain_items.size(), small,
-                                k.po.window_size, k.po.max_length, k.chain_depth, k.v.cd, cd2, k.lazy ? (uint8_t *)c->d_len.p : nullptr,
-                                n_plain, cdict.win ? &cdict : nullptr));
+                                k.po.window_size, k.po.max_length, k.chain_depth, k.v.cd, cd2,
+                                k.lazy || k.tuned ? (uint8_t *)c->d_len.p : nullptr, n_plain, cdict.win ? &cdict : nullptr,
+                                k.tuned ? &ctune : nullptr));
     }
     k.v.cd = cd2;
     c->phase("lz77_chain_cand");
     if (k.lazy) {
         if (!c->chain_items.empty())
             LAUNCH_TRY(launch_demote(st, k.v.chunks, (const ChainItem *)c->d_chain_items.p, (uint32_t)c->chain_items.size(), small,
-                                     (const uint8_t *)c->d_len.p, cd2));
+                                     (const uint8_t *)c->d_len.p, cd2, k.tuned ? k.tune.max_lazy : 0u));
         c->phase("lz77_lazy_demote");
     }
     return LFX_OK;
@@ -446,7 +454,7 @@ int encode_prepare(Ctx *c, const Plan &plan, const EncodeSpec &sp, const uint8_t
     c->phase("start");
     EncCall k{plan, sp.plan, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
               hc ? 0u : sp.chain_depth,     // (a caller's own code words switch the chain stage off)
-              sp.lazy, sp.auto_blocks,
+              sp.lazy, sp.tuned, sp.tune, sp.auto_blocks,
               encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
     if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)

@@ -20,7 +20,7 @@ struct PlanOpts {
     uint64_t block_size = 1u << 20;
     bool dynamic_huffman = true;
     bool no_compression = false;
-    int lz77_kind = 0;  // 0 default, 1 NoCompressionLz77Encoder, 2 ChainLz77Encoder, 3 LazyLz77Encoder (the kind alone: the depth is no concern of the plan)
+    int lz77_kind = 0;  // 0 default, 1 NoCompressionLz77Encoder, 2 ChainLz77Encoder, 3 LazyLz77Encoder, 4 LFX_LZ77_LEVEL (the kind alone: depth and level are no concern of the plan)
     uint32_t window_size = MAX_WINDOW;
     uint32_t max_length = MAX_LENGTH;
     bool zlib_sync = false;  // zlib FlushMode::Sync (only meaningful for the zlib container)
@@ -157,7 +157,7 @@ class Planner {
   private:
     // DefaultLz77Encoder's buffering (default.rs:60-68): its own, ChainLz77Encoder's (kind 2) and
     // LazyLz77Encoder's (kind 3, §20)
-    bool buffers() const { return o_.lz77_kind == 0 || o_.lz77_kind == 2 || o_.lz77_kind == 3; }
+    bool buffers() const { return o_.lz77_kind == 0 || o_.lz77_kind == 2 || o_.lz77_kind == 3 || o_.lz77_kind == 4; }
     void emit_chunk(uint64_t off, uint64_t len, uint32_t flags) {
         ChunkDesc c{};
         c.in_off = off;

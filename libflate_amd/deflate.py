@@ -68,24 +68,30 @@ class Encoder(_EncoderBase):
         return cls(inner, options, context)
 
 
-def _with_lz77(options, lz77, cls):
-    """options with `lz77` (an Lz77Encode of this package, e.g. lz77.ChainLz77Encoder(8)) put in; None: options as they are"""
+def _with_lz77(options, lz77, cls, level=None):
+    """options with `lz77` (an Lz77Encode of this package, e.g. lz77.ChainLz77Encoder(8)) put in; None: options as they are.
+    level: shorthand for lz77=lz77.LevelLz77Encoder(level), exclusive with lz77"""
+    if level is not None:
+        if lz77 is not None:
+            raise ValueError("level= and lz77= exclude each other: level=n is lz77=LevelLz77Encoder(n)")
+        from .lz77 import LevelLz77Encoder
+        lz77 = LevelLz77Encoder(level)
     if lz77 is None:
         return options
     return (options if options is not None else cls()).with_lz77(lz77)
 
 
-def _compress(fmt, data, zdict, options, context, lz77=None):
+def _compress(fmt, data, zdict, options, context, lz77=None, level=None):
     from .context import Dictionary, default_context
     ctx = context if context is not None else default_context()
-    options = _with_lz77(options, lz77, EncodeOptions)
+    options = _with_lz77(options, lz77, EncodeOptions, level)
     opts = options._to_c() if options is not None else None
     if zdict is None:
         return ctx.encode_host(fmt, data, opts)
     own = not hasattr(zdict, "handle")
     # (bytes: the dictionary is made here, with a chain of its own when the parse is a chained one, DESIGN.md §21; a caller's
     # Dictionary is taken as it was made)
-    chained = opts is not None and (opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY)
+    chained = opts is not None and (opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL)
     d = Dictionary(zdict, ctx, chain=chained) if own else zdict
     try:
         return ctx.encode_dict_host(fmt, d, data, opts)
@@ -94,12 +100,13 @@ def _compress(fmt, data, zdict, options, context, lz77=None):
             d.close()
 
 
-def compress(data, zdict=None, options=None, context=None, lz77=None):
+def compress(data, zdict=None, options=None, context=None, lz77=None, level=None):
     """`data` as one raw DEFLATE stream, encoded in one call (one write_all + finish).  zdict: a preset dictionary, bytes or a
     libflate_amd.Dictionary — the stream then starts with the dictionary as history, what
     zlib.decompressobj(wbits=-15, zdict=...) reads (lfx_encode_dict_host).  lz77: an Lz77Encode of this package
-    for the options, e.g. lz77.ChainLz77Encoder(8)."""
-    return _compress(_ffi.DEFLATE, data, zdict, options, context, lz77)
+    for the options, e.g. lz77.ChainLz77Encoder(8).  level: 1..9, shorthand for lz77=lz77.LevelLz77Encoder(level)
+    (DESIGN.md §23), exclusive with lz77."""
+    return _compress(_ffi.DEFLATE, data, zdict, options, context, lz77, level)
 
 
 class Decoder(_DecoderBase):

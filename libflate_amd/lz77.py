@@ -147,6 +147,29 @@ class LazyLz77Encoder(ChainLz77Encoder):
         return dict(super()._opts(), lz77_kind=_ffi.LZ77_LAZY | (self._depth if 0 <= self._depth <= 255 else 256) << 8)
 
 
+class LevelLz77Encoder:
+    """This library's own Lz77Encode (LFX_LZ77_LEVEL): the chained parse tuned by one number, `level` 1..9, the
+    way zlib's deflate is — each level is a chain depth, a "nice" length at which a chain walk stops, and from level 4 on the
+    lazy walk with zlib's max_lazy and TOO_FAR rules (the table: include/lfx.h).  Not bit-exact with zlib: good_length is not
+    modelled.  Accepted wherever LazyLz77Encoder is; like it, it has no encode / flush of its own."""
+
+    def __init__(self, level, window_size=MAX_WINDOW_SIZE, max_length=MAX_LENGTH):
+        self._level = int(level)
+        self._window = min(window_size, MAX_WINDOW_SIZE)
+        self._max_length = min(max_length, MAX_LENGTH)
+
+    def compression_level(self):
+        return CompressionLevel.FAST if self._level <= 3 else CompressionLevel.BEST if self._level >= 7 else CompressionLevel.BALANCE
+
+    def window_size(self):
+        return self._window
+
+    def _opts(self):
+        # (a level outside 1..9 reaches encode_spec as one that it refuses: LFX_E_ARG, not a silently different level)
+        return {"lz77_kind": _ffi.LZ77_LEVEL | (self._level if 0 <= self._level <= 255 else 255) << 8,
+                "window_size": self._window, "max_length": self._max_length}
+
+
 class NoCompressionLz77Encoder:
     """lib.rs:111-145: every byte a literal (still Huffman coded by the block encoder)."""
 

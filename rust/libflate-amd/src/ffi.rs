@@ -32,6 +32,9 @@ pub const fn lfx_lz77_chain_depth(depth: u8) -> i32 { LFX_LZ77_CHAIN | (depth as
 /// LazyLz77Encoder (include/lfx.h): ChainLz77Encoder with lazy matching; the depth (1..255) in bits 8..15 as well
 pub const LFX_LZ77_LAZY: i32 = 3;
 pub const fn lfx_lz77_lazy_depth(depth: u8) -> i32 { LFX_LZ77_LAZY | (depth as i32) << 8 }
+/// `LevelLz77Encoder` (include/lfx.h): bits 8..15 hold the level, 1..=9
+pub const LFX_LZ77_LEVEL: i32 = 4;
+pub const fn lfx_lz77_level_n(level: u8) -> i32 { LFX_LZ77_LEVEL | (level as i32) << 8 }
 /// lfx_encode_opts::dynamic_huffman (include/lfx.h): 0 fixed codes, 1 dynamic codes, 2 the smallest of the dynamic, the fixed and
 /// the stored form per block (opt-in, not a reference option)
 pub const LFX_HUFFMAN_FIXED: i32 = 0;
