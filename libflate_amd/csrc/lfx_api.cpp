@@ -113,6 +113,7 @@ void Diag::read() {
     if (const char *eb = getenv("LFX_ENC_BATCH_MB")) enc_batch_mb = atoi(eb);
     two_pass = on("LFX_TWO_PASS");
     hist_separate = on("LFX_HIST_SEPARATE");
+    if (const char *pc = getenv("LFX_PACK_BY_CHUNK")) pack_by_chunk = atoi(pc) ? 1 : 0;
     find2_exp = getenv("LFX_FIND2_EXP") ? atoi(getenv("LFX_FIND2_EXP")) : 0;
     no_pin_slots = on("LFX_NO_PIN_SLOTS");
     no_small_scan = on("LFX_NO_SMALL_SCAN");

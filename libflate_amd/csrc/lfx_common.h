@@ -57,6 +57,12 @@ struct BlockCodes {
 };
 
 constexpr uint32_t PACK_TILE = 2048;  // codes per pack tile
+// Pack by chunk (pack_chunk_kernel): one workgroup walks a chunk's tiles in order, so a chunk of more tiles than
+// this stays on the tile-parallel kernels.  The reference's chunks (window_size * 8 = 256 KiB) have at most 129 tiles; a chunk
+// that is a whole large input (schedule S1: 131073 tiles at 256 MiB) would be one workgroup's serial walk.  1024 tiles = 2 Mi
+// code words, about twenty times the walk of a reference chunk.
+constexpr uint32_t PACK_CHUNK_MAX_TILES = 1024;
+constexpr uint32_t SYM_ROW = 320;     // one row of symbol counters: [0,288) literal/length, [288,320) distance
 // Speculative parse segments: one wavefront per segment, 64 lanes ("groups") of PARSE_GROUP positions each; a group's
 // visited mask is one 64-bit word of vis[].  52 positions = 13 dwords per lane: an odd dword stride, so that 32 lanes
 // reading at the same offset inside their groups hit 32 different LDS banks (lfx_parse2.hip).

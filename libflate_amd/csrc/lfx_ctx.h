@@ -41,6 +41,7 @@ struct Diag {
     bool no_pin_slots = false;   // LFX_NO_PIN_SLOTS: the decode's small transfers as plain pageable copies (the path of a full arena)
     int find2_exp = 0;           // LFX_FIND2_EXP=1..4: a cut-down finder stage 2 runs in front of the real one (phase "find2x"): timing only
     bool hist_separate = false;  // LFX_HIST_SEPARATE: the blocks' symbol counts by histogram_kernel (round 5) instead of inside parse_emit
+    int pack_by_chunk = -1;      // LFX_PACK_BY_CHUNK: 0 the tile-parallel pack kernels always, 1 pack_chunk_kernel wherever it is legal (unset: by the geometry)
     bool store_tight = false;    // LFX_STORE_TIGHT: the storing scan's regions sized for 16 bits a code (tests: lanes overflow, blocks fall back)
     int enc_batch_mb = 0;        // LFX_ENC_BATCH_MB: the stream encoder encodes closed blocks once so many MiB wait (0: the default, 8)
     void read();
@@ -106,6 +107,9 @@ struct Ctx {
     // test hook lfx_debug_block_choices alone, no encode path looks at either.
     DevBuf d_choice;
     uint32_t n_choices = 0;
+    // an encode that packs by chunk: 320 symbol counters per chunk, and every chunk's packed size and first bit
+    // (16 bytes).  Sized only by calls of that kind.
+    DevBuf d_hist_chunk, d_chunk_bits;
     std::vector<ChainItem> chain_items;
     // decode scratch
     // host shadows of the plan tables last uploaded (chunks, blocks, segments, parse workgroups) and the device buffers they
@@ -128,7 +132,7 @@ struct Ctx {
                 &d_tile_bits, &d_tile_start, &d_ck, &d_res, &d_small, &d_hdr, &d_io_in, &d_io_out, &d_vis, &d_segtmp, &d_stage, &d_chunkmap, &d_glnk, &d_ucount,
                 &d_dec_streams, &d_dec_state, &d_dec_tmp, &d_dec_cand, &d_dec_blocks, &d_dec_tabs, &d_dec_sym, &d_dec_win, &d_dec_maps,
                 &d_dec_temp, &d_dec_lanesx, &d_idx_tasks, &d_idx_probe, &d_idx_stage, &d_idx_enc,
-                &d_bgzf_meta, &d_bgzf_tasks, &d_bgzf_scratch, &d_bgzf_pack, &d_dict_items, &d_cd2, &d_chain_items, &d_len, &d_choice};
+                &d_bgzf_meta, &d_bgzf_tasks, &d_bgzf_scratch, &d_bgzf_pack, &d_dict_items, &d_cd2, &d_chain_items, &d_len, &d_choice, &d_hist_chunk, &d_chunk_bits};
     }
     void *h_res = nullptr;  // pinned, 4 KiB (+ the arena below)
     // Small transfers of the decode paths (job lists up, scan results and counters down) go through page-locked memory: a
@@ -173,6 +177,7 @@ struct Ctx {
     uint64_t cur_ntiles = 0, cur_n = 0;
     const uint32_t *cur_tile_map = nullptr;   // tile → chunk table of the prepared encode (lives in d_chunkmap)
     const uint8_t *cur_in = nullptr;
+    bool cur_pack_by_chunk = false;           // the prepared encode counted its symbols per chunk: pack_blocks launches pack_chunk_kernel
     bool force_match_v1 = false;   // sticky: the second-generation match kernel reported a lane-order violation
     uint64_t match_fallbacks = 0;  // encode passes this context ran on the fallback kernel because of it (lfx_ctx_match_fallbacks)
     HostIo hostio;                 // copy streams and page-locked slabs for callers' pageable buffers (lfx_hostio.h), made on first use

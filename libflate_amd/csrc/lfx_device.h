@@ -66,7 +66,8 @@ int launch_parse_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, con
                                          (launch_histogram is then not needed); nullptr: not counted */,
                        uint32_t emit_per /* with hist: segments per emit workgroup ... */,
                        uint32_t emit_parts /* ... and workgroups for the chunk of most segments (grid = nchunks x emit_parts) */,
-                       const uint8_t *dict_win, bool fixseg_only = false /* diagnostics (LFX_DUMP_SEG): stop behind fixseg */);
+                       const uint8_t *dict_win, bool fixseg_only = false /* diagnostics (LFX_DUMP_SEG): stop behind fixseg */,
+                       bool hist_by_chunk = false /* hist holds 320 zeroed counters per CHUNK (pack by chunk) */);
 struct ZeroSpan { uint32_t *p; uint32_t n; };      // n words at p to be cleared (by the kernel that runs first anyway)
 int launch_chunk_maps(hipStream_t st, const ChunkDesc *chunks, uint32_t nchunks, uint64_t ntiles, uint32_t nsegs,
                       uint32_t *tile_map, uint32_t *seg_map, ZeroSpan z0 = ZeroSpan{nullptr, 0}, ZeroSpan z1 = ZeroSpan{nullptr, 0},
@@ -111,6 +112,15 @@ int launch_pack(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Chun
                 const uint32_t *codes, const uint32_t *ncodes, const BlockCodes *bc,
                 const uint64_t *block_start, uint32_t *tile_bits, uint64_t *tile_start,
                 const EncodeResult *res, uint64_t out_base_bit, uint32_t *out, const uint32_t *tile_map);
+// pack by chunk.  hist_chunk: 320 counters per chunk, as launch_parse_chain(hist_by_chunk) left them; chunk_bits:
+// 2 * nchunks words — every chunk's packed size, then its first bit behind its block's header.  launch_pack_chunks takes the
+// place of launch_pack; check: a chunk whose walk does not end at its counted size raises res->status (2).
+int launch_huffman_chunks(hipStream_t st, const BlockDesc *blocks, uint32_t nblocks, uint32_t nchunks, const uint32_t *hist_chunk,
+                          BlockCodes *bc, uint64_t *chunk_bits, uint64_t *dbg = nullptr);
+int launch_pack_chunks(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, uint32_t nchunks,
+                       const BlockDesc *blocks, uint32_t nblocks, const uint32_t *codes, const uint32_t *ncodes, const BlockCodes *bc,
+                       const uint64_t *block_start, const uint64_t *chunk_bits, bool check, EncodeResult *res, uint64_t out_base_bit,
+                       uint32_t *out, uint32_t n_cu);
 // span of the checksum kernels = the bytes one wavefront folds serially: 64 KiB; 8 KiB up to 64 MiB (a 1 MiB buffer is
 // sixteen 64 KiB spans — sixteen wavefronts on the whole GPU, each walking sixteen dependent pieces: 0.12 ms; 16 MiB are 256)
 inline uint32_t ck_span(uint64_t n) { return n <= (64ull << 20) ? 8192u : 65536u; }

@@ -69,6 +69,7 @@ struct EncCall {
     LevelTune tune;               // ... the level's nice, max_lazy and too_far (chain_depth and lazy above are the level's too)
     bool auto_blocks;             // LFX_HUFFMAN_AUTO (§22): block_choose_kernel behind the Huffman kernel; any other call: no launch, no buffer
     EncodeGeom g;
+    bool pack_by_chunk = false;   // the geometry's flag, and nothing behind the Huffman stage rewrites the blocks' codes (LFX_HUFFMAN_AUTO) or reads tile starts (the encode index)
     uint64_t nspans = 0;          // partial results of the checksum kernels
     bool forked = false;          // the first half of the checksum's sweep is on the side stream already
     EncView v{};
@@ -113,7 +114,7 @@ int parse_chain(Ctx *c, const EncCall &k, bool counted, bool fixseg_only = false
     const EncView &v = k.v;
     LAUNCH_TRY(launch_parse_chain(c->stream, k.d_in, k.n, v.chunks, c->cur_nchunks, k.plan.n_segs, v.cd, k.po.max_length, v.vis, v.segtmp,
                                   v.codes, v.ncodes, v.stage, v.seg_map, counted && k.g.fused_hist ? v.hist : nullptr, k.g.emit_per,
-                                  k.g.emit_parts, k.dict ? k.dict->d_win : nullptr, fixseg_only));
+                                  k.g.emit_parts, k.dict ? k.dict->d_win : nullptr, fixseg_only, k.pack_by_chunk));
     return LFX_OK;
 }
 // LFX_DUMP_SEG: the parse state of one segment behind the walk, behind fixseg and at the end
@@ -181,6 +182,8 @@ int reserve_scratch(Ctx *c, EncCall &k) {
     if (!hc && (rc = c->d_stage.reserve(4ull * (n + 64)))) return rc;   // code words staged by the speculative parse walk
     if ((rc = c->d_chunkmap.reserve(4ull * (plan.n_tiles + plan.n_segs + 2)))) return rc;   // tile → chunk, segment → chunk
     if ((rc = c->d_hist.reserve(4ull * 320 * std::max<size_t>(nblocks, 1)))) return rc;
+    if (k.pack_by_chunk && (rc = c->d_hist_chunk.reserve(4ull * SYM_ROW * nchunks))) return rc;   // pack by chunk: the symbol counts per chunk ...
+    if (k.pack_by_chunk && (rc = c->d_chunk_bits.reserve(16ull * nchunks))) return rc;            // ... every chunk's packed size and first bit
     if ((rc = c->d_bc.reserve(sizeof(BlockCodes) * std::max<size_t>(nblocks, 1)))) return rc;
     if ((rc = c->d_block_start.reserve(8 * std::max<size_t>(nblocks, 1)))) return rc;
     if (k.auto_blocks && (rc = c->d_choice.reserve(std::max<size_t>(nblocks, 1)))) return rc;   // LFX_HUFFMAN_AUTO: the chosen type per block
@@ -194,7 +197,8 @@ int reserve_scratch(Ctx *c, EncCall &k) {
     v.chunks = (const ChunkDesc *)c->d_chunks.p; v.blocks = (const BlockDesc *)c->d_blocks.p;
     v.segs = (const SegDesc *)c->d_segs.p; v.pwgs = (const ParseWg *)c->d_pwgs.p;
     v.cd = (uint16_t *)c->d_cd.p; v.codes = (uint32_t *)c->d_codes.p; v.ncodes = (uint32_t *)c->d_ncodes.p;
-    v.stage = (uint32_t *)c->d_stage.p; v.segtmp = (uint32_t *)c->d_segtmp.p; v.hist = (uint32_t *)c->d_hist.p;
+    v.stage = (uint32_t *)c->d_stage.p; v.segtmp = (uint32_t *)c->d_segtmp.p;
+    v.hist = (uint32_t *)(k.pack_by_chunk ? c->d_hist_chunk.p : c->d_hist.p);
     v.ck = (uint32_t *)c->d_ck.p; v.vis = (uint64_t *)c->d_vis.p; v.res = (EncodeResult *)c->d_res.p;
     v.tile_map = (uint32_t *)c->d_chunkmap.p; v.seg_map = v.tile_map + plan.n_tiles;
     v.d_match_flags = (uint32_t *)((uint8_t *)c->d_res.p + offsetof(EncodeResult, match_flags));
@@ -225,7 +229,7 @@ int upload_tables(Ctx *c, const EncCall &k) {
 // match stage's per-segment counts (three fill operations in front of the match kernel before: 22 us of a 4.6 ms step)
 int chunk_maps(Ctx *c, const EncCall &k) {
     const bool ucount_here = !k.hc && !k.match_v1 && !c->diag.match_v5;
-    const ZeroSpan z_hist{k.v.hist, (uint32_t)(320 * std::max<size_t>(c->cur_nblocks, 1))}, z_res{(uint32_t *)c->d_res.p, 64u},
+    const ZeroSpan z_hist{k.v.hist, (uint32_t)(320 * (k.pack_by_chunk ? (size_t)c->cur_nchunks : std::max<size_t>(c->cur_nblocks, 1)))}, z_res{(uint32_t *)c->d_res.p, 64u},
         z_ucount{ucount_here ? (uint32_t *)c->d_ucount.p : nullptr, ucount_here ? (uint32_t)std::max<size_t>(k.g.segs.size(), 1) : 0u};
     c->cur_tile_map = k.v.tile_map;
     if (int e_ = launch_chunk_maps(c->stream, k.v.chunks, c->cur_nchunks, k.plan.n_tiles, k.plan.n_segs, k.v.tile_map, k.v.seg_map, z_hist,
@@ -428,7 +432,12 @@ int stage_huffman(Ctx *c, const EncCall &k) {
     hipStream_t st = c->stream;
     if (!k.g.fused_hist) LAUNCH_TRY(launch_histogram(st, v.chunks, c->cur_nchunks, k.g.split, v.codes, v.ncodes, v.hist));
     c->phase("histogram");
-    LAUNCH_TRY(launch_huffman(st, v.blocks, c->cur_nblocks, v.hist, (BlockCodes *)c->d_bc.p, v.mdbg ? v.mdbg + 512 : nullptr));
+    // (pack by chunk: the counts are a row per chunk — the kernel sums a block's rows first and sizes every chunk behind its codes)
+    if (k.pack_by_chunk)
+        LAUNCH_TRY(launch_huffman_chunks(st, v.blocks, c->cur_nblocks, c->cur_nchunks, v.hist, (BlockCodes *)c->d_bc.p,
+                                         (uint64_t *)c->d_chunk_bits.p, v.mdbg ? v.mdbg + 512 : nullptr));
+    else
+        LAUNCH_TRY(launch_huffman(st, v.blocks, c->cur_nblocks, v.hist, (BlockCodes *)c->d_bc.p, v.mdbg ? v.mdbg + 512 : nullptr));
     c->phase("huffman");
     if (v.mdbg) dbg_huffman(k);
     if (k.auto_blocks) {
@@ -455,8 +464,10 @@ int encode_prepare(Ctx *c, const Plan &plan, const EncodeSpec &sp, const uint8_t
     EncCall k{plan, sp.plan, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
               hc ? 0u : sp.chain_depth,     // (a caller's own code words switch the chain stage off)
               sp.lazy, sp.tuned, sp.tune, sp.auto_blocks,
-              encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate)};
+              encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate, c->diag.pack_by_chunk)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
+    k.pack_by_chunk = k.g.pack_by_chunk && !k.auto_blocks && !c->idx_enc;
+    c->cur_pack_by_chunk = k.pack_by_chunk;
     if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)
     c->cur_nchunks = (uint32_t)plan.chunks.size();
     c->cur_nblocks = (uint32_t)plan.blocks.size();
@@ -485,7 +496,18 @@ int encode_prepare(Ctx *c, const Plan &plan, const EncodeSpec &sp, const uint8_t
     return LFX_OK;
 }
 
+// LFX_DEBUG, pack by chunk: pack_chunk_kernel raised bit 1 of the result record's status — every tail that packs reports it
+static const char *const PACK_MISMATCH = "pack by chunk: a chunk's packed size differs from its counted size";
+
 int pack_blocks(Ctx *c, void *d_out) {
+    if (c->cur_pack_by_chunk) {
+        LAUNCH_TRY(launch_pack_chunks(c->stream, c->cur_in, c->cur_n, (const ChunkDesc *)c->d_chunks.p, c->cur_nchunks,
+                                      (const BlockDesc *)c->d_blocks.p, c->cur_nblocks, (const uint32_t *)c->d_codes.p,
+                                      (const uint32_t *)c->d_ncodes.p, (const BlockCodes *)c->d_bc.p, (const uint64_t *)c->d_block_start.p,
+                                      (const uint64_t *)c->d_chunk_bits.p, c->diag.debug, (EncodeResult *)c->d_res.p, 0, (uint32_t *)d_out,
+                                      (uint32_t)std::max(c->n_cu, 1)));
+        return LFX_OK;
+    }
     LAUNCH_TRY(launch_pack(c->stream, c->cur_in, c->cur_n, (const ChunkDesc *)c->d_chunks.p, c->cur_nchunks,
                            (const BlockDesc *)c->d_blocks.p, c->cur_nblocks, c->cur_ntiles,
                            (const uint32_t *)c->d_codes.p, (const uint32_t *)c->d_ncodes.p,
@@ -530,6 +552,7 @@ int encode_emit(Ctx *c, int format, bool with_trailer, uint32_t trailer_check, b
     if (async_slot) return LFX_OK;
     HIP_TRY(hipStreamSynchronize(st));
     *host_res = *(EncodeResult *)c->h_res;
+    if (host_res->status & 2u) { c->set_error(PACK_MISMATCH); return LFX_E_DEVICE; }
     if (host_res->status != 0) { c->set_error("output capacity too small"); return LFX_E_NOSPACE; }
     return LFX_OK;
 }
@@ -575,6 +598,7 @@ int encode_batch(Ctx *c, const Plan &plan, const EncodeSpec &sp, const BatchCall
         c->phase("frame");
         HIP_TRY(hipStreamSynchronize(st));
         res = *(EncodeResult *)c->h_res;
+        if (res.status & 2u) { c->set_error(PACK_MISMATCH); return LFX_E_DEVICE; }
         return LFX_OK;
     });
 }
@@ -615,6 +639,7 @@ int encode_members(Ctx *c, const Plan &plan, const EncodeSpec &sp, const Members
         c->phase("frame");
         HIP_TRY(hipStreamSynchronize(st));
         res = *(EncodeResult *)c->h_res;
+        if (res.status & 2u) { c->set_error(PACK_MISMATCH); return LFX_E_DEVICE; }
         return LFX_OK;
     });
     c->prezero.settle();     // (failed before the stream waited for the fill: it is on the caller's buffer)

@@ -458,6 +458,37 @@ __global__ __launch_bounds__(HUFF_THREADS) void huffman_kernel(const BlockDesc *
     if (dbg && b == 0 && threadIdx.x < 24) dbg[threadIdx.x] = S.stamp[threadIdx.x];   // (LFX_DEBUG)
 }
 
+// Pack by chunk: the symbol counts arrive one row per CHUNK (hist_chunk, written by the parse).  The block's histogram is the
+// sum of its chunks' rows — bd.n_chunks of them, four at the reference's sizes — taken into LDS in front of the same code
+// construction; behind it every chunk's packed size follows from its own row and the widths just built, and their running sum
+// is every chunk's first bit behind the block's header: pack_chunk_kernel needs no tile sizes and no scan over them.
+// chunk_bits: [0, nchunks) the sizes, [nchunks, 2 nchunks) the starts.
+__global__ __launch_bounds__(HUFF_THREADS) void huffman_chunk_kernel(const BlockDesc *__restrict__ blocks, uint32_t nchunks,
+                                                                     const uint32_t *__restrict__ hist_chunk,
+                                                                     BlockCodes *__restrict__ bc, uint64_t *__restrict__ chunk_bits,
+                                                                     uint64_t *__restrict__ dbg) {
+    __shared__ HuffScratch S;
+    __shared__ uint32_t s_hist[SYM_ROW];
+    const uint32_t b = blockIdx.x;
+    const BlockDesc bd = blocks[b];
+    if (bd.type == BT_RAW) return;
+    const uint32_t *rows = hist_chunk + (uint64_t)bd.first_chunk * SYM_ROW;
+    sym_rows_sum(rows, bd.n_chunks, s_hist, (int)threadIdx.x, HUFF_THREADS);
+    __syncthreads();
+    huff_block_build(s_hist, bd.type, &bc[b], S, (int)threadIdx.x, HUFF_THREADS);
+    if (dbg && b == 0 && threadIdx.x < 24) dbg[threadIdx.x] = S.stamp[threadIdx.x];   // (LFX_DEBUG)
+    // (huff_block_build ends with a barrier: this workgroup's writes of bc[b] are visible to all of its lanes)
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t *bits = chunk_bits + bd.first_chunk, *start = chunk_bits + nchunks + bd.first_chunk;
+    for (uint32_t c = wave; c < bd.n_chunks; c += HUFF_THREADS / 64) {
+        uint64_t part = chunk_bits_part(rows + (uint64_t)c * SYM_ROW, &bc[b], (int)lane, 64);
+        for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o);
+        if (lane == 0) bits[c] = part;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) chunk_start_prefix(bits, bd.n_chunks, start);
+}
+
 // ------------------------------------------------------------------------------------------------
 // LFX_HUFFMAN_AUTO: behind huffman_kernel, one wavefront per block picks the smallest of the block's dynamic
 // form (D = bc[b].body_bits), its fixed form (F = 3 + Σ count · (fixed width + extra bits) over the block's own counts) and —
@@ -751,6 +782,62 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(const ChunkDesc *__rest
 
 constexpr int STAGE_WORDS64 = (PACK_TILE * 48) / 64 + 4;  // worst case + phase + spill
 
+// One tile of pack_kernel / pack_chunk_kernel: the lane's PACK_PER_THREAD code words cv (codes first .. first + 7 of the chunk,
+// those at hi or behind do not count) are sized, a workgroup scan gives each its place, they are ORed into the LDS staging
+// buffer and that is flushed to `out` from bit `start` on.  Called by all lanes behind a barrier (the tables lit / dst are
+// loaded, the staging buffer is free); returns the tile's bits.
+__device__ __forceinline__ uint32_t pack_tile(const uint32_t (&cv)[PACK_PER_THREAD], uint32_t first, uint32_t hi, const uint32_t *lit,
+                                              const uint32_t *dst, uint32_t *wsum, unsigned long long *stage, uint64_t start,
+                                              uint32_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t i = threadIdx.x; i < STAGE_WORDS64; i += PACK_THREADS) stage[i] = 0;
+    __syncthreads();
+    uint64_t cb[PACK_PER_THREAD];
+    uint32_t cn[PACK_PER_THREAD];
+    uint32_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < PACK_PER_THREAD; ++k) {
+        const uint32_t i = first + k;
+        const uint32_t nb = code_bits(cv[k], lit, dst, cb[k]);
+        cn[k] = i < hi ? nb : 0u;
+        cb[k] = i < hi ? cb[k] : 0ull;
+        mine += cn[k];
+    }
+    // exclusive scan of `mine` over the workgroup
+    uint32_t x = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o);
+        if ((int)lane >= o) x += y;
+    }
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    uint32_t pre = 0;
+    for (uint32_t w = 0; w < wave; ++w) pre += wsum[w];
+    const uint32_t total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const uint32_t phase = (uint32_t)start & 31;
+    uint32_t bit = phase + pre + x - mine;
+#pragma unroll
+    for (int k = 0; k < PACK_PER_THREAD; ++k) {
+        if (cn[k]) {
+            const uint32_t w = bit >> 6, sh = bit & 63;
+            atomicOr(&stage[w], cb[k] << sh);
+            if (sh + cn[k] > 64) atomicOr(&stage[w + 1], cb[k] >> (64 - sh));
+            bit += cn[k];
+        }
+    }
+    __syncthreads();
+    // staging → output words; the first and last word may be shared with neighbours
+    const uint32_t nwords = (phase + total + 31) >> 5;
+    const uint32_t *s32 = (const uint32_t *)stage;
+    uint32_t *o = out + (start >> 5);
+    for (uint32_t i = threadIdx.x; i < nwords; i += PACK_THREADS) {
+        const uint32_t v = s32[i];
+        if (i == 0 || i == nwords - 1) { if (v) atomicOr(&o[i], v); }
+        else o[i] = v;
+    }
+    return total;
+}
+
 __global__ __launch_bounds__(PACK_THREADS) void pack_kernel(
     const ChunkDesc *__restrict__ chunks, uint32_t nchunks, const BlockDesc *__restrict__ blocks,
     const uint32_t *__restrict__ codes, const uint32_t *__restrict__ ncodes,
@@ -775,7 +862,6 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_kernel(
     bool raw = false;
     uint32_t cv[PACK_PER_THREAD], cvn[PACK_PER_THREAD];
     bool have_next = false;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (uint32_t q = 0; q < PACK_TPW; ++q) {
         const uint64_t gt = g0 + q;
@@ -813,52 +899,65 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_kernel(
             for (uint32_t i = threadIdx.x; i < 288; i += PACK_THREADS) lit[i] = B->lit[i];
             if (threadIdx.x < 32) dst[threadIdx.x] = B->dist[threadIdx.x];
         }
-        for (uint32_t i = threadIdx.x; i < STAGE_WORDS64; i += PACK_THREADS) stage[i] = 0;
-        __syncthreads();
-        uint64_t cb[PACK_PER_THREAD];
-        uint32_t cn[PACK_PER_THREAD];
-        uint32_t mine = 0;
+        pack_tile(cv, first, hi, lit, dst, wsum, stage, ts[q] - out_base_bit, out);
+    }
+}
+
+// Pack by chunk: a chunk's first bit is known before packing — huffman_chunk_kernel derived it from the chunk's
+// symbol counts — so ONE workgroup walks the chunk's tiles in order and carries the bit offset in a register: the code words
+// are sized and packed while they sit in registers, read once, and only the div_up(n, PACK_TILE) tiles that hold codes are
+// visited.  A workgroup takes the chunks blockIdx.x, blockIdx.x + gridDim.x, … (launch_pack_chunks: one chunk each up to
+// eight workgroups per CU, several beyond that); no workgroup waits for another.  A tile's codes
+// are requested while the tile before is packed.  chunk_start: every chunk's first bit behind its block's header;
+// want_bits (LFX_DEBUG, else null): the counted sizes — a walk that ends elsewhere raises res->status (2) instead of leaving
+// a corrupt stream.
+__global__ __launch_bounds__(PACK_THREADS) void pack_chunk_kernel(
+    const ChunkDesc *__restrict__ chunks, uint32_t nchunks, const BlockDesc *__restrict__ blocks,
+    const uint32_t *__restrict__ codes, const uint32_t *__restrict__ ncodes,
+    const BlockCodes *__restrict__ bc, const uint64_t *__restrict__ block_start,
+    const uint64_t *__restrict__ chunk_start, const uint64_t *__restrict__ want_bits,
+    EncodeResult *__restrict__ res, uint64_t out_base_bit, uint32_t *__restrict__ out) {
+    __shared__ uint32_t lit[288], dst[32];
+    __shared__ uint32_t wsum[PACK_THREADS / 64];
+    __shared__ unsigned long long stage[STAGE_WORDS64];
+    // (read by one lane: under LFX_DEBUG another workgroup may raise the status while this one starts, and the lanes of a
+    //  workgroup must all take the same way to the barriers)
+    __shared__ uint32_t s_status;
+    if (threadIdx.x == 0) s_status = res->status;
+    __syncthreads();
+    if (s_status != 0) return;
+    uint32_t cur_block = 0xFFFFFFFFu;
+    uint32_t cv[PACK_PER_THREAD], cvn[PACK_PER_THREAD];
+    for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const ChunkDesc ch = chunks[c];
+        const uint32_t n = ncodes[c];
+        const uint64_t rel = chunk_start[c];
+        if (n == 0 || blocks[ch.block].type == BT_RAW) continue;      // (uniform; a stored block's bytes: block_header_kernel)
+        const uint64_t start = block_start[ch.block] + 3 + bc[ch.block].hdr_bits + rel - out_base_bit;   // bit offset inside `out`
+        const uint32_t *p = codes + ch.code_off;
+        // each lane owns PACK_PER_THREAD consecutive codes of a tile (loads first, clamped addresses, no branch around a load)
 #pragma unroll
-        for (int k = 0; k < PACK_PER_THREAD; ++k) {
-            const uint32_t i = first + k;
-            const uint32_t nb = code_bits(cv[k], lit, dst, cb[k]);
-            cn[k] = i < hi ? nb : 0u;
-            cb[k] = i < hi ? cb[k] : 0ull;
-            mine += cn[k];
-        }
-        // exclusive scan of `mine` over the workgroup
-        uint32_t x = mine;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o);
-            if ((int)lane >= o) x += y;
-        }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        uint32_t pre = 0;
-        for (uint32_t w = 0; w < wave; ++w) pre += wsum[w];
-        const uint32_t total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        const uint64_t start = ts[q] - out_base_bit;  // bit offset inside `out`
-        const uint32_t phase = (uint32_t)start & 31;
-        uint32_t bit = phase + pre + x - mine;
+        for (int k = 0; k < PACK_PER_THREAD; ++k) cv[k] = p[min(threadIdx.x * PACK_PER_THREAD + k, n - 1)];
+        uint64_t carry = start;
+        for (uint32_t lo = 0; lo < n; lo += PACK_TILE) {
+            const uint32_t hi = min(n, lo + PACK_TILE);
+            const uint32_t first = lo + threadIdx.x * PACK_PER_THREAD;
+            if (hi < n) {                                             // (uniform) the next tile's codes are requested now
 #pragma unroll
-        for (int k = 0; k < PACK_PER_THREAD; ++k) {
-            if (cn[k]) {
-                const uint32_t w = bit >> 6, sh = bit & 63;
-                atomicOr(&stage[w], cb[k] << sh);
-                if (sh + cn[k] > 64) atomicOr(&stage[w + 1], cb[k] >> (64 - sh));
-                bit += cn[k];
+                for (int k = 0; k < PACK_PER_THREAD; ++k) cvn[k] = p[min(first + PACK_TILE + k, n - 1)];
             }
+            __syncthreads();             // (the previous tile's flush has read the staging buffer, its sums the tables)
+            if (ch.block != cur_block) {
+                cur_block = ch.block;
+                const BlockCodes *B = &bc[ch.block];
+                for (uint32_t i = threadIdx.x; i < 288; i += PACK_THREADS) lit[i] = B->lit[i];
+                if (threadIdx.x < 32) dst[threadIdx.x] = B->dist[threadIdx.x];
+            }
+            carry += pack_tile(cv, first, hi, lit, dst, wsum, stage, carry, out);
+#pragma unroll
+            for (int k = 0; k < PACK_PER_THREAD; ++k) cv[k] = cvn[k];
         }
-        __syncthreads();
-        // staging → output words; the first and last word may be shared with neighbours
-        const uint32_t nwords = (phase + total + 31) >> 5;
-        const uint32_t *s32 = (const uint32_t *)stage;
-        uint32_t *o = out + (start >> 5);
-        for (uint32_t i = threadIdx.x; i < nwords; i += PACK_THREADS) {
-            const uint32_t v = s32[i];
-            if (i == 0 || i == nwords - 1) { if (v) atomicOr(&o[i], v); }
-            else o[i] = v;
-        }
+        if (want_bits && threadIdx.x == 0 && carry - start != want_bits[c]) atomicOr(&res->status, 2u);
     }
 }
 
@@ -1356,6 +1455,34 @@ int launch_pack(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Chun
         LFX_LAUNCH_CHECK();
         hipLaunchKernelGGL(pack_kernel, dim3(ngroups), dim3(PACK_THREADS), 0, st, chunks,
                            nchunks, blocks, codes, ncodes, bc, tile_start, res, out_base_bit, out, tile_map, ntiles);
+        LFX_LAUNCH_CHECK();
+    }
+    if (nblocks) {
+        hipLaunchKernelGGL(block_header_kernel, dim3(nblocks), dim3(256), 0, st, in, in_bytes, blocks,
+                           bc, block_start, res, out_base_bit, out);
+        LFX_LAUNCH_CHECK();
+    }
+    return 0;
+}
+// pack by chunk: the Huffman stage over per-chunk symbol counts, and the one pack kernel behind it (chunk_bits: 2 * nchunks
+// words — sizes, then starts; check: LFX_DEBUG, the walk's end is compared with the counted size)
+int launch_huffman_chunks(hipStream_t st, const BlockDesc *blocks, uint32_t nblocks, uint32_t nchunks, const uint32_t *hist_chunk,
+                          BlockCodes *bc, uint64_t *chunk_bits, uint64_t *dbg) {
+    if (nblocks == 0) return 0;
+    hipLaunchKernelGGL(huffman_chunk_kernel, dim3(nblocks), dim3(HUFF_THREADS), 0, st, blocks, nchunks, hist_chunk, bc, chunk_bits, dbg);
+    LFX_LAUNCH_CHECK();
+    return 0;
+}
+int launch_pack_chunks(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, uint32_t nchunks,
+                       const BlockDesc *blocks, uint32_t nblocks, const uint32_t *codes, const uint32_t *ncodes, const BlockCodes *bc,
+                       const uint64_t *block_start, const uint64_t *chunk_bits, bool check, EncodeResult *res, uint64_t out_base_bit,
+                       uint32_t *out, uint32_t n_cu) {
+    if (nchunks) {
+        // (at most eight workgroups per CU — 32 wavefronts, all that a CU holds: with more chunks than that a workgroup takes
+        //  several, one after the other.  The benchmark's 1025 chunks on 256 CUs are one chunk per workgroup, four per CU.)
+        const uint32_t grid = std::min<uint32_t>(nchunks, 8 * std::max<uint32_t>(n_cu, 1));
+        hipLaunchKernelGGL(pack_chunk_kernel, dim3(grid), dim3(PACK_THREADS), 0, st, chunks, nchunks, blocks, codes, ncodes, bc,
+                           block_start, chunk_bits + nchunks, check ? chunk_bits : nullptr, res, out_base_bit, out);
         LFX_LAUNCH_CHECK();
     }
     if (nblocks) {

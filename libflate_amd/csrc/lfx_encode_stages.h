@@ -26,10 +26,14 @@ struct EncodeGeom {
     uint32_t emit_per = 0, emit_parts = 0;   // parse_emit_hist_kernel: segments per workgroup, workgroups for the chunk of most segments
     bool fused_hist = false;      // the parse counts the blocks' symbols (no histogram_kernel)
     uint32_t split = 1;           // histogram_kernel: workgroups per chunk
+    bool pack_by_chunk = false;   // symbol counts per chunk, huffman_chunk_kernel, pack_chunk_kernel (no tile_bits / tile_scan / pack_kernel)
 };
+enum : int { PACK_BY_CHUNK_AUTO = -1, PACK_BY_CHUNK_OFF = 0, PACK_BY_CHUNK_ON = 1 };   // LFX_PACK_BY_CHUNK (Diag::pack_by_chunk)
 
 // host_codes: the code words come from the caller (no match, no parse: no segments and no workgroups).
-inline EncodeGeom encode_geometry(const Plan &plan, bool host_codes, uint32_t n_cu, bool hist_separate) {
+// pack_switch: PACK_BY_CHUNK_*.
+inline EncodeGeom encode_geometry(const Plan &plan, bool host_codes, uint32_t n_cu, bool hist_separate,
+                                  int pack_switch = PACK_BY_CHUNK_AUTO) {
     EncodeGeom g;
     for (const ChunkDesc &ch : plan.chunks)
         if (ch.len >= (1ull << 32) - 4) { g.err = GEOM_E_CHUNK_4G; return g; }
@@ -98,6 +102,16 @@ inline EncodeGeom encode_geometry(const Plan &plan, bool host_codes, uint32_t n_
     g.fused_hist = !hist_separate && parts <= 65535 && (uint64_t)nchunks * parts <= 4 * useful + 4096;
     g.emit_per = per;
     g.emit_parts = (uint32_t)parts;
+    // Pack by chunk needs the chunks' own symbol counts (the fused histogram keeps them) and sizes compressed blocks only.  It
+    // pays where every CU gets a chunk to walk and no walk is long: a workgroup packs a chunk's tiles one after the other.
+    // LFX_PACK_BY_CHUNK=1 takes it wherever it is legal, whatever the chunks; =0 never.
+    bool stored = false;
+    uint64_t max_tiles = 0;
+    for (const BlockDesc &b : plan.blocks) stored |= b.type == BT_RAW;
+    for (const ChunkDesc &ch : plan.chunks) max_tiles = std::max<uint64_t>(max_tiles, div_up(ch.len + 1, PACK_TILE));
+    const bool legal = g.fused_hist && !stored && nchunks > 0;
+    g.pack_by_chunk = legal && pack_switch != PACK_BY_CHUNK_OFF &&
+                      (pack_switch == PACK_BY_CHUNK_ON || (nchunks >= std::max<uint32_t>(n_cu, 1) && max_tiles <= PACK_CHUNK_MAX_TILES));
     return g;
 }
 

@@ -38,10 +38,14 @@ LFX_HD inline uint32_t dist_symbol(uint32_t distance, uint32_t &ebits, uint32_t 
     extra = x & ((1u << e) - 1);
     return 2 * e + 2 + ((x >> e) & 1);
 }
-#ifdef __HIPCC__
 // a code word ((val << 16) | dist) → its bit count; `bits` = its bits, LSB first (lit / dst: BlockCodes::lit / dist)
-__device__ __forceinline__ uint32_t code_bits(uint32_t v, const uint32_t *lit, const uint32_t *dst,
-                                              uint64_t &bits) {
+// (the host compiles it too: tests/c/chunk_bits.cpp sizes code lists with it)
+#ifdef __HIPCC__
+__host__ __device__ __forceinline__
+#else
+inline
+#endif
+uint32_t code_bits(uint32_t v, const uint32_t *lit, const uint32_t *dst, uint64_t &bits) {
     const uint32_t dist = v & 0xFFFFu, val = v >> 16;
     if (dist == 0) {
         const uint32_t e = lit[val];
@@ -62,7 +66,6 @@ __device__ __forceinline__ uint32_t code_bits(uint32_t v, const uint32_t *lit, c
     bits = acc;
     return n;
 }
-#endif
 LFX_HD inline uint32_t len_extra_bits_of_symbol(uint32_t sym) {  // sym 257..285
     return (sym < 265 || sym == 285) ? 0 : (sym - 261) >> 2;
 }
@@ -572,6 +575,36 @@ LFX_HD inline void huff_block_build(const uint32_t *hist, uint32_t type, BlockCo
     }
     LFX_STAMP(S, 10);
     LFX_SYNC();
+}
+
+// ---- per-chunk symbol counts (pack by chunk): a block's counters are kept one row of SYM_ROW per chunk; the
+// block's histogram is their sum, and a chunk's packed size follows from its row and the block's code widths alone.  Plain
+// lane-strided loops: the Huffman kernel calls them with its lanes, the host test (tests/c/chunk_bits.cpp) with one.
+//
+// out[i] = Σ rows[r][i] over a block's nrows chunk rows
+LFX_HD inline void sym_rows_sum(const uint32_t *rows, uint32_t nrows, uint32_t *out, int lane, int nlanes) {
+    for (uint32_t i = (uint32_t)lane; i < SYM_ROW; i += (uint32_t)nlanes) {
+        uint32_t v = 0;
+        for (uint32_t r = 0; r < nrows; r++) v += rows[(uint64_t)r * SYM_ROW + i];
+        out[i] = v;
+    }
+}
+// bits of one code word's share of counter i: the symbol's code width (BlockCodes: width << 16) plus its extra bits
+LFX_HD inline uint32_t sym_row_bits(uint32_t i, const BlockCodes *bc) {
+    if (i < 286) return (bc->lit[i] >> 16) + (i > 256 ? len_extra_bits_of_symbol(i) : 0u);
+    if (i >= 288 && i < 318) return (bc->dist[i - 288] >> 16) + dist_extra_bits_of_symbol(i - 288);
+    return 0;
+}
+// this lane's part of Σ row[i] · (width[i] + extra[i]): the sum over the lanes is the bits the chunk's code words pack into
+LFX_HD inline uint64_t chunk_bits_part(const uint32_t *row, const BlockCodes *bc, int lane, int nlanes) {
+    uint64_t part = 0;
+    for (uint32_t i = (uint32_t)lane; i < SYM_ROW; i += (uint32_t)nlanes) part += (uint64_t)row[i] * sym_row_bits(i, bc);
+    return part;
+}
+// start[c] = Σ bits[0..c): every chunk's first bit behind the block's header (one lane)
+LFX_HD inline void chunk_start_prefix(const uint64_t *bits, uint32_t n, uint64_t *start) {
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < n; c++) { start[c] = at; at += bits[c]; }
 }
 
 }  // namespace lfx

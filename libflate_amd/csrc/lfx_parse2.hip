@@ -632,6 +632,7 @@ __global__ __launch_bounds__(p2::THREADS) void parse_walk_kernel(
     }
 }
 
+static_assert(SYM_ROW == 320, "a row of symbol counters");
 constexpr uint32_t PARSE_HIST_STRIDE = 320;      // a block's symbol counters: [0,288) literal/length, [288,320) distance (= HIST_STRIDE, lfx_encode_kernels.hip)
 
 // ------------------------------------------------------------------------------------------------
@@ -754,7 +755,7 @@ __global__ __launch_bounds__(1024) void parse_fix_kernel(const uint8_t *__restri
                                                          uint32_t *__restrict__ seg_exit2,
                                                          uint32_t *__restrict__ seg_off, uint32_t *__restrict__ codes,
                                                          uint32_t *__restrict__ ncodes, uint32_t *__restrict__ seg_mpos,
-                                                         uint32_t *__restrict__ hist, DE... dict_end) {
+                                                         uint32_t *__restrict__ hist, uint32_t hist_by_chunk, DE... dict_end) {
     typedef typename p2::SrcOf<sizeof...(DE) != 0>::type Src;
     __shared__ uint32_t s_first_bad, s_wsum[16], s_redo[2];
     const ChunkDesc ch = chunks[blockIdx.x];
@@ -826,7 +827,8 @@ __global__ __launch_bounds__(1024) void parse_fix_kernel(const uint8_t *__restri
         // default.rs:105-107: the rest are literals (at most 3 bytes)
         const uint32_t pos = ch.n_seg ? e_last : 0;
         // (hist: the block's symbol counts are taken where the code words are written — parse_emit_hist_kernel — so these few are too)
-        uint32_t *hb = hist ? hist + (uint64_t)ch.block * PARSE_HIST_STRIDE : nullptr;
+        // (hist_by_chunk: a row per chunk — pack by chunk sizes every chunk from its own counts; EndOfBlock is the last chunk's)
+        uint32_t *hb = hist ? hist + (uint64_t)(hist_by_chunk ? blockIdx.x : ch.block) * PARSE_HIST_STRIDE : nullptr;
         for (uint32_t i = pos + tid; i < n; i += T) {
             const uint32_t byte = src.load1(i);
             out[total + (i - pos)] = byte << 16;
@@ -837,7 +839,7 @@ __global__ __launch_bounds__(1024) void parse_fix_kernel(const uint8_t *__restri
     if (ch.flags & CH_LAST_IN_BLOCK) {
         if (tid == 0) {
             out[total] = CODE_EOB;  // encode.rs:417
-            if (hist) atomicAdd(&hist[(uint64_t)ch.block * PARSE_HIST_STRIDE + 256], 1u);
+            if (hist) atomicAdd(&hist[(uint64_t)(hist_by_chunk ? blockIdx.x : ch.block) * PARSE_HIST_STRIDE + 256], 1u);
         }
         total += 1;
     }
@@ -982,7 +984,8 @@ __global__ __launch_bounds__(64 * EMIT_WAVES) void parse_emit_hist_kernel(const 
                                                                          const uint32_t *__restrict__ seg_exit2,
                                                                          const uint32_t *__restrict__ seg_mpos,
                                                                          const uint32_t *__restrict__ seg_kspec,
-                                                                         uint32_t segs_per_wg, uint32_t *__restrict__ hist) {
+                                                                         uint32_t segs_per_wg, uint32_t *__restrict__ hist,
+                                                                         uint32_t hist_by_chunk) {
     __shared__ uint32_t hh[EMIT_HREP * PARSE_HIST_STRIDE];
     const ChunkDesc ch = chunks[blockIdx.x];
     const uint32_t sA = blockIdx.y * segs_per_wg;
@@ -996,7 +999,8 @@ __global__ __launch_bounds__(64 * EMIT_WAVES) void parse_emit_hist_kernel(const 
         emit_segment<true>(in, in_bytes, ch, ch.seg_base + s, cd, vis, seg_off, codes, stage, seg_count, seg_exit2, seg_mpos, seg_kspec,
                            lane, h);
     __syncthreads();
-    uint32_t *g = hist + (uint64_t)ch.block * PARSE_HIST_STRIDE;
+    // (hist_by_chunk: the chunk's own row — the same number of atomics, on more addresses)
+    uint32_t *g = hist + (uint64_t)(hist_by_chunk ? blockIdx.x : ch.block) * PARSE_HIST_STRIDE;
     for (uint32_t i = tid; i < PARSE_HIST_STRIDE; i += 64 * EMIT_WAVES) {
         uint32_t v = 0;
 #pragma unroll
@@ -1061,7 +1065,8 @@ int launch_parse_walk(hipStream_t st, const uint8_t *in, uint64_t in_bytes, cons
 int launch_parse_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks, uint32_t nchunks, uint32_t nsegs,
                        const uint16_t *cd, uint32_t max_len, uint64_t *vis, uint32_t *seg_tmp, uint32_t *codes, uint32_t *ncodes,
                        uint32_t *stage, const uint32_t *seg_map, uint32_t *hist, uint32_t emit_per, uint32_t emit_parts,
-                       const uint8_t *dict_win, bool fixseg_only) {
+                       const uint8_t *dict_win, bool fixseg_only, bool hist_by_chunk) {
+    const uint32_t by_chunk = hist_by_chunk ? 1u : 0u;
     if (nchunks == 0) return 0;
     const uint8_t *dict_end = dict_win ? dict_win + MAX_WINDOW : nullptr;
     const SegTmp t(seg_tmp, nsegs);
@@ -1079,15 +1084,15 @@ int launch_parse_chain(hipStream_t st, const uint8_t *in, uint64_t in_bytes, con
     const uint32_t fix_threads = nsegs / nchunks > 128 ? 1024u : 64u;
     if (dict_win)
         hipLaunchKernelGGL(parse_fix_kernel<const uint8_t *>, dim3(nchunks), dim3(fix_threads), 0, st, in, in_bytes, chunks, cd, max_len,
-                           vis, t.exit, t.count, t.exit2, t.off, codes, ncodes, t.mpos, hist, dict_end);
+                           vis, t.exit, t.count, t.exit2, t.off, codes, ncodes, t.mpos, hist, by_chunk, dict_end);
     else
         hipLaunchKernelGGL(parse_fix_kernel<>, dim3(nchunks), dim3(fix_threads), 0, st, in, in_bytes, chunks, cd, max_len, vis,
-                           t.exit, t.count, t.exit2, t.off, codes, ncodes, t.mpos, hist);
+                           t.exit, t.count, t.exit2, t.off, codes, ncodes, t.mpos, hist, by_chunk);
     LFX_LAUNCH_CHECK();
     if (nsegs && hist) {
         // (the caller sizes the grid: emit_per segments per workgroup, emit_parts = the longest chunk's workgroups)
         hipLaunchKernelGGL(parse_emit_hist_kernel, dim3(nchunks, emit_parts ? emit_parts : 1), dim3(64 * EMIT_WAVES), 0, st, in, in_bytes,
-                           chunks, cd, vis, t.off, codes, stage, t.count, t.exit2, t.mpos, t.kspec, emit_per ? emit_per : 1, hist);
+                           chunks, cd, vis, t.off, codes, stage, t.count, t.exit2, t.mpos, t.kspec, emit_per ? emit_per : 1, hist, by_chunk);
         LFX_LAUNCH_CHECK();
     } else if (nsegs) {
         hipLaunchKernelGGL(parse_emit_kernel, dim3(nsegs), dim3(64), 0, st, in, in_bytes, chunks, cd, vis, t.off, codes,
