@@ -507,6 +507,80 @@ def build_M():
     return head + bits.getvalue() + tail.compress(text[cut:]) + tail.flush(), plain + b + text[cut:]
 
 
+# ---- N: the shapes above as ONE stream of unlike neighbours, stored blocks at four bit phases between them
+N_PHASES = (1, 4, 6, 7)
+E2_SYMBOLS = rle(E2_LIT + E2_DIST)
+E3_SYMBOLS = rle(E3_LIT) + [(16, 3), (16, 3), (16, 1)]
+N_WRITERS = {
+    "A": lambda bits, t: dyn_block(bits, A_LIT, A_DIST, t, False),
+    "C1": lambda bits, t: dyn_block(bits, C1_LIT, [1], t, False),
+    "C2": lambda bits, t: dyn_block(bits, C2_LIT, sparse(30, {29: 1}), t, False),
+    "D": lambda bits, t: dyn_block(bits, FIXED_LIT, [5] * 30, t, False, nl=288, nd=30),
+    "E2": lambda bits, t: dyn_block(bits, E2_LIT, E2_DIST, t, False, nl=257, header_symbols=E2_SYMBOLS),
+    "E3": lambda bits, t: dyn_block(bits, E3_LIT, E3_DIST, t, False, header_symbols=E3_SYMBOLS),
+    "E4": lambda bits, t: dyn_block(bits, E2_LIT, E2_DIST, t, False, cl_lengths=E2_CL),
+}
+
+
+def n_c1_tokens(rng, groups):
+    """forty short codes at distance 1, then a run of one to three matches of 258 bytes, `groups` times"""
+    tokens = [120]
+    for _ in range(groups):
+        tokens += rng.choices([120, 121, (3, 1), (4, 1), (5, 1), (6, 1), (11, 1)], k=40) + [(258, 1)] * rng.randint(1, 3)
+    return tokens
+
+
+def build_N_chain(phases=None, kinds=None):
+    """phases (a list) receives the bit position mod 8 of every stored block's header, kinds the blocks' names in order.  A
+    block in front of a stored one gets up to seven more literals of a width that shifts its end to the wanted phase."""
+    rng = random.Random(0x4E)
+    bits = BitWriter()
+    plain = bytearray()
+    stored = iter(N_PHASES)
+
+    def block(kind, tokens, filler=None):
+        if filler is not None:            # a stored block follows: end this one at its phase
+            want = next(stored)
+            for k in range(8):
+                probe = BitWriter()
+                N_WRITERS[kind](probe, tokens + [filler] * k)
+                if (bits.bitpos() + probe.bitpos()) % 8 == want:
+                    break
+            else:
+                raise AssertionError((kind, want))
+            tokens = tokens + [filler] * k
+        N_WRITERS[kind](bits, tokens)
+        plain.extend(expand(tokens, history=bytes(plain[-32768:]))[min(len(plain), 32768):])
+        if kinds is not None:
+            kinds.append(kind)
+        if filler is not None:
+            if phases is not None:
+                phases.append(bits.bitpos() % 8)
+            data = rng.randbytes(rng.randint(1000, 3000))
+            stored_block(bits, data, False)
+            plain.extend(data)
+            if kinds is not None:
+                kinds.append("stored")
+
+    def a_first():
+        return [(258, 32768), (3, 32768)] + a_tokens(rng, 25000, 3000, matches_first=True)
+
+    block("D", list(rng.randbytes(20000)))
+    block("C1", n_c1_tokens(rng, 420), filler=120)                       # (3 bits a literal)
+    block("A", a_first(), filler=ord("e"))                               # its (…, 32768) read across the stored block (1 bit)
+    plain.extend(b_block(bits, rng, 20000, False))
+    if kinds is not None:
+        kinds.append("B")
+    block("C2", rng.choices(range(48, 56), k=20000) + rng.choices([(3, 32768), (258, 32768), (6, 24577), 50], k=1500), filler=48)
+    block("E2", e2_tokens(20000))
+    block("E3", rng.choices(range(14), k=3000) + rng.choices(list(range(14)) + [(3, d) for d in (1, 2, 4, 6, 12, 24, 48, 96, 192, 255)], k=17000))
+    block("E4", e2_tokens(20000), filler=248)                            # (5 bits)
+    block("A", a_first())
+    block("A", a_first())
+    fixed_block(bits, [], True)
+    return bits.getvalue(), bytes(plain)
+
+
 # ---- rejects: alone, and behind the block of B (≥ 8 KiB compressed)
 def _front(bits, behind):
     if not behind:
@@ -553,9 +627,36 @@ def build_L(behind=False):
     return bits.getvalue(), None
 
 
+def valid_prefix(name):
+    """the blocks of a reject in front of the block that holds its fault, closed by an empty final block: a valid stream"""
+    bits = BitWriter()
+    _front(bits, name.endswith("_behind"))
+    if name.split("_")[0] in ("I1", "J"):
+        fixed_block(bits, list(b"0123456789"), False)
+    fixed_block(bits, [], True)
+    return bits.getvalue()
+
+
+def same_bits(a, b, nbits):
+    """the first `nbits` bits of two streams are equal"""
+    k, r = divmod(nbits, 8)
+    return a[:k] == b[:k] and (r == 0 or (a[k] ^ b[k]) & ((1 << r) - 1) == 0)
+
+
+def takes_windows(blocks, n, step, head=0):
+    """Whether the stream decoder MUST decode a stream of `n` bytes in more than one window when its reader hands over `step`
+    bytes a call, decided from the oracle's block list alone.  With E the byte at which the first block ends (`head`: the
+    container header's bytes in front), an attempt is due once the input has grown by a quarter since the last one that
+    found no complete block, and one read may lie on either side of it: the first window is decoded in front of the stream's
+    end when 1.25 E + 2 step < n."""
+    assert not blocks[0][3]
+    e = head + (blocks[0][1] + 7) // 8
+    return 1.25 * e + 2 * step < n
+
+
 VALID_ZLIB_AGREES = ["A", "C1", "C2", "E1", "E2", "E2_span", "E3", "E4_hclen5", "E4_hclen_field4", "E4_hclen19", "E4_wide_step", "G", "H"]
 VALID_ZLIB_REFUSES = ["B", "D"]
-VALID_ORACLE_ONLY = ["M"]
+VALID_ORACLE_ONLY = ["M", "N_chain"]
 SMALL = ["A_small", "B_small", "C1_small", "G_small"]
 REJECT_PREFIX = {"I1": "The value 286 must not occur in compressed data", "I2": "Invalid huffman coded stream", "J": "Bit region conflict",
                  "K": "failed to fill whole buffer", "L": "No preceding value"}
@@ -564,7 +665,7 @@ CASES = [
     ("A", build_A), ("B", build_B), ("C1", build_C1), ("C2", build_C2), ("D", build_D), ("E1", build_E1),
     ("E2", build_E2), ("E2_span", functools.partial(build_E2, nl=270)), ("E3", build_E3),
     ("E4_hclen5", build_E4_hclen5), ("E4_hclen_field4", build_E4_hclen_field4), ("E4_hclen19", build_E4_hclen19),
-    ("E4_wide_step", build_E4_wide_step), ("G", build_G), ("H", build_H), ("M", build_M),
+    ("E4_wide_step", build_E4_wide_step), ("G", build_G), ("H", build_H), ("M", build_M), ("N_chain", build_N_chain),
     ("A_small", functools.partial(build_A, 300, 100)), ("B_small", functools.partial(build_B, 600)),
     ("C1_small", functools.partial(build_C1, 400)), ("G_small", functools.partial(build_G, 30, 300)),
 ]

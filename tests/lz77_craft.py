@@ -509,6 +509,13 @@ def built():
     return dict((name, (write(blocks_of(name)), model(blocks_of(name))[0])) for name, _ in CASES)
 
 
+def valid_prefix(name):
+    """the blocks of a reject in front of the block that holds its bad token, closed by an empty final block: a valid stream"""
+    blocks = blocks_of(name)
+    k = next(i for i in range(len(blocks)) if model(blocks[:i + 1])[0] is None)
+    return write(blocks[:k] + [("fixed", [])])
+
+
 def front_of(name):
     """the bytes in front of a reject's bad token"""
     return model(blocks_of(name))[1]

@@ -75,6 +75,66 @@ def test_stored_headers_at_every_bit_phase():
     assert sorted(phases) == list(range(8))
 
 
+N_CODED = ["D", "C1", "A", "B", "C2", "E2", "E3", "E4", "A", "A"]
+
+
+def test_N_chain_blocks(oracle, verdicts):
+    """one stream of every shape: at least twelve non-final blocks, the coded ones of 8 to 40 KiB, four stored ones of 1000 to
+    3000 bytes whose headers sit at four bit phases, unlike neighbours, an empty final fixed block"""
+    phases, kinds = [], []
+    z, want = dc.build_N_chain(phases, kinds)
+    assert (z, want) == verdicts["N_chain"][:2]
+    assert phases == list(dc.N_PHASES) and len(set(phases)) == 4
+    blocks = oracle.scan_blocks(z)
+    assert len(blocks) == len(kinds) + 1 >= 13 and [b[3] for b in blocks] == [0] * len(kinds) + [1]
+    assert blocks[-1][2:] == (1, 1, 0) and blocks[-1][1] - blocks[-1][0] == 10
+    assert [k for k in kinds if k != "stored"] == N_CODED and all(a != b for a, b in zip(kinds, kinds[1:-1]))
+    at, got_phases = 0, []
+    for kind, (start, end, btype, bfinal, out_len) in zip(kinds, blocks):
+        size = (end - start) / 8
+        print("N_chain %-6s btype %d  %7.0f bytes -> %6d" % (kind, btype, size, out_len))
+        if kind == "stored":
+            assert btype == 0 and 1000 <= out_len <= 3000
+            got_phases.append(start % 8)
+        else:
+            assert btype == 2 and 8 * dc.KIB <= size <= 40 * dc.KIB, (kind, size)
+        at += out_len
+    assert got_phases == phases and at == len(want) < dc.MIB
+    # the matches that open the A blocks read the blocks in front, the first of them through a stored block
+    for i, kind in enumerate(kinds):
+        if kind == "A":
+            assert sum(b[4] for b in blocks[:i]) >= 32768
+    assert kinds[kinds.index("A") - 1] == "stored" and kinds[len(kinds) - 2:] == ["A", "A"] and kinds[len(kinds) - 3] == "stored"
+
+
+STREAM_STEP = 997           # (test_gpu_craft_stream.py: a prime below every multi-block case's block size)
+
+
+def test_cases_that_must_take_several_windows(oracle, verdicts):
+    """the stream decoder's tests mean something only where a case cannot be decoded in one window (deflate_craft.takes_windows)"""
+    for name, step in (("N_chain", STREAM_STEP), ("G", STREAM_STEP), ("H", STREAM_STEP), ("M", 65536)):
+        z = verdicts[name][0]
+        blocks = oracle.scan_blocks(z)
+        assert len(blocks) >= 5 and dc.takes_windows(blocks, len(z), step), name
+    for name in ("N_chain", "H"):         # ... also as zlib and gzip streams
+        z = verdicts[name][0]
+        assert dc.takes_windows(oracle.scan_blocks(z), len(z) + 18, STREAM_STEP, head=10), name
+    coded = [b for b in oracle.scan_blocks(verdicts["N_chain"][0]) if b[2] == 2]
+    assert min(b[1] - b[0] for b in coded) // 8 > STREAM_STEP
+
+
+@pytest.mark.parametrize("name", dc.REJECTS)
+def test_reject_prefixes(oracle, verdicts, name):
+    """valid_prefix(name) is the reject's own bits up to the block that holds the fault, and the oracle delivers its bytes"""
+    z, _want, (rc, out, used, msg) = verdicts[name]
+    prefix = dc.valid_prefix(name)
+    prc, pout, pused, _ = oracle.decode(oracle.DEFLATE, prefix)
+    blocks = oracle.scan_blocks(prefix)
+    assert prc == OK and pused == len(prefix) and blocks[-1][2:] == (1, 1, 0)
+    assert dc.same_bits(z, prefix, blocks[-1][0])
+    assert out[:len(pout)] == pout and len(pout) == sum(b[4] for b in blocks)
+
+
 def test_the_shapes_the_cases_are_about(oracle, verdicts):
     # A: both codes reach 15 bits and the distances 24577...32768 are used
     assert max(dc.A_LIT) == 15 and max(dc.A_DIST) == 15 and dc.dist_symbol(32768) == (29, 13, 8191)

@@ -1,5 +1,6 @@
 """GPU: legal DEFLATE that neither this library's encoder nor python-zlib writes, and rejects decided in a header or by one
-symbol (deflate_craft.CASES), through three entry points: lfx_decode_device, lfx_decode_size_device, lfx_decode_batch_device.
+symbol (deflate_craft.CASES), through three entry points: lfx_decode_device, lfx_decode_size_device, lfx_decode_batch_device,
+and as the members of one gzip file through both members paths.
 Every stream's verdict is fixed by the oracle on the CPU first (test_craft_streams.py holds the conditions under which these
 tests mean anything).  Integer work: every comparison is exact.  A test walks all its cases and reports every one that differs."""
 import ctypes as C
@@ -11,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 import deflate_craft as dc
 from test_gpu_parity import ctx, ffi, lfx, synth  # noqa: F401  (fixtures)
-from test_gpu_members import _dev, torch  # noqa: F401
+from test_gpu_members import _dev, check, torch  # noqa: F401
 from deflate_craft import gzwrap, zwrap
 
 GUARD = 256
@@ -131,6 +132,62 @@ def test_decode_batch_device(ctx, ffi, oracle, torch, crafted):
         if not (host[out_off[i] + out_cap[i]:end] == 0x5A).all():
             bad.append("%s: the gap behind its output was written" % name)
     _report(bad)
+
+
+def _gzip_file(crafted, third=None):
+    """every valid case but M as a gzip member, in CASES order (`third`: a case to put in as the third member)
+    → (the file, [(name, member bytes, output bytes)])"""
+    raw = dict((name, (z, v)) for name, fmt_name, z, v in crafted if fmt_name == "DEFLATE")
+    names = [n for n, _ in dc.CASES if n in dc.VALID and n != "M"]
+    if third is not None:
+        names.insert(2, third)
+    parts = [(n, gzwrap(raw[n][1][1], raw[n][0]), raw[n][1][1]) for n in names]
+    return b"".join(p[1] for p in parts), parts
+
+
+def _table(parts):
+    out, at, oat = [], 0, 0
+    for _name, member, plain in parts:
+        out.append((at, len(member), oat, len(plain)))
+        at, oat = at + len(member), oat + len(plain)
+    return out
+
+
+def test_members_paths(ctx, ffi, oracle, torch, crafted):
+    """one gzip file whose members are the valid cases: lfx_decode_members_device and the sequential member loop (`check` holds
+    them to each other and to the oracle's MultiDecoder) give the oracle's bytes and the member table of the file as built"""
+    data, parts = _gzip_file(crafted)
+    assert len(parts) == len(dc.VALID) - 1 >= 20
+    o_rc, o_out, o_used, o_msg = oracle.decode(oracle.GZIP, data, multi=True)
+    assert (o_rc, o_used) == (0, len(data)) and o_out == b"".join(p[2] for p in parts), o_msg
+    rc, out, used, members = check(ctx, ffi, oracle, torch, data, want_status=ffi.OK)
+    bad = []
+    if out != o_out:
+        first = next((i for i in range(min(len(out), len(o_out))) if out[i] != o_out[i]), min(len(out), len(o_out)))
+        at = [p[0] for p, m in zip(parts, _table(parts)) if m[2] <= first < m[2] + max(m[3], 1)]
+        bad.append("bytes differ from %d (%d of %d), in %s" % (first, len(out), len(o_out), at))
+    if used != len(data):
+        bad.append("consumed %d of %d" % (used, len(data)))
+    for (name, _m, _p), got, want in zip(parts, members, _table(parts)):
+        if got != want:
+            bad.append("%s: member %r, built as %r" % (name, got, want))
+    if len(members) != len(parts):
+        bad.append("%d members of %d" % (len(members), len(parts)))
+    _report(bad)
+
+
+def test_members_paths_reject_as_third_member(ctx, ffi, oracle, torch, crafted):
+    """the same file with J_behind (an over-subscribed code behind 10 KB of valid blocks) as its third member: the oracle's
+    status and message, the first two members in the table, the oracle's bytes up to the fault"""
+    data, parts = _gzip_file(crafted, third="J_behind")
+    assert parts[2][0] == "J_behind"
+    o_rc, o_out, o_used, o_msg = oracle.decode(oracle.GZIP, data, multi=True)
+    assert o_rc == ffi.E_INVALID_DATA and o_msg.startswith(dc.REJECT_PREFIX["J"])
+    assert o_out == b"".join(p[2] for p in parts[:3]) and len(parts[2][2]) >= 20000
+    rc, out, used, members = check(ctx, ffi, oracle, torch, data, want_status=ffi.E_INVALID_DATA)
+    assert ctx.last_error().startswith(dc.REJECT_PREFIX["J"]), ctx.last_error()
+    assert members == _table(parts)[:2]
+    assert out == o_out
 
 
 def test_record_shapes_that_leave_the_fast_path(ffi, lfx, torch, crafted, monkeypatch):

@@ -8,7 +8,7 @@ import zlib
 import pytest
 
 import lz77_craft as lc
-from deflate_craft import KIB, MIB
+from deflate_craft import KIB, MIB, same_bits, takes_windows
 
 OK, INVALID_DATA = 0, 1
 
@@ -56,6 +56,29 @@ def test_reject_cases(verdicts, name):
     assert out == lc.front_of(name)            # the model's bytes in front of the bad token
     with pytest.raises(zlib.error):
         zlib.decompress(z, -15)
+
+
+@pytest.mark.parametrize("name", lc.REJECTS)
+def test_reject_prefixes(oracle, verdicts, name):
+    """valid_prefix(name) is the reject's own bits up to the block that holds the bad token, and the oracle delivers its bytes"""
+    z, _want, (rc, out, used, msg) = verdicts[name]
+    prefix = lc.valid_prefix(name)
+    prc, pout, pused, _ = oracle.decode(oracle.DEFLATE, prefix)
+    blocks = oracle.scan_blocks(prefix)
+    assert prc == OK and pused == len(prefix) and blocks[-1][2:] == (1, 1, 0)
+    assert same_bits(z, prefix, blocks[-1][0])
+    assert out[:len(pout)] == pout and len(pout) == sum(b[4] for b in blocks)
+
+
+STREAM_STEP = 997           # (test_gpu_craft_stream.py)
+
+
+def test_cases_that_must_take_several_windows(oracle, verdicts):
+    """the stream decoder's tests mean something only where a case cannot be decoded in one window (deflate_craft.takes_windows)"""
+    for name in ("X_relay40", "X_over_stored", "U_anchor_big"):
+        z = verdicts[name][0]
+        assert takes_windows(oracle.scan_blocks(z), len(z), STREAM_STEP), name
+    assert len(oracle.scan_blocks(verdicts["X_relay40"][0])) == 41 and len(oracle.scan_blocks(verdicts["U_anchor_big"][0])) == 5
 
 
 def test_rejects_reach_one_byte_too_far():
