@@ -134,6 +134,31 @@ enum { LFX_LZ77_LEVEL = 4 };
  * (lfx_encode_shard_prepare, lfx_sharded_encode_begin): a stored block's size depends on the bit phase there.  LFX_LZ77_LEVEL
  * (kind 4) is served and refused with LFX_HUFFMAN_AUTO exactly as the kinds 2 and 3 are. */
 enum { LFX_HUFFMAN_FIXED = 0, LFX_HUFFMAN_DYNAMIC = 1, LFX_HUFFMAN_AUTO = 2 };
+/* lfx_encode_opts::block_merge.  0: off (the default: the blocks are the plan's, as in the reference).  1 — opt-in, not a
+ * reference option: neighbouring dynamic blocks are joined wherever one Huffman code for both is no longer
+ * than two, so that block_size becomes the SMALLEST block.  Any other value: LFX_E_ARG.  No effect under no_compression or
+ * dynamic_huffman = 0 (there is no dynamic block to join).
+ *  - The plan, the LZ77 code words and the container header are those of the same call with block_merge = 0.
+ *  - Candidates are the plan's dynamic blocks.  A run is a maximal sequence of consecutive candidates of one stream (a stream:
+ *    one batch record, one dictionary record, the one buffer of a one-shot call); a stored block of the plan (the zlib sync
+ *    marker) ends a run.  The candidates of a run are numbered from 0, n of them.
+ *  - The decision is a fixed binary tree over a run, so it is parallel and deterministic.  The node at level l = 1..4 with
+ *    index k covers the candidates [k * 2^l, min((k + 1) * 2^l, n)); its children are the two level l - 1 nodes inside it; a
+ *    level 0 node is one candidate.  A leaf is whole.  A node whose right child is empty IS its left child.  Any other node is
+ *    whole exactly when both children are whole and D(node) <= D(left) + D(right).
+ *  - D(X) = the exact bits (3 + dynamic header + symbols) of the dynamic block over the sum of the symbol counts of X's
+ *    candidates with ONE EndOfBlock.
+ *  - Every maximal whole node becomes one block: at most LFX_MERGE_MAX candidates form one block, and a block never crosses a
+ *    LFX_MERGE_MAX-candidate boundary of its run.  A merged block holds its candidates' code words in order without the interior
+ *    EndOfBlocks, takes BFINAL and the byte alignment behind it from its last candidate, and covers the input bytes of all.
+ *  - With dynamic_huffman = 1 the output is never longer than the block_merge = 0 output of the same call (by induction over the
+ *    tree: a whole node is no longer than its children together): lfx_encode_bound and its siblings hold as they are.  With
+ *    LFX_HUFFMAN_AUTO the form is chosen per MERGED block, behind the merge, so that output is never longer than the
+ *    block_merge = 1, dynamic_huffman = 1 output (per block the smallest of three forms, the dynamic one among them).
+ * Served by lfx_encode_device / _host, lfx_encode_batch_device and the dictionary encode calls (plain and chain dictionaries),
+ * with every lz77_kind.  LFX_E_UNSUPPORTED from lfx_encoder_* (a merge across a flush would break what a flush promises), from
+ * lfx_encode_members_*, from lfx_encode_index_device and from the N-GPU encode. */
+#define LFX_MERGE_MAX 16
 /* zlib::FlushMode (src/zlib.rs:184-195) */
 enum { LFX_FLUSH_NONE = 0, LFX_FLUSH_SYNC = 2 };
 
@@ -157,6 +182,8 @@ typedef struct lfx_encode_opts {
                                   (gzip.rs:84-92,684) */
     const uint8_t *extra;      /* gzip.rs:191    serialized subfields (id[2] len[2] data)* */
     uint32_t extra_len;
+    uint32_t block_merge;      /* 0 (default): the plan's blocks; 1: neighbouring dynamic blocks joined where one code is no longer
+                                  (opt-in, above; in what was padding: the size and every other offset are unchanged) */
     const char *filename;      /* gzip.rs:197    NUL-terminated */
     const char *comment;       /* gzip.rs:203 */
 } lfx_encode_opts;

@@ -42,6 +42,12 @@ void lfx_debug_symbols(uint32_t length, uint32_t distance, uint32_t *out6);
  * at most max_blocks entries are written.  Reads results back; starts no compression work. */
 int lfx_debug_block_choices(lfx_ctx *c, uint8_t *out, size_t max_blocks, size_t *n_blocks);
 
+/* block_merge: for every block of the plan of the context's last encode pass, in plan order, the index of the
+ * block its code words ended up in — its own for a block that was not absorbed.  *n_blocks = the blocks of that pass — 0 when
+ * it was not a block_merge one; at most max_blocks entries are written.  Reads results back; starts no compression work.
+ * (Under LFX_HUFFMAN_AUTO, lfx_debug_block_choices reports 3 for an absorbed block.) */
+int lfx_debug_block_merges(lfx_ctx *c, uint32_t *out, size_t max_blocks, size_t *n_blocks);
+
 #ifdef __cplusplus
 }
 #endif

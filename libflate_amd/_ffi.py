@@ -56,6 +56,7 @@ class EncodeOpts(C.Structure):
         ("lz77_kind", C.c_int32), ("window_size", C.c_uint32), ("max_length", C.c_uint32),
         ("zlib_flush_mode", C.c_int32), ("mtime", C.c_uint32), ("os", C.c_uint8), ("is_text", C.c_uint8),
         ("hcrc", C.c_uint8), ("lz77_level", C.c_uint8), ("extra", C.c_char_p), ("extra_len", C.c_uint32),
+        ("block_merge", C.c_uint32),     # (in what was padding: sizeof stays 72)
         ("filename", C.c_char_p), ("comment", C.c_char_p),
     ]
 
@@ -324,6 +325,7 @@ def lib():
                                              C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lfx_debug_symbols.argtypes = [u32, u32, vp]
     L.lfx_debug_block_choices.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lfx_debug_block_merges.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = L
     return L
 

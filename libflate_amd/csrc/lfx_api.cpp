@@ -865,6 +865,19 @@ extern "C" int lfx_debug_block_choices(lfx_ctx *cc, uint8_t *out, size_t max_blo
     if (n) HIP_TRY(hipMemcpy(out, c->d_choice.p, n, hipMemcpyDeviceToHost));
     return LFX_OK;
 } LFX_ABI_CATCH
+// the block every block of the context's last encode_prepare ended up in (block_merge)
+extern "C" int lfx_debug_block_merges(lfx_ctx *cc, uint32_t *out, size_t max_blocks, size_t *n_blocks) try {
+    if (!cc || !n_blocks) return LFX_E_ARG;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    (void)hipSetDevice(c->device);
+    *n_blocks = c->n_merges;
+    const size_t n = std::min<size_t>(c->n_merges, max_blocks);
+    if (n && !out) return LFX_E_ARG;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n) HIP_TRY(hipMemcpy(out, c->d_merge.p, 4 * n, hipMemcpyDeviceToHost));
+    return LFX_OK;
+} LFX_ABI_CATCH
 extern "C" void lfx_debug_symbols(uint32_t length, uint32_t distance, uint32_t *out6) {
     out6[0] = len_symbol(length, out6[1], out6[2]);
     out6[3] = dist_symbol(distance, out6[4], out6[5]);

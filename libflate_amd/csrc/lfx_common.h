@@ -12,6 +12,9 @@ namespace lfx {
 
 // DEFLATE block types (reference src/deflate/mod.rs:34-39)
 enum : uint32_t { BT_RAW = 0, BT_FIXED = 1, BT_DYNAMIC = 2 };
+// block_merge, in the DEVICE's block table only: a block whose code words went into the block in front of it.
+// It has no bits and no header; no chunk points at it.  (3 is DEFLATE's reserved BTYPE: no plan and no stream ever holds it.)
+enum : uint32_t { BT_ABSORBED = 3 };
 
 constexpr uint32_t MAX_WINDOW = 32768;  // libflate_lz77/src/lib.rs:21-24
 constexpr uint32_t MAX_LENGTH = 258;    // lib.rs:18

@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include "lfx_hostio.h"
+#include "lfx_merge.h"
 
 namespace lfx {
 
@@ -107,6 +108,14 @@ struct Ctx {
     // test hook lfx_debug_block_choices alone, no encode path looks at either.
     DevBuf d_choice;
     uint32_t n_choices = 0;
+    // an encode with block_merge: the regions block_merge_kernel works on, and for every block of the plan the
+    // block its code words ended up in.  Sized only by calls of that kind; the host vectors outlive the asynchronous uploads
+    // (every encode entry point synchronises before it returns).  n_merges: the entries of d_merge of the last prepare (0: that
+    // call was not one) — read by the test hook lfx_debug_block_merges alone.
+    DevBuf d_merge_regions, d_merge;
+    std::vector<MergeRegion> merge_regions;
+    std::vector<uint32_t> merge_ident;
+    uint32_t n_merges = 0;
     // an encode that packs by chunk: 320 symbol counters per chunk, and every chunk's packed size and first bit
     // (16 bytes).  Sized only by calls of that kind.
     DevBuf d_hist_chunk, d_chunk_bits;
@@ -132,7 +141,8 @@ struct Ctx {
                 &d_tile_bits, &d_tile_start, &d_ck, &d_res, &d_small, &d_hdr, &d_io_in, &d_io_out, &d_vis, &d_segtmp, &d_stage, &d_chunkmap, &d_glnk, &d_ucount,
                 &d_dec_streams, &d_dec_state, &d_dec_tmp, &d_dec_cand, &d_dec_blocks, &d_dec_tabs, &d_dec_sym, &d_dec_win, &d_dec_maps,
                 &d_dec_temp, &d_dec_lanesx, &d_idx_tasks, &d_idx_probe, &d_idx_stage, &d_idx_enc,
-                &d_bgzf_meta, &d_bgzf_tasks, &d_bgzf_scratch, &d_bgzf_pack, &d_dict_items, &d_cd2, &d_chain_items, &d_len, &d_choice, &d_hist_chunk, &d_chunk_bits};
+                &d_bgzf_meta, &d_bgzf_tasks, &d_bgzf_scratch, &d_bgzf_pack, &d_dict_items, &d_cd2, &d_chain_items, &d_len, &d_choice, &d_hist_chunk, &d_chunk_bits,
+                &d_merge_regions, &d_merge};
     }
     void *h_res = nullptr;  // pinned, 4 KiB (+ the arena below)
     // Small transfers of the decode paths (job lists up, scan results and counters down) go through page-locked memory: a

@@ -80,6 +80,12 @@ int launch_huffman(hipStream_t st, const BlockDesc *blocks, uint32_t nblocks, co
 // stored_ok — stored form; choice[b] = the type block b leaves with
 int launch_block_choose(hipStream_t st, BlockDesc *blocks, uint32_t nblocks, const uint32_t *hist, BlockCodes *bc, bool stored_ok,
                         uint8_t *choice);
+// block_merge, behind launch_huffman: one workgroup per region (merge_regions, lfx_merge.h) joins neighbouring
+// dynamic blocks where one code is no longer than two and rewrites the device's block, chunk, code-count and counter tables;
+// merge_head[b] = the block candidate b ends up in (the caller presets the identity).  launch_huffman runs again behind it.
+struct MergeRegion;
+int launch_block_merge(hipStream_t st, const MergeRegion *regions, uint32_t nregions, BlockDesc *blocks, ChunkDesc *chunks,
+                       uint32_t *ncodes, uint32_t *hist, BlockCodes *bc, uint32_t *merge_head);
 int launch_offsets(hipStream_t st, const BlockDesc *blocks, uint32_t nblocks, const BlockCodes *bc,
                    uint64_t start_bit, uint64_t cap_bits, uint64_t *block_start, EncodeResult *res);
 int launch_offsets_batch(hipStream_t st, const BatchStream *streams, uint32_t count, const BlockDesc *blocks, const BlockCodes *bc,

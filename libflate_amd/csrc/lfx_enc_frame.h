@@ -122,6 +122,7 @@ struct EncodeSpec {
     bool tuned = false;           // LFX_LZ77_LEVEL (§23): chain_depth and lazy come from the level, and the chain stage runs its tuned instances with ...
     LevelTune tune{0, false, 0, 0, 0};   // ... this (tune.depth == chain_depth, tune.lazy == lazy); all 0 for any other kind
     bool auto_blocks = false;     // LFX_HUFFMAN_AUTO (§22): every dynamic block's form chosen on the device; never under no_compression
+    bool merge_blocks = false;    // block_merge (§24): neighbouring dynamic blocks joined on the device; never under no_compression or fixed codes
 };
 // → LFX_OK, or LFX_E_ARG for options outside the domain.  *out is filled either way (lfx_encode_index_device asks
 // encode_served before it answers for the domain).
@@ -136,6 +137,7 @@ inline int encode_spec(int format, const lfx_encode_opts *o, EncodeSpec *out) {
     out->chain_depth = lz77_chained(kind) ? ((uint32_t)d.lz77_kind >> 8) & 0xFFu : out->tune.depth;
     out->lazy = kind == LFX_LZ77_LAZY || out->tune.lazy;
     out->auto_blocks = d.dynamic_huffman == LFX_HUFFMAN_AUTO && !d.no_compression;
+    out->merge_blocks = d.block_merge == 1 && d.dynamic_huffman != 0 && !d.no_compression;
     PlanOpts &p = out->plan;
     p.block_size = d.block_size;
     p.dynamic_huffman = d.dynamic_huffman != 0;
@@ -147,6 +149,7 @@ inline int encode_spec(int format, const lfx_encode_opts *o, EncodeSpec *out) {
     if (d.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
     if (d.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
     if (lz77_chain_stage(kind) && (out->chain_depth == 0 || ((uint32_t)d.lz77_kind >> 16) != 0)) return LFX_E_ARG;
+    if (d.block_merge > 1) return LFX_E_ARG;
     return LFX_OK;
 }
 
@@ -163,6 +166,11 @@ inline int encode_served(EncodeEntry e, const EncodeSpec &sp, DictKind dict, con
          : e == ENC_SHARD && chained ? (sp.lazy ? "lz77_kind: the N-GPU encode does not serve LFX_LZ77_LAZY" : "lz77_kind: the N-GPU encode does not serve LFX_LZ77_CHAIN")
          : e == ENC_SHARD && sp.auto_blocks ? "dynamic_huffman: the N-GPU encode does not serve LFX_HUFFMAN_AUTO (a stored block's size depends on the bit phase)"
          : e == ENC_INDEX && sp.auto_blocks ? "dynamic_huffman: lfx_encode_index_device does not serve LFX_HUFFMAN_AUTO (the candidates are laid out from the host plan's block types)"
+         // block_merge (§24): the entry points that read the host plan's blocks behind the Huffman stage, or promise a block boundary
+         : e == ENC_SHARD && sp.merge_blocks ? "block_merge: the N-GPU encode does not serve block_merge (a shard's blocks are laid out from the host plan)"
+         : e == ENC_INDEX && sp.merge_blocks ? "block_merge: lfx_encode_index_device does not serve block_merge (the candidates are laid out from the host plan's blocks)"
+         : e == ENC_MEMBERS && sp.merge_blocks ? "block_merge: lfx_encode_members_* does not serve block_merge (a member's blocks are laid out from the host plan)"
+         : e == ENC_STREAM && sp.merge_blocks ? "block_merge: the stream encoder does not serve block_merge (a merge across a flush would break what a flush promises)"
          // ChainLz77Encoder and LazyLz77Encoder have no chain behind a plain dictionary's candidate (§19); a chain dictionary brings its own
          : dict == DICT_PLAIN && level ? "lz77_kind: LFX_LZ77_LEVEL with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"
          : dict == DICT_PLAIN && chained ? (sp.lazy ? "lz77_kind: LFX_LZ77_LAZY with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"

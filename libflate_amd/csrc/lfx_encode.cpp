@@ -68,8 +68,9 @@ struct EncCall {
     bool tuned;                   // LFX_LZ77_LEVEL (§23): the chain stage's tuned instances, with ...
     LevelTune tune;               // ... the level's nice, max_lazy and too_far (chain_depth and lazy above are the level's too)
     bool auto_blocks;             // LFX_HUFFMAN_AUTO (§22): block_choose_kernel behind the Huffman kernel; any other call: no launch, no buffer
+    bool merge_blocks;            // block_merge (§24): block_merge_kernel and a second Huffman pass behind the first; any other call: no launch, no buffer
     EncodeGeom g;
-    bool pack_by_chunk = false;   // the geometry's flag, and nothing behind the Huffman stage rewrites the blocks' codes (LFX_HUFFMAN_AUTO) or reads tile starts (the encode index)
+    bool pack_by_chunk = false;   // the geometry's flag, and nothing behind the Huffman stage rewrites the blocks' codes (LFX_HUFFMAN_AUTO), joins blocks (block_merge) or reads tile starts (the encode index)
     uint64_t nspans = 0;          // partial results of the checksum kernels
     bool forked = false;          // the first half of the checksum's sweep is on the side stream already
     EncView v{};
@@ -187,6 +188,11 @@ int reserve_scratch(Ctx *c, EncCall &k) {
     if ((rc = c->d_bc.reserve(sizeof(BlockCodes) * std::max<size_t>(nblocks, 1)))) return rc;
     if ((rc = c->d_block_start.reserve(8 * std::max<size_t>(nblocks, 1)))) return rc;
     if (k.auto_blocks && (rc = c->d_choice.reserve(std::max<size_t>(nblocks, 1)))) return rc;   // LFX_HUFFMAN_AUTO: the chosen type per block
+    if (k.merge_blocks) {                                                                      // block_merge: the regions, and every block's head
+        merge_regions(plan.blocks, c->merge_regions);
+        if ((rc = c->d_merge_regions.reserve(sizeof(MergeRegion) * std::max<size_t>(c->merge_regions.size(), 1)))) return rc;
+        if ((rc = c->d_merge.reserve(4 * std::max<size_t>(nblocks, 1)))) return rc;
+    }
     if ((rc = c->d_tile_bits.reserve(4 * std::max<uint64_t>(plan.n_tiles, 1)))) return rc;
     if ((rc = c->d_tile_start.reserve(8 * std::max<uint64_t>(plan.n_tiles, 1)))) return rc;
     k.nspans = ck_nspans(n);
@@ -440,6 +446,29 @@ int stage_huffman(Ctx *c, const EncCall &k) {
         LAUNCH_TRY(launch_huffman(st, v.blocks, c->cur_nblocks, v.hist, (BlockCodes *)c->d_bc.p, v.mdbg ? v.mdbg + 512 : nullptr));
     c->phase("huffman");
     if (v.mdbg) dbg_huffman(k);
+    if (k.merge_blocks) {
+        // block_merge: the first pass left every candidate's exact dynamic size in bc[].body_bits.  The merge
+        // kernel rewrites the device's block AND chunk tables (and the code counts and counter rows, which every call makes
+        // anew): neither equals its shadow any more, the next prepare uploads both, whatever its plan — a pass repeated by
+        // with_match_fallback included.  The second pass builds the codes of the blocks that are left; absorbed ones are skipped.
+        c->merge_ident.resize(c->cur_nblocks);
+        for (uint32_t b = 0; b < c->cur_nblocks; b++) c->merge_ident[b] = b;
+        if (c->cur_nblocks) HIP_TRY(hipMemcpyAsync(c->d_merge.p, c->merge_ident.data(), 4ull * c->cur_nblocks, hipMemcpyHostToDevice, st));
+        c->n_merges = c->cur_nblocks;
+        if (!c->merge_regions.empty()) {
+            HIP_TRY(hipMemcpyAsync(c->d_merge_regions.p, c->merge_regions.data(), sizeof(MergeRegion) * c->merge_regions.size(),
+                                   hipMemcpyHostToDevice, st));
+            LAUNCH_TRY(launch_block_merge(st, (const MergeRegion *)c->d_merge_regions.p, (uint32_t)c->merge_regions.size(),
+                                          (BlockDesc *)c->d_blocks.p, (ChunkDesc *)c->d_chunks.p, v.ncodes, v.hist, (BlockCodes *)c->d_bc.p,
+                                          (uint32_t *)c->d_merge.p));
+            c->up_dev[0] = 0;
+            c->up_dev[1] = 0;
+        }
+        c->phase("block_merge");
+        if (!c->merge_regions.empty())
+            LAUNCH_TRY(launch_huffman(st, v.blocks, c->cur_nblocks, v.hist, (BlockCodes *)c->d_bc.p, nullptr));
+        c->phase("huffman_merged");
+    }
     if (k.auto_blocks) {
         // LFX_HUFFMAN_AUTO: in front of everything that reads a block's size or type — tile_bits, the offset
         // folds, the members' sizes.  Stored is a candidate only where the blocks have input bytes behind them (not for a
@@ -463,10 +492,10 @@ int encode_prepare(Ctx *c, const Plan &plan, const EncodeSpec &sp, const uint8_t
     c->phase("start");
     EncCall k{plan, sp.plan, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
               hc ? 0u : sp.chain_depth,     // (a caller's own code words switch the chain stage off)
-              sp.lazy, sp.tuned, sp.tune, sp.auto_blocks,
+              sp.lazy, sp.tuned, sp.tune, sp.auto_blocks, sp.merge_blocks,
               encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate, c->diag.pack_by_chunk)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
-    k.pack_by_chunk = k.g.pack_by_chunk && !k.auto_blocks && !c->idx_enc;
+    k.pack_by_chunk = k.g.pack_by_chunk && !k.auto_blocks && !k.merge_blocks && !c->idx_enc;
     c->cur_pack_by_chunk = k.pack_by_chunk;
     if (c->force_match_v1 && !hc) c->match_fallbacks++;      // (a silent fallback must be visible)
     c->cur_nchunks = (uint32_t)plan.chunks.size();
@@ -475,6 +504,7 @@ int encode_prepare(Ctx *c, const Plan &plan, const EncodeSpec &sp, const uint8_t
     c->cur_n = n;
     c->cur_in = d_in;
     c->n_choices = 0;
+    c->n_merges = 0;
     int rc;
     if ((rc = reserve_scratch(c, k))) return rc;
     if ((rc = upload_tables(c, k))) return rc;

@@ -19,6 +19,7 @@
 #include "lfx_common.h"
 #include "lfx_device.h"
 #include "lfx_huff.h"
+#include "lfx_merge_tree.h"
 
 namespace lfx {
 
@@ -453,7 +454,7 @@ __global__ __launch_bounds__(HUFF_THREADS) void huffman_kernel(const BlockDesc *
     __shared__ HuffScratch S;
     const uint32_t b = blockIdx.x;
     const uint32_t type = blocks[b].type;
-    if (type == BT_RAW) return;
+    if (type == BT_RAW || type == BT_ABSORBED) return;
     huff_block_build(hist + (uint64_t)b * HIST_STRIDE, type, &bc[b], S, (int)threadIdx.x, HUFF_THREADS);
     if (dbg && b == 0 && threadIdx.x < 24) dbg[threadIdx.x] = S.stamp[threadIdx.x];   // (LFX_DEBUG)
 }
@@ -471,7 +472,7 @@ __global__ __launch_bounds__(HUFF_THREADS) void huffman_chunk_kernel(const Block
     __shared__ uint32_t s_hist[SYM_ROW];
     const uint32_t b = blockIdx.x;
     const BlockDesc bd = blocks[b];
-    if (bd.type == BT_RAW) return;
+    if (bd.type == BT_RAW || bd.type == BT_ABSORBED) return;
     const uint32_t *rows = hist_chunk + (uint64_t)bd.first_chunk * SYM_ROW;
     sym_rows_sum(rows, bd.n_chunks, s_hist, (int)threadIdx.x, HUFF_THREADS);
     __syncthreads();
@@ -544,6 +545,68 @@ __global__ __launch_bounds__(64) void block_choose_kernel(BlockDesc *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
+// block_merge (include/lfx.h): behind huffman_kernel — every candidate's exact dynamic size D is in
+// bc[].body_bits — one workgroup per region of up to MERGE_MAX consecutive candidates (merge_regions, lfx_merge.h) takes the
+// region's symbol counts into LDS, decides the fixed binary tree over them (merge_tree: every node's D is huff_block_build over
+// the summed counts, the Huffman kernel's own source) and rewrites the device's tables for every group of more than one
+// candidate:
+//   - the head's BlockDesc covers the group (n_chunks, in_len; BFINAL and the alignment of the last candidate), its counter row
+//     is the group's sum with one EndOfBlock;
+//   - every other candidate becomes BT_ABSORBED: no bits, no header, no chunk;
+//   - the group's chunks point at the head; the last chunk of every candidate but the group's last loses CH_LAST_IN_BLOCK and
+//     its trailing EndOfBlock (one code word less).
+// The nodes of a region are built one after the other by all lanes of the workgroup: huff_block_build's barriers are the
+// workgroup's, and its scratch is 32 KB of LDS per build.  bc[first candidate] serves as the scratch slot for the nodes' codes:
+// huffman_kernel runs again over the rewritten table.  merge_head[b] = the block that candidate b's code words end up in.  No
+// workgroup reads what another writes; no global atomics.
+__global__ __launch_bounds__(HUFF_THREADS) void block_merge_kernel(const MergeRegion *__restrict__ regions, BlockDesc *__restrict__ blocks,
+                                                                   ChunkDesc *__restrict__ chunks, uint32_t *__restrict__ ncodes,
+                                                                   uint32_t *__restrict__ hist, BlockCodes *__restrict__ bc,
+                                                                   uint32_t *__restrict__ merge_head) {
+    __shared__ HuffScratch S;
+    __shared__ MergeScratch M;
+    __shared__ BlockDesc s_bd[MERGE_MAX];
+    const MergeRegion rg = regions[blockIdx.x];
+    const uint32_t n = min(rg.n, MERGE_MAX), b0 = rg.first_block, tid = threadIdx.x;
+    for (uint32_t i = tid; i < n * SYM_ROW; i += HUFF_THREADS) M.rows[i] = hist[(uint64_t)b0 * HIST_STRIDE + i];
+    if (tid < n) { M.D[tid] = bc[b0 + tid].body_bits; s_bd[tid] = blocks[b0 + tid]; }
+    __syncthreads();
+    merge_tree(M, n, &bc[b0], S, (int)tid, HUFF_THREADS);
+    // (merge_tree ends with a barrier)  the groups: candidate i is a head when head[i] == i, its group runs to the next head
+    for (uint32_t i = 0; i < n; i++) {                   // (uniform)
+        const uint32_t h = M.head[i];
+        if (tid == 0) merge_head[b0 + i] = b0 + h;
+        const bool last_of_group = i + 1 == n || M.head[i + 1] == i + 1;
+        if (h == i && last_of_group) continue;           // a group of one: the tables stay as they are
+        const BlockDesc bd = s_bd[i];
+        if (h != i)
+            for (uint32_t c = tid; c < bd.n_chunks; c += HUFF_THREADS) chunks[bd.first_chunk + c].block = b0 + h;
+        if (tid == 0) {
+            if (!last_of_group && bd.n_chunks) {         // an interior EndOfBlock: the last code word of the block's last chunk
+                const uint32_t c = bd.first_chunk + bd.n_chunks - 1;
+                chunks[c].flags &= ~(uint32_t)CH_LAST_IN_BLOCK;
+                ncodes[c] -= 1;
+            }
+            if (h != i) {
+                BlockDesc a = bd;
+                a.type = BT_ABSORBED; a.n_chunks = 0; a.in_len = 0; a.final = 0; a.align_after = 0;
+                blocks[b0 + i] = a;
+            } else {
+                uint32_t e = i + 1;
+                while (e < n && M.head[e] == i) e++;
+                BlockDesc g = bd;
+                for (uint32_t q = i + 1; q < e; q++) { g.n_chunks += s_bd[q].n_chunks; g.in_len += s_bd[q].in_len; }
+                g.final = s_bd[e - 1].final;
+                g.align_after = s_bd[e - 1].align_after;
+                blocks[b0 + i] = g;
+            }
+        }
+        if (h == i)
+            for (uint32_t q = tid; q < SYM_ROW; q += HUFF_THREADS) hist[(uint64_t)(b0 + i) * HIST_STRIDE + q] = M.rows[i * SYM_ROW + q];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // block start bits: a serial fold (stored blocks byte-align, the final block byte-aligns)
 __global__ __launch_bounds__(256) void offsets_kernel(const BlockDesc *__restrict__ blocks, uint32_t nblocks,
                                                       const BlockCodes *__restrict__ bc, uint64_t start_bit,
@@ -560,7 +623,7 @@ __global__ __launch_bounds__(256) void offsets_kernel(const BlockDesc *__restric
         if (b < nblocks) {
             const BlockDesc bd = blocks[b];
             s_kind[threadIdx.x] = (bd.type == BT_RAW ? 1u : 0u) | (bd.align_after ? 2u : 0u);
-            s_bits[threadIdx.x] = bd.type == BT_RAW ? 32 + 8 * bd.in_len : bc[b].body_bits;
+            s_bits[threadIdx.x] = bd.type == BT_RAW ? 32 + 8 * bd.in_len : bd.type == BT_ABSORBED ? 0ull : bc[b].body_bits;
         }
         const uint32_t cnt = min(256u, nblocks - b0);
         // Compressed blocks without an alignment behind them simply add up: when the round holds nothing else — except,
@@ -621,7 +684,7 @@ __global__ __launch_bounds__(256) void offsets_batch_kernel(const BatchStream *_
         const BlockDesc bd = blocks[b];
         block_start[b] = bit;
         if (bd.type == BT_RAW) { bit += 3; bit = (bit + 7) & ~7ull; bit += 32 + 8 * bd.in_len; }
-        else bit += bc[b].body_bits;
+        else if (bd.type != BT_ABSORBED) bit += bc[b].body_bits;
         if (bd.align_after) bit = (bit + 7) & ~7ull;
     }
     stream_end[s] = bit;
@@ -753,7 +816,7 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(const ChunkDesc *__rest
     __shared__ uint64_t carry;
     const uint32_t b = blockIdx.x;
     const BlockDesc bd = blocks[b];
-    if (bd.type == BT_RAW || bd.n_chunks == 0) return;
+    if (bd.type == BT_RAW || bd.type == BT_ABSORBED || bd.n_chunks == 0) return;
     const uint64_t t0 = chunks[bd.first_chunk].tile_base;
     const uint32_t lastc = bd.first_chunk + bd.n_chunks;
     const uint64_t t1 = lastc < nchunks ? chunks[lastc].tile_base : total_tiles;
@@ -969,6 +1032,7 @@ __global__ __launch_bounds__(256) void block_header_kernel(
     if (res->status != 0) return;
     const uint32_t b = blockIdx.x;
     const BlockDesc bd = blocks[b];
+    if (bd.type == BT_ABSORBED) return;                  // (block_merge: its code words lie in the block in front)
     const uint64_t start = block_start[b] - out_base_bit;
     // Block::flush encode.rs:291-292: 1 bit BFINAL then 2 bits BTYPE, LSB-first
     const uint32_t first3 = (bd.final & 1) | (bd.type << 1);
@@ -1412,6 +1476,13 @@ int launch_block_choose(hipStream_t st, BlockDesc *blocks, uint32_t nblocks, con
                         uint8_t *choice) {
     if (nblocks == 0) return 0;
     hipLaunchKernelGGL(block_choose_kernel, dim3(nblocks), dim3(64), 0, st, blocks, nblocks, hist, bc, stored_ok ? 1u : 0u, choice);
+    LFX_LAUNCH_CHECK();
+    return 0;
+}
+int launch_block_merge(hipStream_t st, const MergeRegion *regions, uint32_t nregions, BlockDesc *blocks, ChunkDesc *chunks,
+                       uint32_t *ncodes, uint32_t *hist, BlockCodes *bc, uint32_t *merge_head) {
+    if (nregions == 0) return 0;
+    hipLaunchKernelGGL(block_merge_kernel, dim3(nregions), dim3(HUFF_THREADS), 0, st, regions, blocks, chunks, ncodes, hist, bc, merge_head);
     LFX_LAUNCH_CHECK();
     return 0;
 }

@@ -116,7 +116,15 @@ extern "C" lfx_encoder *lfx_encoder_new(lfx_ctx *cc, int format, const lfx_encod
     const char *why;
     int rc = encode_spec(format, o, &sp);
     if (!rc) rc = encode_served(ENC_STREAM, sp, DICT_NONE, &why);
-    if (rc) { if (status) *status = rc; return nullptr; }
+    if (rc) {
+        if (rc == LFX_E_UNSUPPORTED) {           // (no handle to ask: the reason goes to the context, as for the one-shot calls)
+            Ctx *rc_ctx = reinterpret_cast<Ctx *>(cc);
+            std::lock_guard<std::recursive_mutex> lock(rc_ctx->mu);
+            rc_ctx->set_error(why);
+        }
+        if (status) *status = rc;
+        return nullptr;
+    }
     lfx_encoder *e = new lfx_encoder(format, sp);
     Ctx *c = e->backend.c = reinterpret_cast<Ctx *>(cc);
     e->backend.format = format;

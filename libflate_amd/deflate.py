@@ -51,6 +51,13 @@ class EncodeOptions:
         self._kw["dynamic_huffman"] = _ffi.HUFFMAN_AUTO
         return self
 
+    def merge_blocks(self):
+        """not a reference option (block_merge): neighbouring dynamic blocks are joined on the device wherever
+        one Huffman code for both is no longer than two — block_size becomes the smallest block; the LZ77 code words stay
+        those of the same options without it.  One-shot, batch and dictionary encodes; the stream encoder refuses it."""
+        self._kw["block_merge"] = 1
+        return self
+
     def _to_c(self):
         return _ffi.make_opts(**self._kw)
 
@@ -81,10 +88,12 @@ def _with_lz77(options, lz77, cls, level=None):
     return (options if options is not None else cls()).with_lz77(lz77)
 
 
-def _compress(fmt, data, zdict, options, context, lz77=None, level=None):
+def _compress(fmt, data, zdict, options, context, lz77=None, level=None, merge_blocks=False):
     from .context import Dictionary, default_context
     ctx = context if context is not None else default_context()
     options = _with_lz77(options, lz77, EncodeOptions, level)
+    if merge_blocks:
+        options = (options if options is not None else EncodeOptions()).merge_blocks()
     opts = options._to_c() if options is not None else None
     if zdict is None:
         return ctx.encode_host(fmt, data, opts)
@@ -100,13 +109,13 @@ def _compress(fmt, data, zdict, options, context, lz77=None, level=None):
             d.close()
 
 
-def compress(data, zdict=None, options=None, context=None, lz77=None, level=None):
+def compress(data, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False):
     """`data` as one raw DEFLATE stream, encoded in one call (one write_all + finish).  zdict: a preset dictionary, bytes or a
     libflate_amd.Dictionary — the stream then starts with the dictionary as history, what
     zlib.decompressobj(wbits=-15, zdict=...) reads (lfx_encode_dict_host).  lz77: an Lz77Encode of this package
     for the options, e.g. lz77.ChainLz77Encoder(8).  level: 1..9, shorthand for lz77=lz77.LevelLz77Encoder(level)
-    (DESIGN.md §23), exclusive with lz77."""
-    return _compress(_ffi.DEFLATE, data, zdict, options, context, lz77, level)
+    (DESIGN.md §23), exclusive with lz77.  merge_blocks=True: the options with merge_blocks()."""
+    return _compress(_ffi.DEFLATE, data, zdict, options, context, lz77, level, merge_blocks)
 
 
 class Decoder(_DecoderBase):

@@ -147,13 +147,14 @@ def list_members(data, context=None):
     return members
 
 
-def compress(data, options=None, context=None, lz77=None, level=None):
+def compress(data, options=None, context=None, lz77=None, level=None, merge_blocks=False):
     """`data` as one gzip member, encoded in one call (one write_all + finish; modification time 0 unless the options say
     otherwise).  lz77: an Lz77Encode of this package for the options, e.g. lz77.ChainLz77Encoder(8).  level:
-    1..9, shorthand for lz77=lz77.LevelLz77Encoder(level), exclusive with lz77."""
+    1..9, shorthand for lz77=lz77.LevelLz77Encoder(level), exclusive with lz77.  merge_blocks=True: the options
+    with merge_blocks()."""
     if options is None:
         options = EncodeOptions()
-    return _deflate._compress(_ffi.GZIP, data, None, options, context, lz77, level)
+    return _deflate._compress(_ffi.GZIP, data, None, options, context, lz77, level, merge_blocks)
 
 
 def encode_members(data, member_size=1 << 20, bgzf=False, options=None, context=None, lz77=None):

@@ -30,15 +30,16 @@ class Encoder(_EncoderBase):
         return cls(inner, options, context)
 
 
-def compress(data, zdict=None, options=None, context=None, lz77=None, level=None):
+def compress(data, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False):
     """`data` as one zlib stream, encoded in one call (one write_all + finish).  zdict: a preset dictionary, bytes or a
     libflate_amd.Dictionary — the stream then carries FDICT and the dictionary's id, what zlib.decompressobj(zdict=...)
     reads (lfx_encode_dict_host).  lz77: an Lz77Encode of this package for the options, e.g.
     lz77.ChainLz77Encoder(8).  level: 1..9, shorthand for lz77=lz77.LevelLz77Encoder(level),
-    exclusive with lz77; with zdict as bytes the dictionary is made with a chain of its own, as for a chained lz77."""
-    if (lz77 is not None or level is not None) and options is None:
+    exclusive with lz77; with zdict as bytes the dictionary is made with a chain of its own, as for a chained lz77.
+    merge_blocks=True: the options with merge_blocks()."""
+    if (lz77 is not None or level is not None or merge_blocks) and options is None:
         options = EncodeOptions()
-    return _deflate._compress(_ffi.ZLIB, data, zdict, options, context, lz77, level)
+    return _deflate._compress(_ffi.ZLIB, data, zdict, options, context, lz77, level, merge_blocks)
 
 
 class Decoder(_DecoderBase):

@@ -17,6 +17,7 @@ where
     pub(crate) block_size: usize,
     pub(crate) dynamic_huffman: bool,
     pub(crate) auto_huffman: bool,     // LFX_HUFFMAN_AUTO (not a reference option): wins over dynamic_huffman
+    pub(crate) merge_blocks: bool,     // block_merge (not a reference option)
     pub(crate) lz77: Option<E>,        // None = stored blocks (encode.rs:77-80)
 }
 impl Default for EncodeOptions<DefaultLz77Encoder> {
@@ -25,7 +26,7 @@ impl Default for EncodeOptions<DefaultLz77Encoder> {
 impl EncodeOptions<DefaultLz77Encoder> {
     /// encode.rs:45-51
     pub fn new() -> Self {
-        EncodeOptions { block_size: DEFAULT_BLOCK_SIZE, dynamic_huffman: true, auto_huffman: false, lz77: Some(DefaultLz77Encoder::new()) }
+        EncodeOptions { block_size: DEFAULT_BLOCK_SIZE, dynamic_huffman: true, auto_huffman: false, merge_blocks: false, lz77: Some(DefaultLz77Encoder::new()) }
     }
 }
 impl<E> EncodeOptions<E>
@@ -33,7 +34,7 @@ where
     E: GpuLz77,
 {
     /// encode.rs:59-65
-    pub fn with_lz77(lz77: E) -> Self { EncodeOptions { block_size: DEFAULT_BLOCK_SIZE, dynamic_huffman: true, auto_huffman: false, lz77: Some(lz77) } }
+    pub fn with_lz77(lz77: E) -> Self { EncodeOptions { block_size: DEFAULT_BLOCK_SIZE, dynamic_huffman: true, auto_huffman: false, merge_blocks: false, lz77: Some(lz77) } }
     /// encode.rs:77-80
     pub fn no_compression(mut self) -> Self { self.lz77 = None; self }
     /// encode.rs:92-95
@@ -43,6 +44,10 @@ where
     /// Not a reference option (`LFX_HUFFMAN_AUTO`, include/lfx.h): every block in the smallest of its dynamic,
     /// fixed and stored form; the blocks and the LZ77 code words stay those of the default options.
     pub fn auto_huffman_codes(mut self) -> Self { self.dynamic_huffman = true; self.auto_huffman = true; self }
+    /// Not a reference option (`block_merge`, include/lfx.h): neighbouring dynamic blocks are joined on the
+    /// device wherever one Huffman code for both is no longer than two; the LZ77 code words stay as they are.  Served by the
+    /// one-shot, batch and dictionary encodes; an `Encoder` made from such options fails with `Unsupported`.
+    pub fn merge_blocks(mut self) -> Self { self.merge_blocks = true; self }
 
     /// → the C options and whether the whole path runs on the device for this `E` (else `E` runs on the caller's side)
     pub(crate) fn to_ffi(&self) -> (ffi::lfx_encode_opts, bool) {
@@ -50,6 +55,7 @@ where
         unsafe { ffi::lfx_encode_opts_default(&mut o) };
         o.block_size = self.block_size as u64;
         o.dynamic_huffman = if self.auto_huffman { ffi::LFX_HUFFMAN_AUTO } else { self.dynamic_huffman as i32 };
+        o.block_merge = self.merge_blocks as u32;
         let on_device = match self.lz77 {
             Some(ref e) => e.configure(&mut o),
             None => { o.no_compression = 1; true }      // RawBuf never calls the Lz77Encode (encode.rs:348-383)

@@ -62,6 +62,7 @@ pub struct lfx_encode_opts {
     pub lz77_level: u8,
     pub extra: *const u8,
     pub extra_len: u32,
+    pub block_merge: u32,      // 0: the plan's blocks; 1: neighbouring dynamic blocks joined (in what was padding: 72 bytes as before)
     pub filename: *const c_char,
     pub comment: *const c_char,
 }

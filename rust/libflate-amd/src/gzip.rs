@@ -140,6 +140,8 @@ impl<E: GpuLz77> EncodeOptions<E> {
     pub fn fixed_huffman_codes(mut self) -> Self { self.inner = self.inner.fixed_huffman_codes(); self }
     /// `LFX_HUFFMAN_AUTO`: see `deflate::EncodeOptions::auto_huffman_codes`
     pub fn auto_huffman_codes(mut self) -> Self { self.inner = self.inner.auto_huffman_codes(); self }
+    /// `block_merge`: see `deflate::EncodeOptions::merge_blocks`
+    pub fn merge_blocks(mut self) -> Self { self.inner = self.inner.merge_blocks(); self }
 }
 
 /// `gzip::Encoder<W, E>` (gzip.rs:754-908)
