@@ -800,7 +800,8 @@ int lfx_decoder_set_dict(lfx_decoder *d, const lfx_dict *dict);
  *  In the batch call every stream's first chunk is primed by the one dictionary, read in place; status, LFX_E_NOSPACE and the
  *  zero fill are lfx_encode_batch_device's.  lfx_encode_dict_bound = lfx_encode_bound + 4 (0 where that is 0).
  *  The first encode call that uses a dictionary builds its prefix table on the device and keeps it in the lfx_dict.
- *  Not covered: the stream encoder (lfx_encoder_*), the members encode, the encode-time index, the N-GPU encode, lfx_lz77. */
+ *  The stream encoder takes a dictionary through lfx_encoder_new_dict (below).
+ *  Not covered: the members encode, the encode-time index, the N-GPU encode, lfx_lz77. */
 uint64_t lfx_encode_dict_bound(uint64_t n, const lfx_encode_opts *o, const lfx_schedule *s);
 int lfx_encode_dict_device(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
                            const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len);
@@ -838,6 +839,40 @@ int lfx_encode_batch_dict_device(lfx_ctx *c, int format, const lfx_encode_opts *
  *  position — takes 64 KiB of device memory, and is built by the first chained encode that takes the dictionary, on the
  *  context's stream, and freed with the lfx_dict.  Nothing of a call stays in the context. */
 lfx_dict *lfx_dict_new_chain(lfx_ctx *c, const void *bytes, uint64_t len, int on_device, int *status);
+
+/* ---- the stream encoder with a preset dictionary: zlib's deflateSetDictionary on a z_stream, Python's
+ * zlib.compressobj(zdict=...) — the streams lfx_decoder_set_dict reads, written without knowing their length in advance.
+ * lfx_encoder_new with a dictionary.  It comes with the constructor, not with a set_dict call as for the decoder: a zlib
+ * encoder writes its header inside the constructor, and FDICT and DICTID are part of that header.  Every other lfx_encoder_*
+ * call takes the encoder as it takes one made by lfx_encoder_new.
+ *
+ *  1. dict == NULL: byte for byte lfx_encoder_new — status, messages and every byte the sink receives.
+ *  2. Formats: LFX_ZLIB and LFX_DEFLATE.  LFX_GZIP is LFX_E_ARG (gzip has no preset dictionary), whatever `dict` is.
+ *  3. A dictionary of another context is LFX_E_ARG.  A NULL context gives NULL with *status = LFX_E_DEVICE.
+ *  4. The dictionary must outlive the encoder.
+ *  5. Output.  The writes, flushes and the finish made on the encoder are its write schedule.  The bytes handed to the sink are
+ *     exactly what lfx_encode_dict_host writes for the concatenated input with that schedule, the same options and the same
+ *     dictionary: the stream's first LZ77 chunk is primed as defined above (§18; with a chain dictionary and the kinds 2, 3 and
+ *     4: §21), every later chunk is what the dictionary-less stream encoder makes of it.  "First chunk" is a property of the
+ *     stream, not of a batch of the encoder's: exactly one chunk is primed, whichever call closes its block and however the
+ *     encoder groups blocks into GPU passes.  As in the one-shot call, the first chunk is the first flush of the LZ77 stage: a
+ *     flush() before the first byte closes an empty block whose empty chunk is that first chunk — nothing behind it is primed —
+ *     while writes of no bytes cut nothing.  An empty dictionary primes nothing.
+ *  6. LFX_ZLIB: the header is CMF and FLEVEL as lfx_encoder_new writes them, FDICT set, FCHECK recomputed, then DICTID =
+ *     lfx_dict_id(dict) big-endian — six bytes, handed to the sink inside this call.  The trailer's Adler-32 covers the input only.
+ *  7. LFX_DEFLATE: the body alone.
+ *  8. no_compression and LFX_LZ77_NOCOMPRESSION: the zlib header still carries FDICT and DICTID, the code words are unchanged.
+ *  9. Served and refused (DESIGN.md §3.0, row `stream`): a dictionary made by lfx_dict_new with LFX_LZ77_CHAIN, LFX_LZ77_LAZY or
+ *     LFX_LZ77_LEVEL is LFX_E_UNSUPPORTED, one made by lfx_dict_new_chain is served; block_merge stays LFX_E_UNSUPPORTED for the
+ *     stream encoder, and its reason comes first; LFX_HUFFMAN_AUTO is served as without a dictionary.  The reason is
+ *     lfx_ctx_last_error's.
+ * 10. Codes mode (lfx_encoder_write_codes) is served: the header carries FDICT and DICTID, and the code words are
+ *     Huffman-coded as they come — the caller's Lz77Encode did its own priming, and a Pointer of the first block may reach in
+ *     front of byte 0 (the codes mode checks no distance against the position).  No match stage and no dictionary stage run.
+ *  Nothing of an encoder's dictionary stays in the context: a dictionary-less encoder on the same context, before or after,
+ *  launches what it launches without this call. */
+lfx_encoder *lfx_encoder_new_dict(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_dict *dict,
+                                  lfx_write_cb w, lfx_flush_cb f, void *user, int *status);
 
 /* ---- plug-in: libflate_lz77::Lz77Encode (libflate_lz77/src/lib.rs:83-107) -----------------
  * Codes are delivered in batches: word = (val << 16) | dist; dist == 0 → Code::Literal(val),

@@ -46,7 +46,7 @@ EXPORTS = [
     "lfx_dict_new", "lfx_dict_id", "lfx_dict_free", "lfx_decode_dict_device", "lfx_decode_dict_host",
     "lfx_decode_batch_dict_device", "lfx_decoder_set_dict",
     "lfx_encode_dict_bound", "lfx_encode_dict_device", "lfx_encode_dict_host", "lfx_encode_batch_dict_device",
-    "lfx_dict_new_chain",
+    "lfx_dict_new_chain", "lfx_encoder_new_dict",
 ]
 
 
@@ -268,6 +268,8 @@ def lib():
     L.lfx_container_header_len.argtypes = [i32, C.POINTER(EncodeOpts)]
     L.lfx_encoder_new.restype = vp
     L.lfx_encoder_new.argtypes = [vp, i32, C.POINTER(EncodeOpts), WRITE_CB, FLUSH_CB, vp, C.POINTER(i32)]
+    L.lfx_encoder_new_dict.restype = vp
+    L.lfx_encoder_new_dict.argtypes = [vp, i32, C.POINTER(EncodeOpts), vp, WRITE_CB, FLUSH_CB, vp, C.POINTER(i32)]
     L.lfx_encoder_write.restype = C.c_int64
     L.lfx_encoder_write.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.lfx_encoder_write_codes.argtypes = [vp, C.POINTER(u32), C.c_size_t, C.c_char_p, C.c_size_t, i32]

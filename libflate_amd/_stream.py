@@ -21,9 +21,13 @@ class StreamError(IOError):
 class _EncoderBase:
     FORMAT = _ffi.DEFLATE
 
-    def __init__(self, inner, options=None, context=None):
-        """`inner` is any object with write(bytes) (and optionally flush()) — the reference's `W`."""
+    def __init__(self, inner, options=None, context=None, zdict=None):
+        """`inner` is any object with write(bytes) (and optionally flush()) — the reference's `W`.  zdict (zlib / deflate): a
+        preset dictionary, bytes or a libflate_amd.Dictionary — what zlib.compressobj(zdict=...) takes (lfx_encoder_new_dict,
+        DESIGN.md §25).  From bytes the dictionary is made here, with a chain of its own when the options' parse is a chained
+        one (§21), and lives as long as the encoder; a caller's Dictionary is taken as it was made."""
         self._ctx = context or default_context()
+        self._zdict = None
         self._inner = inner
         self._opts = options._to_c() if options is not None else _ffi.make_opts()
         # a caller-supplied Lz77Encode (EncodeOptions::with_lz77(E), encode.rs:59-65) runs here; its codes go to the GPU
@@ -34,6 +38,25 @@ class _EncoderBase:
         self._wcb = _ffi.WRITE_CB(self._on_write)
         self._fcb = _ffi.FLUSH_CB(self._on_flush)
         st = C.c_int(0)
+        if zdict is not None:
+            if self.FORMAT == _ffi.GZIP:
+                raise StreamError(_ffi.E_ARG, "gzip has no preset dictionary")
+            own = not hasattr(zdict, "handle")
+            if own:
+                from .context import Dictionary
+                chained = (self._opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL)
+                zdict = Dictionary(zdict, self._ctx, chain=chained)
+            self._h = _ffi.lib().lfx_encoder_new_dict(self._ctx.handle, self.FORMAT, C.byref(self._opts), zdict.handle,
+                                                      self._wcb, self._fcb, None, C.byref(st))
+            if not self._h:
+                if own:
+                    zdict.close()
+                why = self._ctx.last_error() if st.value == _ffi.E_UNSUPPORTED else \
+                    "a dictionary of another context" if st.value == _ffi.E_ARG and zdict._ctx is not self._ctx else ""
+                raise StreamError(st.value, "encoder construction failed (status %d)%s" % (st.value, why and ": " + why))
+            self._zdict, self._zdict_own = zdict, own
+            self._ctx._retain()
+            return
         self._h = _ffi.lib().lfx_encoder_new(self._ctx.handle, self.FORMAT, C.byref(self._opts), self._wcb,
                                              self._fcb, None, C.byref(st))
         if not self._h:
@@ -122,6 +145,10 @@ class _EncoderBase:
             _ffi.lib().lfx_encoder_free(self._h)
             self._h = None
             self._ctx._release()
+            if self._zdict is not None:        # (only now: the encoder's batches read the dictionary)
+                if self._zdict_own:
+                    self._zdict.close()
+                self._zdict = None
 
     def __del__(self):
         self._free()

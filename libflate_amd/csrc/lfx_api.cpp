@@ -232,20 +232,13 @@ extern "C" int lfx_ctx_last_timing(lfx_ctx *cc, lfx_timing *t) try {
 
 // ------------------------------------------------------------------------------------------------
 // encode entry points: argument checks, the plan, then the encode core (lfx_encode.cpp)
-// A preset dictionary in the container and in the plan.  zlib: FDICT set, FCHECK recomputed, DICTID behind
-// the two header bytes (RFC 1950 2.2); raw DEFLATE: nothing.
-static void dict_header(int format, const lfx_dict *dict, std::vector<uint8_t> &hdr) {
-    if (format != LFX_ZLIB || hdr.size() != 2) return;
-    uint8_t flg = (uint8_t)((hdr[1] & 0xC0) | 0x20);
-    const uint32_t check = ((uint32_t)hdr[0] << 8) + flg;
-    if (check % 31 != 0) flg = (uint8_t)(flg + (31 - check % 31));
-    hdr[1] = flg;
-    for (int sh = 24; sh >= 0; sh -= 8) hdr.push_back((uint8_t)(dict->id >> sh));
-}
+// A preset dictionary in the container and in the plan: dict_header and dict_prime_first (lfx_enc_frame.h),
+// which the stream encoder writes and marks with as well.
+static void dict_header(int format, const lfx_dict *dict, std::vector<uint8_t> &hdr) { lfx::dict_header(format, dict->id, hdr); }
 // the stream's first LZ77 flush unit is the one the dictionary primes — where the options match at all and the dictionary
 // has bytes to offer
 static void dict_prime(const lfx_dict *dict, Plan &p) {
-    if (dict->usable && !p.chunks.empty() && !(p.chunks[0].flags & CH_LITERALS)) p.chunks[0].flags |= CH_DICT;
+    if (dict->usable) (void)dict_prime_first(p);
 }
 
 static int encode_device_impl(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,

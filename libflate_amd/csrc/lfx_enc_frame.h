@@ -231,4 +231,22 @@ inline int container_header(int format, const lfx_encode_opts &o, std::vector<ui
     return LFX_OK;
 }
 
+// A preset dictionary in the container and in the plan (the stream encoder: §25).  zlib: FDICT set, FCHECK
+// recomputed, DICTID behind the two header bytes (RFC 1950 2.2); raw DEFLATE: nothing.  hdr: what container_header wrote.
+inline void dict_header(int format, uint32_t dict_id, std::vector<uint8_t> &hdr) {
+    if (format != LFX_ZLIB || hdr.size() != 2) return;
+    uint8_t flg = (uint8_t)((hdr[1] & 0xC0) | 0x20);
+    const uint32_t check = ((uint32_t)hdr[0] << 8) + flg;
+    if (check % 31 != 0) flg = (uint8_t)(flg + (31 - check % 31));
+    hdr[1] = flg;
+    for (int sh = 24; sh >= 0; sh -= 8) hdr.push_back((uint8_t)(dict_id >> sh));
+}
+// p: a plan that starts with a stream's first LZ77 flush unit, the one a dictionary with bytes to offer primes — where the
+// options match at all.  → whether a chunk was marked
+inline bool dict_prime_first(Plan &p) {
+    if (p.chunks.empty() || (p.chunks[0].flags & CH_LITERALS)) return false;
+    p.chunks[0].flags |= CH_DICT;
+    return true;
+}
+
 }  // namespace lfx

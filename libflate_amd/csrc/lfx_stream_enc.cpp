@@ -21,6 +21,7 @@ struct GpuBatches {
     Ctx *c = nullptr;
     int format = 0;
     const EncodeSpec *spec = nullptr;   // the encoder's (StreamEnc::spec)
+    const lfx_dict *dict = nullptr;     // the encoder's preset dictionary (lfx_encoder_new_dict): for the batch that is `primed`, no other
     DevBuf d_in, d_out;
     PinVec h_out;                       // a batch's output lands here (page-locked) and goes to the sink from here: no copy between
     PinVec h_res;                       // result slot + the shared byte
@@ -32,7 +33,8 @@ struct GpuBatches {
     int encode(EncodeResult *res, EncodeResult *async_slot, std::string &err) {
         const uint8_t prefix[1] = {cur.carry};
         const HostCodes hc{cur.codes, cur.n_codes, cur.chunk_codes};
-        int rc = encode_prepare(c, cur.plan, *spec, (const uint8_t *)d_in.p, cur.n, ck_mode_of(format), cur.coded ? &hc : nullptr);
+        int rc = encode_prepare(c, cur.plan, *spec, (const uint8_t *)d_in.p, cur.n, ck_mode_of(format), cur.coded ? &hc : nullptr,
+                                cur.primed ? dict : nullptr);
         if (!rc) rc = encode_emit(c, LFX_DEFLATE, false, 0, true, 0, prefix, cur.carry_bits ? 1 : 0, cur.carry_bits, (uint8_t *)d_out.p,
                                   cur.bound & ~3ull, res, async_slot);
         if (rc) err = c->err;
@@ -109,13 +111,15 @@ struct lfx_encoder : StreamEnc<PinVec, GpuBatches> {
 };
 
 extern "C" void lfx_encoder_free(lfx_encoder *e);
-extern "C" lfx_encoder *lfx_encoder_new(lfx_ctx *cc, int format, const lfx_encode_opts *o, lfx_write_cb w,
-                                        lfx_flush_cb f, void *user, int *status) try {
+// lfx_encoder_new and lfx_encoder_new_dict behind their argument checks.  dict == nullptr: the dictionary-less encoder, which
+// asks the table with DICT_NONE, writes container_header's bytes and never marks a chunk.
+static lfx_encoder *encoder_new(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_dict *dict, lfx_write_cb w,
+                                lfx_flush_cb f, void *user, int *status) {
     if (!cc || !w) { if (status) *status = cc ? LFX_E_ARG : LFX_E_DEVICE; return nullptr; }
     EncodeSpec sp;
     const char *why;
     int rc = encode_spec(format, o, &sp);
-    if (!rc) rc = encode_served(ENC_STREAM, sp, DICT_NONE, &why);
+    if (!rc) rc = encode_served(ENC_STREAM, sp, !dict ? DICT_NONE : dict->chain ? DICT_CHAIN : DICT_PLAIN, &why);
     if (rc) {
         if (rc == LFX_E_UNSUPPORTED) {           // (no handle to ask: the reason goes to the context, as for the one-shot calls)
             Ctx *rc_ctx = reinterpret_cast<Ctx *>(cc);
@@ -129,6 +133,10 @@ extern "C" lfx_encoder *lfx_encoder_new(lfx_ctx *cc, int format, const lfx_encod
     Ctx *c = e->backend.c = reinterpret_cast<Ctx *>(cc);
     e->backend.format = format;
     e->backend.spec = &e->spec;
+    if (dict) {
+        e->backend.dict = dict;
+        e->set_dict(dict, dict->id, dict->usable != 0);
+    }
     if (c->diag.enc_batch_mb > 0) e->pol.batch_bytes = (uint64_t)c->diag.enc_batch_mb << 20;
     // (page-locked and device buffers of an earlier encoder of this context, when there are any)
     e->pending = c->take_pin();
@@ -143,6 +151,21 @@ extern "C" lfx_encoder *lfx_encoder_new(lfx_ctx *cc, int format, const lfx_encod
     if (rc) { if (status) *status = rc; lfx_encoder_free(e); return nullptr; }
     if (status) *status = LFX_OK;
     return e;
+}
+extern "C" lfx_encoder *lfx_encoder_new(lfx_ctx *cc, int format, const lfx_encode_opts *o, lfx_write_cb w,
+                                        lfx_flush_cb f, void *user, int *status) try {
+    return encoder_new(cc, format, o, nullptr, w, f, user, status);
+} LFX_ABI_CATCH_NEW
+//  the dictionary comes with the constructor: the zlib header — FDICT, DICTID — is written in it
+extern "C" lfx_encoder *lfx_encoder_new_dict(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_dict *dict,
+                                             lfx_write_cb w, lfx_flush_cb f, void *user, int *status) try {
+    if (format == LFX_GZIP) { if (status) *status = LFX_E_ARG; return nullptr; }      // (gzip has no preset dictionary)
+    if (!cc) { if (status) *status = LFX_E_DEVICE; return nullptr; }
+    if (dict && (dict->c != reinterpret_cast<Ctx *>(cc) || (format != LFX_ZLIB && format != LFX_DEFLATE))) {
+        if (status) *status = LFX_E_ARG;
+        return nullptr;
+    }
+    return encoder_new(cc, format, o, dict, w, f, user, status);
 } LFX_ABI_CATCH_NEW
 
 extern "C" int64_t lfx_encoder_write(lfx_encoder *e, const uint8_t *p, size_t n) try {

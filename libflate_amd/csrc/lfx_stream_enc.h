@@ -91,6 +91,9 @@ struct EncBatch {
     const uint32_t *codes = nullptr;          // n_codes words, every block's EndOfBlock included ...
     uint64_t n_codes = 0;
     const uint32_t *chunk_codes = nullptr;    // ... and how many of them each chunk of the plan holds
+    // an encoder made with a preset dictionary: plan.chunks[0] is the stream's first chunk and carries CH_DICT —
+    // the backend gives the encoder's dictionary to this batch, every time it runs it, and to no other
+    bool primed = false;
 };
 // what collect() reports of the batch
 struct EncDone {
@@ -138,6 +141,12 @@ struct StreamEnc {
     std::vector<uint32_t> chunk_codes;   // of the batch in flight
     uint64_t closed_codes = 0, open_codes = 0;
     bool final_closed = false;
+    // ---- a preset dictionary (set_dict, before enc_open).  Opaque here: the backend knows what it points to.
+    const void *dict = nullptr;
+    uint32_t dict_id = 1;                // RFC 1950's DICTID, for the zlib header
+    bool dict_usable = false;            // it has bytes to offer: the stream's first chunk is primed
+    bool first_chunk_handed = false;     // the stream's first chunk has been handed to a batch (a property of the stream, not of a batch)
+    void set_dict(const void *d, uint32_t id, bool usable) { dict = d; dict_id = id; dict_usable = usable; }
 
     // sp: what encode_spec(format_, ...) resolved
     StreamEnc(int format_, const EncodeSpec &sp) : format(format_), spec(sp), pl(spec.plan) {
@@ -243,6 +252,12 @@ EncBatch enc_next_batch(E *e, bool final) {
     b.plan = final ? std::move(e->pl.plan()) : e->pl.take_closed();
     b.final = final;
     b.bound = bytes_bound(b.n, b.plan.blocks.size());
+    // the stream's first chunk, whichever batch it lands in (stored blocks have none; an empty chunk — a flush before the first
+    // byte — is the first chunk, as it is the first flush of the Lz77Encode): that one is primed, and no later one
+    if (e->dict && !e->first_chunk_handed && !b.plan.chunks.empty()) {
+        e->first_chunk_handed = true;
+        b.primed = e->dict_usable && dict_prime_first(b.plan);
+    }
     return b;
 }
 
@@ -274,6 +289,7 @@ template <class E>
 int enc_open(E *e) {
     std::vector<uint8_t> hdr;
     if (int rc = container_header(e->format, e->spec.o, hdr)) return rc;
+    if (e->dict) dict_header(e->format, e->dict_id, hdr);      // (the codes mode and stored blocks included: what the one-shot calls do)
     return enc_sink(e, hdr.data(), hdr.size());
 }
 

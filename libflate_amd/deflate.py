@@ -67,12 +67,15 @@ class Encoder(_EncoderBase):
     FORMAT = _ffi.DEFLATE
 
     @classmethod
-    def new(cls, inner, context=None):
-        return cls(inner, None, context)
+    def new(cls, inner, context=None, options=None, zdict=None):
+        """zdict: a preset dictionary, bytes or a libflate_amd.Dictionary (what zlib.compressobj(zdict=...) takes; DESIGN.md
+        §25).  options: EncodeOptions, e.g. EncodeOptions(lz77.LevelLz77Encoder(6)) — with zdict as bytes and a chained, lazy or
+        level parse the encoder makes the chain dictionary itself, as compress(data, zdict=bytes, level=6) does."""
+        return cls(inner, options, context, zdict)
 
     @classmethod
-    def with_options(cls, inner, options, context=None):
-        return cls(inner, options, context)
+    def with_options(cls, inner, options, context=None, zdict=None):
+        return cls(inner, options, context, zdict)
 
 
 def _with_lz77(options, lz77, cls, level=None):

@@ -89,6 +89,12 @@ impl<W: io::Write, E: GpuLz77> Encoder<W, E> {
         let (o, on_device) = options.to_ffi();
         Ok(Encoder { raw: RawEncoder::new(ffi::LFX_DEFLATE, &o, inner)?, stage: options.into_stage(on_device) })
     }
+    /// `try_with_options` with a preset dictionary (`deflateSetDictionary` on a raw stream; not a reference call): the
+    /// stream starts with the dictionary as history.  A chained, lazy or level parse needs a `Dictionary::with_chain`.
+    pub fn with_dictionary(inner: W, options: EncodeOptions<E>, dictionary: std::sync::Arc<crate::dict::Dictionary>) -> io::Result<Self> {
+        let (o, on_device) = options.to_ffi();
+        Ok(Encoder { raw: RawEncoder::new_dict(ffi::LFX_DEFLATE, &o, dictionary, inner)?, stage: options.into_stage(on_device) })
+    }
     pub fn finish(mut self) -> Finish<W, io::Error> {
         let closed = self.stage.close(&mut self.raw, 2);
         let (w, e) = self.raw.finish();

@@ -11,6 +11,7 @@
 //! There is no CPU fallback: without a usable GPU every constructor returns an `io::Error`.
 mod ffi;
 pub mod deflate;
+pub mod dict;
 pub mod gzip;
 pub mod lz77;
 pub mod non_blocking;
@@ -126,6 +127,7 @@ pub(crate) struct RawEncoder<W: io::Write> {
     pub(crate) h: *mut ffi::lfx_encoder,
     pub(crate) inner: Option<Box<W>>,    // boxed: the callbacks hold its address
     pub(crate) _ctx: Arc<Context>,
+    pub(crate) _dict: Option<Arc<dict::Dictionary>>,    // (the encoder's batches read it: it lives as long as the handle)
 }
 // (the handles are plain heap objects behind the C ABI and the context serialises every call: moving an encoder /
 //  decoder to another thread is sound whenever the inner stream may move — the reference's types are Send when W / R are)
@@ -144,7 +146,22 @@ impl<W: io::Write> RawEncoder<W> {
         if h.is_null() {
             return Err(io_error(st, format!("encoder construction failed: {}", ctx.last_error())));
         }
-        Ok(RawEncoder { h, inner: Some(inner), _ctx: ctx })
+        Ok(RawEncoder { h, inner: Some(inner), _ctx: ctx, _dict: None })
+    }
+    /// `lfx_encoder_new_dict`: the zlib header carries FDICT and the dictionary's id, the stream's first chunk
+    /// is primed by it
+    pub(crate) fn new_dict(format: c_int, opts: &ffi::lfx_encode_opts, dictionary: Arc<dict::Dictionary>, inner: W) -> io::Result<Self> {
+        let ctx = dictionary.ctx.clone();
+        let mut inner = Box::new(inner);
+        let mut st: c_int = 0;
+        let h = unsafe {
+            dict::lfx_encoder_new_dict(ctx.0, format, opts, dictionary.h, write_tramp::<W>, Some(flush_tramp::<W>),
+                                       &mut *inner as *mut W as *mut c_void, &mut st)
+        };
+        if h.is_null() {
+            return Err(io_error(st, format!("encoder construction failed: {}", ctx.last_error())));
+        }
+        Ok(RawEncoder { h, inner: Some(inner), _ctx: ctx, _dict: Some(dictionary) })
     }
     fn err(&self, st: c_int) -> io::Error {
         io_error(st, unsafe { CStr::from_ptr(ffi::lfx_encoder_last_error(self.h)).to_string_lossy().into_owned() })

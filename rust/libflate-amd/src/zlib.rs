@@ -68,6 +68,13 @@ impl<W: io::Write, E: GpuLz77> Encoder<W, E> {
         let (o, on_device) = options.to_ffi();
         Ok(Encoder { raw: RawEncoder::new(ffi::LFX_ZLIB, &o, inner)?, stage: options.inner.into_stage(on_device) })
     }
+    /// `with_options` with a preset dictionary (`deflateSetDictionary`; not a reference call): the six-byte header with FDICT
+    /// and the dictionary's id is written here, the stream's first chunk is primed.  A chained, lazy or level parse needs a
+    /// `Dictionary::with_chain`.
+    pub fn with_dictionary(inner: W, options: EncodeOptions<E>, dictionary: std::sync::Arc<crate::dict::Dictionary>) -> io::Result<Self> {
+        let (o, on_device) = options.to_ffi();
+        Ok(Encoder { raw: RawEncoder::new_dict(ffi::LFX_ZLIB, &o, dictionary, inner)?, stage: options.inner.into_stage(on_device) })
+    }
     pub fn finish(mut self) -> Finish<W, io::Error> {
         let closed = self.stage.close(&mut self.raw, 2);
         let (w, e) = self.raw.finish();
