@@ -812,6 +812,30 @@ int lfx_encode_dict_host(lfx_ctx *c, int format, const lfx_encode_opts *o, const
 int lfx_encode_batch_dict_device(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_schedule *s, const lfx_dict *dict,
                                  uint32_t count, const void *d_in, const uint64_t *in_off, const uint64_t *in_len, void *d_out,
                                  const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status);
+/* The batch packed back to back: the caller names no place for any stream.  Stream i is byte for byte the stream
+ * lfx_encode_batch_device writes for record i with the same format, options and schedule — with `dict`, the stream
+ * lfx_encode_batch_dict_device writes — container header, trailer and empty records (in_len == 0) included.  The streams' sizes
+ * are known on the device behind the Huffman stage; a device scan places them, and they are packed where they stay:
+ *   out_off[0] = 0, out_off[i + 1] = round_up(out_off[i] + out_len[i], align), *total = out_off[count - 1] + out_len[count - 1]
+ * (the tail is not rounded); gap bytes are zero.  count == 0: LFX_OK, *total = 0.
+ * align: a power of two in 1..4096, else LFX_E_ARG.  d_out must be 4-byte aligned (LFX_E_ARG).  dict (NULL: none): only with
+ * LFX_ZLIB or LFX_DEFLATE, and a dictionary of this context, else LFX_E_ARG.  Options are served and refused exactly as by the
+ * batch call of the same dictionary kind.  in_off, in_len, out_off, out_len and total are HOST memory; out_off, out_len and total
+ * may each be NULL.  d_table (NULL: none; device memory, 8-byte aligned): count pairs {off, len} of uint64_t, the same layout —
+ * for a kernel or an lfx_decode_batch_device call that follows without a host round trip of the caller's.
+ * Capacity.  *total > cap: LFX_E_NOSPACE; *total, out_off[], out_len[] and d_table hold the layout the call would have produced,
+ * no stream is written, [0, cap) may have been zero-filled, and the context is usable for the next call, as after a voided batch
+ * call.  d_out == NULL with cap == 0 is therefore the size query (d_out == NULL with any other cap: LFX_E_ARG).  There is no
+ * bound to meet: any cap >= *total serves, and the sum of lfx_encode_bound (lfx_encode_dict_bound) over the records, every term
+ * rounded up to align, always does.
+ * Reach.  d_out[0, min(cap, that sum)) is zero-filled first.  No byte at or behind cap changes its value; read-modify-writes of
+ * whole dwords stay inside [d_out, d_out + ((cap + 3) & ~3)).  A NULL context: LFX_E_DEVICE, nothing written. */
+int lfx_encode_batch_packed_device(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_schedule *s,
+                                   const lfx_dict *dict /* NULL: none */, uint32_t count,
+                                   const void *d_in, const uint64_t *in_off, const uint64_t *in_len,
+                                   uint32_t align, void *d_out, uint64_t cap,
+                                   uint64_t *out_off, uint64_t *out_len, uint64_t *total,
+                                   void *d_table /* optional, device: count x {off, len} as uint64 pairs */);
 
 /* ---- a chain dictionary: LFX_LZ77_CHAIN and LFX_LZ77_LAZY through a preset dictionary ----
  * lfx_dict_new_chain makes a dictionary that also carries the hash chain of its own tail.  With it lfx_encode_dict_device,

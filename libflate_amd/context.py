@@ -417,6 +417,54 @@ class Context:
             raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
         return rc, [(st[i], out_len[i]) for i in range(k)]
 
+    # ---- a batch packed back to back (lfx_encode_batch_packed_device) -------------------
+    def encode_batch_packed_device(self, fmt, d_in, in_offs, in_lens, d_out, cap, *, zdict=None, opts=None, schedule=None, align=1,
+                                   d_table=None):
+        """lfx_encode_batch_packed_device: the records d_in[in_offs[i], +in_lens[i]) as the streams the batch call writes, laid
+        out on the device back to back in d_out[0, cap), every stream's start a multiple of `align`; zdict: one Dictionary for
+        all of them (zlib / raw DEFLATE); d_table: device memory for count {off, len} pairs of uint64, or None
+        → (rc, total, [(off, len)] per stream); rc is LFX_OK or LFX_E_NOSPACE (total > cap: the call is void, total and the
+        layout say what it needs; d_out = None with cap = 0 is the size query), anything else raises"""
+        k = len(in_offs)
+        a = lambda v: (C.c_uint64 * max(k, 1))(*v)
+        io, il = a(in_offs), a(in_lens)
+        oo, ol, total = (C.c_uint64 * max(k, 1))(), (C.c_uint64 * max(k, 1))(), C.c_uint64(0)
+        rc = _ffi.lib().lfx_encode_batch_packed_device(self._h, fmt, C.byref(opts) if opts is not None else None,
+                                                       C.byref(schedule) if schedule is not None else None, self._dict_handle(zdict),
+                                                       k, d_in, io, il, align, d_out, cap, oo, ol, C.byref(total), d_table)
+        if rc and rc != _ffi.E_NOSPACE:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return rc, total.value, [(oo[i], ol[i]) for i in range(k)]
+
+    def encode_batch_packed_host(self, fmt, records, zdict=None, opts=None, schedule=None):
+        """a list of bytes → the list of their streams: one upload, one lfx_encode_batch_packed_device call with cap = the sum
+        of the bounds, one download of `total` bytes"""
+        import torch
+        records = [bytes(r) for r in records]
+        if not records:
+            return []
+        bound = _ffi.lib().lfx_encode_dict_bound if zdict is not None else _ffi.lib().lfx_encode_bound
+        op, sp = C.byref(opts) if opts is not None else None, C.byref(schedule) if schedule is not None else None
+        known, cap, offs, at = {}, 0, [], 0
+        for r in records:
+            if len(r) not in known:
+                known[len(r)] = bound(len(r), op, sp)
+                if known[len(r)] == 0:
+                    raise _ffi.LfxError(_ffi.E_ARG, "option outside the reference's domain")
+            cap += known[len(r)]
+            offs.append(at)
+            at += len(r)
+        dev = torch.device("cuda", self.device)
+        d_in = torch.frombuffer(bytearray(b"".join(records) or b"\0"), dtype=torch.uint8).to(dev)
+        d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        rc, total, layout = self.encode_batch_packed_device(fmt, d_in.data_ptr(), offs, [len(r) for r in records], d_out.data_ptr(), cap,
+                                                            zdict=zdict, opts=opts, schedule=schedule)
+        if rc:
+            raise _ffi.LfxError(rc, self.last_error())
+        out = d_out[:total].cpu().numpy().tobytes()
+        return [out[o:o + n] for o, n in layout]
+
 
 class Dictionary:
     """A preset dictionary (lfx_dict): what zlib.compressobj(zdict=...) was given.  The last 32 KiB are the

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "lfx_batch_pack.h"
 #include "lfx_ctx.h"
 #include "lfx_device.h"
 #include "lfx_enc_frame.h"
@@ -62,17 +63,19 @@ static void apply_schedule(Planner &pl, const lfx_schedule *s, uint64_t n) {
     }
 }
 
-extern "C" uint64_t lfx_encode_bound(uint64_t n, const lfx_encode_opts *o, const lfx_schedule *s) {
-    EncodeSpec sp;
-    if (encode_spec(LFX_ZLIB, o, &sp)) return 0;
-    const lfx_encode_opts &d = sp.o;
-    Planner pl(sp.plan);
-    apply_schedule(pl, s, n);
-    Plan &p = pl.finish();
+// the bound of n bytes planned into nblocks blocks (lfx_encode_batch_packed_device plans every stream anyway)
+static uint64_t encode_bound_of(const lfx_encode_opts &d, uint64_t n, size_t nblocks) {
     // a dynamic block never costs more than ~9 bits per literal + its header; stored: 5 bytes per block
     uint64_t hdr = 64 + (d.extra ? d.extra_len + 2 : 0) + (d.filename ? strlen(d.filename) + 1 : 0) +
                    (d.comment ? strlen(d.comment) + 1 : 0);
-    return n + n / 4 + 1024 * (uint64_t)p.blocks.size() + hdr + 64;
+    return n + n / 4 + 1024 * (uint64_t)nblocks + hdr + 64;
+}
+extern "C" uint64_t lfx_encode_bound(uint64_t n, const lfx_encode_opts *o, const lfx_schedule *s) {
+    EncodeSpec sp;
+    if (encode_spec(LFX_ZLIB, o, &sp)) return 0;
+    Planner pl(sp.plan);
+    apply_schedule(pl, s, n);
+    return encode_bound_of(sp.o, n, pl.finish().blocks.size());
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -364,6 +367,65 @@ extern "C" int lfx_encode_batch_dict_device(lfx_ctx *cc, int format, const lfx_e
     if (format != LFX_ZLIB && format != LFX_DEFLATE) return LFX_E_ARG;
     if (dict && dict->c != reinterpret_cast<Ctx *>(cc)) return LFX_E_ARG;
     return encode_batch_impl(cc, format, o, s, dict, count, d_in, in_off, in_len, d_out, out_off, out_cap, out_len, status);
+} LFX_ABI_CATCH
+
+// ---- the batch packed back to back: the batch call's merged plan and kernels; the streams' places come from
+// a device scan of their sizes behind the Huffman kernel (lfx_batch_pack.hip) instead of from the caller
+extern "C" int lfx_encode_batch_packed_device(lfx_ctx *cc, int format, const lfx_encode_opts *o, const lfx_schedule *s,
+                                              const lfx_dict *dict, uint32_t count, const void *d_in, const uint64_t *in_off,
+                                              const uint64_t *in_len, uint32_t align, void *d_out, uint64_t cap, uint64_t *out_off,
+                                              uint64_t *out_len, uint64_t *total, void *d_table) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (format < 0 || format > 2 || (count && (!in_off || !in_len))) return LFX_E_ARG;
+    if (dict && ((format != LFX_ZLIB && format != LFX_DEFLATE) || dict->c != c)) return LFX_E_ARG;
+    if (!bpack_align_ok(align)) { c->set_error("align: a power of two in 1..4096"); return LFX_E_ARG; }
+    if (((uintptr_t)d_out & 3) != 0) { c->set_error("output buffer must be 4-byte aligned"); return LFX_E_ARG; }
+    if (!d_out && cap) { c->set_error("d_out: NULL with a capacity (the size query is d_out = NULL, cap = 0)"); return LFX_E_ARG; }
+    if (((uintptr_t)d_table & 7) != 0) { c->set_error("d_table must be 8-byte aligned"); return LFX_E_ARG; }
+    if (count > BPACK_MAX_COUNT) { c->set_error("count: too many streams for one call"); return LFX_E_ARG; }
+    EncodeSpec sp;
+    int rc = encode_spec(format, o, &sp);
+    if (rc) { c->set_error("option outside the reference's domain"); return rc; }
+    if ((rc = served(c, ENC_BATCH_PACKED, sp, dict))) return rc;
+    std::vector<uint8_t> hdr;
+    if ((rc = container_header(format, sp.o, hdr))) { c->set_error("bad container options"); return rc; }
+    if (dict) dict_header(format, dict, hdr);
+    if (total) *total = 0;
+    if (!count) return LFX_OK;
+    // ---- the merged plan, as in the batch call; every stream's bound on the way
+    Plan plan;
+    std::vector<BatchStream> streams(count);
+    std::vector<uint64_t> bound(count);
+    uint64_t in_extent = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        Planner pl(sp.plan);
+        apply_schedule(pl, s, in_len[i]);
+        Plan &p = pl.finish();
+        if (dict) dict_prime(dict, p);
+        bound[i] = encode_bound_of(sp.o, in_len[i], p.blocks.size()) + (dict ? 4 : 0);
+        streams[i] = BatchStream{in_off[i], in_len[i], 0, 0, (uint32_t)plan.blocks.size(), (uint32_t)p.blocks.size()};
+        plan.append(p, in_off[i]);
+        in_extent = std::max(in_extent, in_off[i] + in_len[i]);
+    }
+    uint64_t bound_sum = 0;
+    if (!bpack_bound_sum(bound.data(), count, align, &bound_sum)) { c->set_error("in_len: the streams' bounds exceed 64 bits"); return LFX_E_ARG; }
+    std::vector<uint64_t> pairs;
+    EncodeResult res{};
+    const BatchPackedCall call{format, streams, hdr, (const uint8_t *)d_in, in_extent, (uint8_t *)d_out, cap, std::min(cap, bound_sum),
+                               align, dict, (uint64_t *)d_table};
+    if ((rc = encode_batch_packed(c, plan, sp, call, pairs, res))) return rc;
+    for (uint32_t i = 0; i < count; i++) {
+        if (out_off) out_off[i] = pairs[2 * (size_t)i];
+        if (out_len) out_len[i] = pairs[2 * (size_t)i + 1];
+    }
+    if (total) *total = res.out_bytes;
+    if (res.status) {
+        c->set_error("output capacity too small (*total says what the streams need): the call is void, no stream was written");
+        return LFX_E_NOSPACE;
+    }
+    return LFX_OK;
 } LFX_ABI_CATCH
 
 // A host variant: `in` staged into d_io_in, run(len) — the device entry point on d_io_in / d_io_out — and len bytes back.

@@ -113,6 +113,18 @@ int launch_members_layout(hipStream_t st, const MembersGeom &g, BlockDesc *block
 // behind pack: headers, trailers, the end-of-file marker (nothing when res->status != 0)
 int launch_members_frame(hipStream_t st, const MembersGeom &g, const uint8_t *hdr, const lfx_member *members, const uint32_t *crc,
                          const EncodeResult *res, uint32_t *out);
+// the second level of that scan alone: wg_sum[0, nwg) → its exclusive scan in place, res->out_bytes = the sum (and res->end_bit
+// = 8 x), res->status = 1 when it exceeds cap
+int launch_scan_wg_sums(hipStream_t st, uint64_t *wg_sum, uint32_t nwg, uint64_t cap, EncodeResult *res);
+// lfx_encode_batch_packed_device (lfx_batch_pack.hip) in the place of launch_offsets_batch: every stream's length
+// (header and trailer included), the device-wide scan of round_up(length, align) — the last stream's unrounded —, then per stream
+// streams[].out_off / out_cap = its offset and length, block_start[] and stream_end[] from there, pairs[] = {off, len} (and the
+// same into table, the caller's, where given); res->out_bytes = the total, res->status = 1 when it exceeds cap.
+// local_off, slen, stream_end: 8 bytes per stream; pairs: 16; wg_sum: 8 bytes per 256 streams
+int launch_batch_pack_layout(hipStream_t st, BatchStream *streams, uint32_t count, const BlockDesc *blocks, const BlockCodes *bc,
+                             uint32_t hdr_len, uint32_t trailer_len, uint32_t align, uint64_t cap, uint64_t *local_off, uint64_t *slen,
+                             uint64_t *wg_sum, uint64_t *block_start, uint64_t *stream_end, uint64_t *pairs, uint64_t *table,
+                             EncodeResult *res);
 int launch_pack(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const ChunkDesc *chunks,
                 uint32_t nchunks, const BlockDesc *blocks, uint32_t nblocks, uint64_t ntiles,
                 const uint32_t *codes, const uint32_t *ncodes, const BlockCodes *bc,

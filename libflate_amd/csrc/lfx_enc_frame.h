@@ -156,7 +156,10 @@ inline int encode_spec(int format, const lfx_encode_opts *o, EncodeSpec *out) {
 // Which entry point serves which spec and dictionary: THE table (the public contract: include/lfx.h, and
 // tests/c/encode_spec.cpp holds one against the other).  Nothing else answers LFX_E_UNSUPPORTED for a combination of options
 // and dictionary.
-enum EncodeEntry { ENC_DEVICE, ENC_BATCH, ENC_DICT_DEVICE, ENC_DICT_BATCH, ENC_STREAM, ENC_MEMBERS, ENC_INDEX, ENC_SHARD, ENC_LZ77 };
+enum EncodeEntry { ENC_DEVICE, ENC_BATCH, ENC_DICT_DEVICE, ENC_DICT_BATCH, ENC_STREAM, ENC_MEMBERS, ENC_INDEX, ENC_SHARD, ENC_LZ77,
+                   // lfx_encode_batch_packed_device (§26), with or without a dictionary: the rows of ENC_BATCH / ENC_DICT_BATCH —
+                   // none of its own, the dictionary rows by the dictionary's kind
+                   ENC_BATCH_PACKED };
 enum DictKind { DICT_NONE, DICT_PLAIN, DICT_CHAIN };     // lfx_dict_new / lfx_dict_new_chain (§18, §21)
 // → LFX_OK (*why = nullptr), or LFX_E_UNSUPPORTED with *why.  Where a call has two reasons, the first row wins.
 inline int encode_served(EncodeEntry e, const EncodeSpec &sp, DictKind dict, const char **why) {

@@ -633,6 +633,57 @@ int encode_batch(Ctx *c, const Plan &plan, const EncodeSpec &sp, const BatchCall
     });
 }
 
+int encode_batch_packed(Ctx *c, const Plan &plan, const EncodeSpec &sp, const BatchPackedCall &b, std::vector<uint64_t> &h_pairs,
+                        EncodeResult &res) {
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    const uint32_t count = (uint32_t)b.streams.size();
+    const uint32_t trailer = trailer_len(b.format), nwg = (count + 255) / 256;
+    // per-stream scratch: descriptors; end bits, offsets inside the workgroup, lengths, the {off, len} pairs, the frame kernel's
+    // lengths; the workgroup sums; checksums (+ the header bytes)
+    const size_t sz_streams = sizeof(BatchStream) * count;
+    DevBuf &sb = c->d_dec_streams;     // (decode scratch: free during an encode)
+    if (int rc = sb.reserve(sz_streams + (8 * 6 + 4 + 4) * (size_t)count + 8 * (size_t)nwg + b.hdr.size() + 64)) return rc;
+    BatchStream *d_streams = (BatchStream *)sb.p;
+    uint64_t *d_end = (uint64_t *)((uint8_t *)sb.p + sz_streams);
+    uint64_t *d_local = d_end + count, *d_slen = d_local + count, *d_pairs = d_slen + count, *d_len = d_pairs + 2 * (size_t)count;
+    uint64_t *d_wg = d_len + count;
+    uint32_t *d_crc = (uint32_t *)(d_wg + nwg), *d_adler = d_crc + count;
+    uint8_t *d_hdr = (uint8_t *)(d_adler + count);
+    h_pairs.resize(2 * (size_t)count);
+    // the kernels OR into zeros: [0, fill) is filled once, beside the match kernel; no stream can end behind the sum of the
+    // bounds, and nothing is written when the total exceeds cap
+    c->prezero.start(b.d_out, b.fill);
+    const int rc = with_match_fallback(c, res, [&]() -> int {
+        if (int rc2 = encode_prepare(c, plan, sp, b.d_in, b.in_extent, 0, nullptr, b.dict)) return rc2;
+        HIP_TRY(hipMemcpyAsync(d_streams, b.streams.data(), sz_streams, hipMemcpyHostToDevice, st));
+        if (!b.hdr.empty()) HIP_TRY(hipMemcpyAsync(d_hdr, b.hdr.data(), b.hdr.size(), hipMemcpyHostToDevice, st));
+        if (trailer)
+            LAUNCH_TRY(launch_checksum_ranges(st, b.d_in, count, (const uint64_t *)d_streams, sizeof(BatchStream) / 8,
+                                              (const uint64_t *)d_streams + 1, sizeof(BatchStream) / 8, d_crc, d_adler));
+        c->phase("checksum");
+        EncodeResult *dres = (EncodeResult *)c->d_res.p;
+        LAUNCH_TRY(launch_batch_pack_layout(st, d_streams, count, (const BlockDesc *)c->d_blocks.p, (const BlockCodes *)c->d_bc.p,
+                                            (uint32_t)b.hdr.size(), trailer, b.align, b.cap, d_local, d_slen, d_wg,
+                                            (uint64_t *)c->d_block_start.p, d_end, d_pairs, b.d_table, dres));
+        c->phase("batch_layout");
+        HIP_TRY(c->prezero.join(st, b.d_out, b.fill));
+        if (int rc2 = pack_blocks(c, b.d_out)) return rc2;
+        c->phase("pack");
+        LAUNCH_TRY(launch_frame_batch(st, b.format, d_streams, count, d_hdr, (uint32_t)b.hdr.size(), d_end, d_crc, d_adler, dres,
+                                      (uint32_t *)b.d_out, d_len));
+        HIP_TRY(hipMemcpyAsync(c->h_res, dres, sizeof(EncodeResult), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_pairs.data(), d_pairs, 16ull * count, hipMemcpyDeviceToHost, st));
+        c->phase("frame");
+        HIP_TRY(hipStreamSynchronize(st));
+        res = *(EncodeResult *)c->h_res;
+        if (res.status & 2u) { c->set_error(PACK_MISMATCH); return LFX_E_DEVICE; }
+        return LFX_OK;
+    });
+    c->prezero.settle();     // (failed before the stream waited for the fill: it is on the caller's buffer)
+    return rc;
+}
+
 int encode_members(Ctx *c, const Plan &plan, const EncodeSpec &sp, const MembersCall &m, EncodeResult &res) {
     hipStream_t st = c->stream;
     const MembersGeom &g = m.g;

@@ -76,6 +76,23 @@ struct BatchCall {
 };
 int encode_batch(Ctx *c, const Plan &plan, const EncodeSpec &sp, const BatchCall &b, std::vector<uint64_t> &h_len,
                  std::vector<int32_t> &h_status, EncodeResult &res);
+// lfx_encode_batch_packed_device behind its argument checks: the same merged plan, the streams laid out on the
+// device behind the Huffman kernel and packed back to back.  streams[].out_off / out_cap are the device's to fill.
+struct BatchPackedCall {
+    int format;
+    const std::vector<BatchStream> &streams;
+    const std::vector<uint8_t> &hdr;
+    const uint8_t *d_in;
+    uint64_t in_extent;
+    uint8_t *d_out;
+    uint64_t cap, fill;           // fill: bytes of d_out to zero, min(cap, the sum of the streams' rounded bounds)
+    uint32_t align;
+    const lfx_dict *dict;
+    uint64_t *d_table;            // the caller's device table of {off, len}, or nullptr
+};
+// h_pairs: {off, len} per stream; res.out_bytes = the total, res.status != 0: it exceeds cap and no stream was written
+int encode_batch_packed(Ctx *c, const Plan &plan, const EncodeSpec &sp, const BatchPackedCall &b, std::vector<uint64_t> &h_pairs,
+                        EncodeResult &res);
 // lfx_encode_members_device behind its argument checks and the merged plan
 struct MembersCall {
     MembersGeom g;

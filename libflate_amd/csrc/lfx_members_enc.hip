@@ -203,6 +203,13 @@ int launch_members_layout(hipStream_t st, const MembersGeom &g, BlockDesc *block
     return 0;
 }
 
+// menc_scan_kernel alone, for lfx_batch_pack.hip: its first scan level leaves its own workgroup sums
+int launch_scan_wg_sums(hipStream_t st, uint64_t *wg_sum, uint32_t nwg, uint64_t cap, EncodeResult *res) {
+    hipLaunchKernelGGL(menc_scan_kernel, dim3(1), dim3(1024), 0, st, wg_sum, nwg, 0ull, cap, res);
+    LFX_LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_members_frame(hipStream_t st, const MembersGeom &g, const uint8_t *hdr, const lfx_member *members, const uint32_t *crc,
                          const EncodeResult *res, uint32_t *out) {
     const uint32_t lanes = g.count + (g.bgzf ? 1u : 0u);

@@ -112,6 +112,30 @@ def _compress(fmt, data, zdict, options, context, lz77=None, level=None, merge_b
             d.close()
 
 
+def _compress_batch(fmt, records, zdict, options, context, lz77=None, level=None, merge_blocks=False):
+    from .context import Dictionary, default_context
+    ctx = context if context is not None else default_context()
+    options = _with_lz77(options, lz77, EncodeOptions, level)
+    if merge_blocks:
+        options = (options if options is not None else EncodeOptions()).merge_blocks()
+    opts = options._to_c() if options is not None else None
+    own = zdict is not None and not hasattr(zdict, "handle")
+    chained = opts is not None and (opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL)
+    d = Dictionary(zdict, ctx, chain=chained) if own else zdict     # (as in _compress)
+    try:
+        return ctx.encode_batch_packed_host(fmt, records, d, opts)
+    finally:
+        if own:
+            d.close()
+
+
+def compress_batch(records, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False):
+    """[compress(r, ...) for r in records] — a list of bytes to the list of their raw DEFLATE streams — in one upload, one
+    encode of all records (lfx_encode_batch_packed_device) and one download of the streams packed back to
+    back.  The keywords are compress's; one zdict serves every record."""
+    return _compress_batch(_ffi.DEFLATE, records, zdict, options, context, lz77, level, merge_blocks)
+
+
 def compress(data, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False):
     """`data` as one raw DEFLATE stream, encoded in one call (one write_all + finish).  zdict: a preset dictionary, bytes or a
     libflate_amd.Dictionary — the stream then starts with the dictionary as history, what

@@ -157,6 +157,15 @@ def compress(data, options=None, context=None, lz77=None, level=None, merge_bloc
     return _deflate._compress(_ffi.GZIP, data, None, options, context, lz77, level, merge_blocks)
 
 
+def compress_batch(records, options=None, context=None, lz77=None, level=None, merge_blocks=False):
+    """[compress(r, ...) for r in records] — a list of bytes to the list of their gzip members — in one upload, one encode of
+    all records (lfx_encode_batch_packed_device) and one download of the members packed back to back.  The
+    keywords are compress's."""
+    if options is None:
+        options = EncodeOptions()
+    return _deflate._compress_batch(_ffi.GZIP, records, None, options, context, lz77, level, merge_blocks)
+
+
 def encode_members(data, member_size=1 << 20, bgzf=False, options=None, context=None, lz77=None):
     """`data` as gzip members of member_size input bytes each, lying back to back: what decode_members, zcat and Python's gzip
     read, and with bgzf=True (member_size at most 65505; bgzip's own is _ffi.BGZF_MEMBER_SIZE = 65280) a BGZF file with its

@@ -45,6 +45,15 @@ def compress(data, zdict=None, options=None, context=None, lz77=None, level=None
     return _deflate._compress(_ffi.ZLIB, data, zdict, options, context, lz77, level, merge_blocks)
 
 
+def compress_batch(records, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False):
+    """[compress(r, zdict=..., ...) for r in records] — a list of bytes to the list of their zlib streams — in one upload, one
+    encode of all records (lfx_encode_batch_packed_device) and one download of the streams packed back to
+    back.  The keywords are compress's; one zdict serves every record."""
+    if (lz77 is not None or level is not None or merge_blocks) and options is None:
+        options = EncodeOptions()
+    return _deflate._compress_batch(_ffi.ZLIB, records, zdict, options, context, lz77, level, merge_blocks)
+
+
 class Decoder(_DecoderBase):
     """zlib::Decoder (zlib.rs:284-410)."""
     FORMAT = _ffi.ZLIB
