@@ -113,6 +113,31 @@ enum { LFX_LZ77_DEFAULT = 0, LFX_LZ77_NOCOMPRESSION = 1, LFX_LZ77_CHAIN = 2, LFX
  * the same rules. */
 enum { LFX_LZ77_LEVEL = 4 };
 #define LFX_LZ77_LEVEL_N(n) (LFX_LZ77_LEVEL | (n) << 8)
+/* LFX_LZ77_COST — CostLz77Encoder(level 1..9, window_size W, max_length M): LevelLz77Encoder(level) with the lazy rule replaced by
+ * a choice by cost in bits.  Opt-in; a valid stream, deterministic, not zlib's bytes.  (The value is 6: 5 names no
+ * kind and stays LFX_E_ARG.)
+ *  - Candidates: L(p), D(p) of LFX_LZ77_LEVEL at the same level — depth K, nice N and too_far F of its row (the levels 1..3 have no
+ *    too-far rule).  max_lazy is not used.  Buffering, window_size, max_length and the tail are LFX_LZ77_LEVEL's.
+ *  - For a flushed buffer with visited range [0, end): lit(p) = the width of the literal buf[p]; mat(p) = the width of L(p)'s
+ *    length symbol + its extra bits + the width of D(p)'s distance symbol + its extra bits.  All widths are those of the block
+ *    that owns the buffer's code words.
+ *  - The widths.  dynamic_huffman = 0: the fixed code's.  Otherwise: the code the same call builds in a first pass — the greedy
+ *    walk over L and D (no position demoted), the block's symbol counts, the plain dynamic code, without LFX_HUFFMAN_AUTO and
+ *    without block_merge.  A symbol without a code in that pass costs one bit more than the longest code of its alphabet
+ *    (literal/length, distance) in that block; an alphabet without any code costs 9 (literal/length) or 5 (distance).
+ *  - The recurrence.  The buffer is cut on a grid of COST_SEG = 4096 positions from its start.  For a segment [a, b) it starts
+ *    at top = min(b + COST_WARM, end), COST_WARM = 512, with cost[top] = 0 and runs backward:
+ *        cost[p] = min(lit(p) + cost[p + 1], mat(p) + cost[min(p + L(p), top)])       the match term only where L(p) != 0
+ *    On a tie the match wins.  For p in [a, b): where the literal won the position loses its candidate, L(p) = 0; the positions
+ *    of the warm-up are the next segment's to decide.  Nothing is read across a buffer.
+ *  - The walk is LFX_LZ77_CHAIN's greedy one over what is left of L and D.
+ *  - compression_level() is Best (FLEVEL 3, XFL 2), with the rules of LFX_LZ77_CHAIN.
+ * lz77_kind & 0xFF is the kind; bits 8..15 hold the level.  Level 0, a level above 9 or any bit above 15 set: LFX_E_ARG.
+ * Served as LFX_LZ77_LEVEL is — one-shot, batch, packed batch, a chain dictionary, lfx_encoder_* (bytes mode), members and BGZF,
+ * with LFX_HUFFMAN_AUTO and block_merge on top (both decide on the final pass' code words) — with two exceptions:
+ * lfx_encode_index_device is LFX_E_UNSUPPORTED (a second parse would list its candidates twice), and so is the N-GPU encode. */
+enum { LFX_LZ77_COST = 6 };
+#define LFX_LZ77_COST_N(n) (LFX_LZ77_COST | (n) << 8)
 /* lfx_encode_opts::dynamic_huffman.  0: fixed codes for every block (fixed_huffman_codes(), encode.rs:107-110).  1, and every
  * value other than 0 and 2: dynamic codes for every block (the reference's default).
  * LFX_HUFFMAN_AUTO (2) — opt-in, not a reference option: per block the smallest of the dynamic, the fixed and

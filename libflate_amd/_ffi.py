@@ -13,6 +13,7 @@ DEFLATE, ZLIB, GZIP = 0, 1, 2
 OK, E_INVALID_DATA, E_UNEXPECTED_EOF, E_IO, E_OOM, E_DEVICE, E_ARG, E_NOSPACE, E_UNSUPPORTED, E_WOULD_BLOCK = range(10)
 LZ77_DEFAULT, LZ77_NOCOMPRESSION, LZ77_CHAIN, LZ77_LAZY = 0, 1, 2, 3     # (LZ77_CHAIN and LZ77_LAZY carry their depth: kind | depth << 8)
 LZ77_LEVEL = 4                                                           # (carries its level 1..9: kind | level << 8)
+LZ77_COST = 6                                                            # (carries its level 1..9 as LZ77_LEVEL does; 5 names no kind)
 HUFFMAN_FIXED, HUFFMAN_DYNAMIC, HUFFMAN_AUTO = 0, 1, 2     # lfx_encode_opts.dynamic_huffman; AUTO: the smallest form per block
 FLUSH_NONE, FLUSH_SYNC = 0, 2
 SCHED_SINGLE, SCHED_FIXED, SCHED_LIST = 0, 1, 2

@@ -44,7 +44,7 @@ class _EncoderBase:
             own = not hasattr(zdict, "handle")
             if own:
                 from .context import Dictionary
-                chained = (self._opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL)
+                chained = (self._opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL, _ffi.LZ77_COST)
                 zdict = Dictionary(zdict, self._ctx, chain=chained)
             self._h = _ffi.lib().lfx_encoder_new_dict(self._ctx.handle, self.FORMAT, C.byref(self._opts), zdict.handle,
                                                       self._wcb, self._fcb, None, C.byref(st))

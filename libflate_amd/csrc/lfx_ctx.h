@@ -8,6 +8,7 @@
 
 #include "lfx_chain.h"
 #include "lfx_common.h"
+#include "lfx_cost.h"
 #include "lfx_device.h"
 #include "lfx_dict_enc.h"
 #include <string.h>
@@ -103,6 +104,10 @@ struct Ctx {
     // its host copy.  Sized only by calls of that kind.  d_len: LazyLz77Encoder's (§20) length byte per position, sized only by
     // calls of that kind.
     DevBuf d_cd2, d_chain_items, d_len;
+    // an encode with CostLz77Encoder: the cost kernel's work list and its host copy.  Sized only by calls of
+    // that kind.
+    DevBuf d_cost_items;
+    std::vector<CostItem> cost_items;
     // an encode with LFX_HUFFMAN_AUTO: the type every block left block_choose_kernel with, one byte per block.
     // Sized only by calls of that kind; n_choices: its entries of the last prepare (0: that call was not one) — read by the
     // test hook lfx_debug_block_choices alone, no encode path looks at either.
@@ -142,7 +147,7 @@ struct Ctx {
                 &d_dec_streams, &d_dec_state, &d_dec_tmp, &d_dec_cand, &d_dec_blocks, &d_dec_tabs, &d_dec_sym, &d_dec_win, &d_dec_maps,
                 &d_dec_temp, &d_dec_lanesx, &d_idx_tasks, &d_idx_probe, &d_idx_stage, &d_idx_enc,
                 &d_bgzf_meta, &d_bgzf_tasks, &d_bgzf_scratch, &d_bgzf_pack, &d_dict_items, &d_cd2, &d_chain_items, &d_len, &d_choice, &d_hist_chunk, &d_chunk_bits,
-                &d_merge_regions, &d_merge};
+                &d_merge_regions, &d_merge, &d_cost_items};
     }
     void *h_res = nullptr;  // pinned, 4 KiB (+ the arena below)
     // Small transfers of the decode paths (job lists up, scan results and counters down) go through page-locked memory: a

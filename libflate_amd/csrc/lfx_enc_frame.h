@@ -73,6 +73,11 @@ inline int lz77_kind_of(const lfx_encode_opts &o) { return (int)((uint32_t)o.lz7
 inline bool lz77_chained(int kind) { return kind == LFX_LZ77_CHAIN || kind == LFX_LZ77_LAZY; }
 // the kinds that run the chain stage: those, and LFX_LZ77_LEVEL, whose depth comes from the level table below (§23)
 inline bool lz77_chain_stage(int kind) { return lz77_chained(kind) || kind == LFX_LZ77_LEVEL; }
+// the kinds that carry a level 1..9 in bits 8..15: LFX_LZ77_LEVEL and LFX_LZ77_COST (§27), which is that level's encoder with
+// the lazy rule replaced by the cost rule.  (5 stays refused: tests/c/level_opts.cpp pins !lz77_chain_stage(5); the kind is 6.)
+inline bool lz77_leveled(int kind) { return kind == LFX_LZ77_LEVEL || kind == LFX_LZ77_COST; }
+// "runs the chain stage", LFX_LZ77_COST included
+inline bool lz77_runs_chain(int kind) { return lz77_chain_stage(kind) || kind == LFX_LZ77_COST; }
 
 // LFX_LZ77_LEVEL: what a level 1..9 resolves into — zlib's configuration_table (deflate.c) without good_length,
 // which makes a position's length depend on its predecessor's and stays out.  max_lazy and too_far are read by the lazy levels
@@ -104,7 +109,7 @@ inline LevelTune level_tune(uint32_t level) {
 // outside 1..9 is refused by encode_spec: Balance here); no_compression() resets the header's level like any other
 // (zlib.rs:471-475, gzip.rs:703)
 inline uint8_t lz77_level_of(const lfx_encode_opts &o) {
-    if (o.lz77_level == 0 && lz77_chained(lz77_kind_of(o)) && !o.no_compression) return 1 + LFX_LEVEL_BEST;
+    if (o.lz77_level == 0 && (lz77_chained(lz77_kind_of(o)) || lz77_kind_of(o) == LFX_LZ77_COST) && !o.no_compression) return 1 + LFX_LEVEL_BEST;
     if (o.lz77_level == 0 && lz77_kind_of(o) == LFX_LZ77_LEVEL && !o.no_compression) {
         const uint32_t level = ((uint32_t)o.lz77_kind >> 8) & 0xFFu;
         return (uint8_t)(1 + (level <= 3 ? LFX_LEVEL_FAST : level >= 7 ? LFX_LEVEL_BEST : LFX_LEVEL_BALANCE));
@@ -121,6 +126,7 @@ struct EncodeSpec {
     bool lazy = false;            // LazyLz77Encoder: the chain stage also demotes a position whose successor matches longer (§20)
     bool tuned = false;           // LFX_LZ77_LEVEL (§23): chain_depth and lazy come from the level, and the chain stage runs its tuned instances with ...
     LevelTune tune{0, false, 0, 0, 0};   // ... this (tune.depth == chain_depth, tune.lazy == lazy); all 0 for any other kind
+    bool cost = false;            // LFX_LZ77_COST (§27): the level's candidates (tuned, tune), the cost rule in place of the lazy one (lazy is false)
     bool auto_blocks = false;     // LFX_HUFFMAN_AUTO (§22): every dynamic block's form chosen on the device; never under no_compression
     bool merge_blocks = false;    // block_merge (§24): neighbouring dynamic blocks joined on the device; never under no_compression or fixed codes
 };
@@ -132,23 +138,25 @@ inline int encode_spec(int format, const lfx_encode_opts *o, EncodeSpec *out) {
     if (d.window_size > MAX_WINDOW) d.window_size = MAX_WINDOW;  // default.rs:228
     if (d.max_length > MAX_LENGTH) d.max_length = MAX_LENGTH;    // default.rs:240
     const int kind = lz77_kind_of(d);
-    out->tuned = kind == LFX_LZ77_LEVEL;
+    out->cost = kind == LFX_LZ77_COST;
+    out->tuned = lz77_leveled(kind);
     out->tune = level_tune(out->tuned ? ((uint32_t)d.lz77_kind >> 8) & 0xFFu : 0u);
     out->chain_depth = lz77_chained(kind) ? ((uint32_t)d.lz77_kind >> 8) & 0xFFu : out->tune.depth;
-    out->lazy = kind == LFX_LZ77_LAZY || out->tune.lazy;
+    out->lazy = kind == LFX_LZ77_LAZY || (out->tune.lazy && !out->cost);
     out->auto_blocks = d.dynamic_huffman == LFX_HUFFMAN_AUTO && !d.no_compression;
     out->merge_blocks = d.block_merge == 1 && d.dynamic_huffman != 0 && !d.no_compression;
     PlanOpts &p = out->plan;
     p.block_size = d.block_size;
     p.dynamic_huffman = d.dynamic_huffman != 0;
     p.no_compression = d.no_compression != 0;
-    p.lz77_kind = kind;                // (without the depth)
+    p.lz77_kind = out->cost ? (int)LFX_LZ77_LEVEL : kind;   // (without the depth; LFX_LZ77_COST buffers and flushes as its level does: the plan is kind 4's)
     p.window_size = d.window_size;
     p.max_length = d.max_length;
     p.zlib_sync = format == LFX_ZLIB && d.zlib_flush_mode == LFX_FLUSH_SYNC;
     if (d.block_size == 0) return LFX_E_ARG;  // `while len >= 0` never terminates in the reference
     if (d.max_length < 3) return LFX_E_ARG;   // default.rs:125 underflows
-    if (lz77_chain_stage(kind) && (out->chain_depth == 0 || ((uint32_t)d.lz77_kind >> 16) != 0)) return LFX_E_ARG;
+    if (kind == 5) return LFX_E_ARG;           // no kind: the number between LFX_LZ77_LEVEL and LFX_LZ77_COST names no encoder
+    if (lz77_runs_chain(kind) && (out->chain_depth == 0 || ((uint32_t)d.lz77_kind >> 16) != 0)) return LFX_E_ARG;
     if (d.block_merge > 1) return LFX_E_ARG;
     return LFX_OK;
 }
@@ -165,6 +173,10 @@ enum DictKind { DICT_NONE, DICT_PLAIN, DICT_CHAIN };     // lfx_dict_new / lfx_d
 inline int encode_served(EncodeEntry e, const EncodeSpec &sp, DictKind dict, const char **why) {
     const bool chained = lz77_chain_stage(sp.plan.lz77_kind), level = sp.plan.lz77_kind == LFX_LZ77_LEVEL;
     *why = e == ENC_SHARD && sp.o.no_compression ? "sharded encode of stored blocks is not supported (their size depends on the bit phase)"
+         // LFX_LZ77_COST (§27; its plan is kind 4's, so its rows stand in front of LFX_LZ77_LEVEL's): a second parse would list
+         // the encode index's candidates twice
+         : e == ENC_SHARD && sp.cost ? "lz77_kind: the N-GPU encode does not serve LFX_LZ77_COST"
+         : e == ENC_INDEX && sp.cost ? "lz77_kind: lfx_encode_index_device does not serve LFX_LZ77_COST (its second parse would list the candidates twice)"
          : e == ENC_SHARD && level ? "lz77_kind: the N-GPU encode does not serve LFX_LZ77_LEVEL"
          : e == ENC_SHARD && chained ? (sp.lazy ? "lz77_kind: the N-GPU encode does not serve LFX_LZ77_LAZY" : "lz77_kind: the N-GPU encode does not serve LFX_LZ77_CHAIN")
          : e == ENC_SHARD && sp.auto_blocks ? "dynamic_huffman: the N-GPU encode does not serve LFX_HUFFMAN_AUTO (a stored block's size depends on the bit phase)"
@@ -175,6 +187,7 @@ inline int encode_served(EncodeEntry e, const EncodeSpec &sp, DictKind dict, con
          : e == ENC_MEMBERS && sp.merge_blocks ? "block_merge: lfx_encode_members_* does not serve block_merge (a member's blocks are laid out from the host plan)"
          : e == ENC_STREAM && sp.merge_blocks ? "block_merge: the stream encoder does not serve block_merge (a merge across a flush would break what a flush promises)"
          // ChainLz77Encoder and LazyLz77Encoder have no chain behind a plain dictionary's candidate (§19); a chain dictionary brings its own
+         : dict == DICT_PLAIN && sp.cost ? "lz77_kind: LFX_LZ77_COST with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"
          : dict == DICT_PLAIN && level ? "lz77_kind: LFX_LZ77_LEVEL with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"
          : dict == DICT_PLAIN && chained ? (sp.lazy ? "lz77_kind: LFX_LZ77_LAZY with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)"
                                                     : "lz77_kind: LFX_LZ77_CHAIN with a preset dictionary is not supported (a dictionary made by lfx_dict_new_chain serves it)")

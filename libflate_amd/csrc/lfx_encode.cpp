@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "lfx_chain.h"
+#include "lfx_cost.h"
 #include "lfx_dict_enc.h"
 #include "lfx_encode_stages.h"
 
@@ -67,6 +68,7 @@ struct EncCall {
     bool lazy;                    // LazyLz77Encoder: the chain stage keeps the lengths and demotes behind them (§20)
     bool tuned;                   // LFX_LZ77_LEVEL (§23): the chain stage's tuned instances, with ...
     LevelTune tune;               // ... the level's nice, max_lazy and too_far (chain_depth and lazy above are the level's too)
+    bool cost;                    // LFX_LZ77_COST (§27): the level's candidates, no lazy demotion; a first pass for the block's code, the cost kernel, the parse again
     bool auto_blocks;             // LFX_HUFFMAN_AUTO (§22): block_choose_kernel behind the Huffman kernel; any other call: no launch, no buffer
     bool merge_blocks;            // block_merge (§24): block_merge_kernel and a second Huffman pass behind the first; any other call: no launch, no buffer
     EncodeGeom g;
@@ -418,6 +420,53 @@ int stage_parse(Ctx *c, EncCall &k) {
     return LFX_OK;
 }
 
+// CostLz77Encoder, behind the chain stage — cd2 and d_len hold the level's candidates, nothing demoted — and in
+// front of the call's parse:
+//   [ parse → plain Huffman ]  the first pass: the greedy walk over the undemoted candidates, the blocks' symbol counts and
+//                              their plain dynamic codes (no block_merge, no LFX_HUFFMAN_AUTO: d_bc is all the cost kernel
+//                              reads of it).  Skipped under fixed codes, whose widths the kernel knows.
+//   cost_demote                cd ← cd2 without the candidates that lose by cost (out of place, lfx_cost.hip): the array the
+//                              match stage wrote, free since the chain stage read it.  The call's parse reads it.
+// Between the passes, everything the parse and the histogram accumulate:
+//   d_hist / d_hist_chunk      counted by atomic adds: cleared HERE, the one buffer that needs it;
+//   d_ucount                   the match stage's open positions per segment: no parse touches it;
+//   d_ncodes, d_segtmp         the code counts and the six per-segment words: every walk and every fold stores all of them
+//                              anew (the debug dump of a segment has always walked twice);
+//   d_vis                      the visited masks: the walk stores every word of every segment, zero where nothing is visited;
+//   d_stage, d_codes           stored, never combined; a shorter second list leaves stale words behind its end, unread;
+//   the result record          its parse-side field is match_flags, the MATCH stage's verdict, which the second walk must
+//                              still see; end_bit, status and the checksums are written behind the prepare stage.
+// The checksum forks once, in the call's parse; with_match_fallback re-runs the prepare stage and with it all of this.
+int stage_cost(Ctx *c, EncCall &k) {
+    const EncView &v = k.v;
+    hipStream_t st = c->stream;
+    const bool fixed = !k.po.dynamic_huffman;
+    cost_items(k.plan.chunks, c->cost_items);
+    if (!fixed && !c->cost_items.empty()) {
+        if (int rc = parse_walk(c, k, v.d_match_flags, nullptr)) return rc;
+        if (int rc = parse_chain(c, k, true)) return rc;
+        if (!k.g.fused_hist) LAUNCH_TRY(launch_histogram(st, v.chunks, c->cur_nchunks, k.g.split, v.codes, v.ncodes, v.hist));
+        if (k.pack_by_chunk)
+            LAUNCH_TRY(launch_huffman_chunks(st, v.blocks, c->cur_nblocks, c->cur_nchunks, v.hist, (BlockCodes *)c->d_bc.p,
+                                             (uint64_t *)c->d_chunk_bits.p, nullptr));
+        else
+            LAUNCH_TRY(launch_huffman(st, v.blocks, c->cur_nblocks, v.hist, (BlockCodes *)c->d_bc.p, nullptr));
+        HIP_TRY(hipMemsetAsync(v.hist, 0, 4ull * SYM_ROW * (k.pack_by_chunk ? (size_t)c->cur_nchunks : std::max<size_t>(c->cur_nblocks, 1)), st));
+    }
+    c->phase("lz77_cost_pass1");
+    if (!c->cost_items.empty()) {
+        const size_t bytes = sizeof(CostItem) * c->cost_items.size();
+        if (int rc = c->d_cost_items.reserve(bytes)) return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_cost_items.p, c->cost_items.data(), bytes, hipMemcpyHostToDevice, st));
+        LAUNCH_TRY(launch_cost_demote(st, k.d_in, v.chunks, (const CostItem *)c->d_cost_items.p, (uint32_t)c->cost_items.size(),
+                                      (const BlockCodes *)c->d_bc.p, fixed, (const uint8_t *)c->d_len.p, (const uint16_t *)c->d_cd2.p,
+                                      (uint16_t *)c->d_cd.p));
+        k.v.cd = (uint16_t *)c->d_cd.p;
+    }
+    c->phase("lz77_cost_demote");
+    return LFX_OK;
+}
+
 // the container checksum reads only the input: it runs on the side stream, beside the parse's chaining kernels (one wavefront
 // per segment, a handful of steps each) and the one-workgroup-per-block Huffman kernel, which leave most of the GPU idle
 // (forked: its first half went there behind the walk kernel, stage_parse).  The join: ev_join, waited for behind the Huffman kernel.
@@ -492,7 +541,7 @@ int encode_prepare(Ctx *c, const Plan &plan, const EncodeSpec &sp, const uint8_t
     c->phase("start");
     EncCall k{plan, sp.plan, d_in, n, ck_mode, hc, dict && dict->usable && !hc ? dict : nullptr, c->force_match_v1 || c->diag.match_v1,
               hc ? 0u : sp.chain_depth,     // (a caller's own code words switch the chain stage off)
-              sp.lazy, sp.tuned, sp.tune, sp.auto_blocks, sp.merge_blocks,
+              sp.lazy, sp.tuned, sp.tune, sp.cost && !hc, sp.auto_blocks, sp.merge_blocks,
               encode_geometry(plan, hc != nullptr, (uint32_t)std::max(c->n_cu, 1), c->diag.hist_separate, c->diag.pack_by_chunk)};
     if (k.g.err) { c->set_error(geom_error(k.g.err)); return LFX_E_ARG; }
     k.pack_by_chunk = k.g.pack_by_chunk && !k.auto_blocks && !k.merge_blocks && !c->idx_enc;
@@ -514,6 +563,7 @@ int encode_prepare(Ctx *c, const Plan &plan, const EncodeSpec &sp, const uint8_t
         rc = stage_match(c, k);
         if (!rc && k.dict) rc = stage_dict(c, k);
         if (!rc && k.chain_depth) rc = stage_chain(c, k);
+        if (!rc && k.cost) rc = stage_cost(c, k);
         if (!rc) rc = stage_parse(c, k);
     }
     if (rc) return rc;

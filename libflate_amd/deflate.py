@@ -103,7 +103,7 @@ def _compress(fmt, data, zdict, options, context, lz77=None, level=None, merge_b
     own = not hasattr(zdict, "handle")
     # (bytes: the dictionary is made here, with a chain of its own when the parse is a chained one; a caller's
     # Dictionary is taken as it was made)
-    chained = opts is not None and (opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL)
+    chained = opts is not None and (opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL, _ffi.LZ77_COST)
     d = Dictionary(zdict, ctx, chain=chained) if own else zdict
     try:
         return ctx.encode_dict_host(fmt, d, data, opts)
@@ -120,7 +120,7 @@ def _compress_batch(fmt, records, zdict, options, context, lz77=None, level=None
         options = (options if options is not None else EncodeOptions()).merge_blocks()
     opts = options._to_c() if options is not None else None
     own = zdict is not None and not hasattr(zdict, "handle")
-    chained = opts is not None and (opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL)
+    chained = opts is not None and (opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL, _ffi.LZ77_COST)
     d = Dictionary(zdict, ctx, chain=chained) if own else zdict     # (as in _compress)
     try:
         return ctx.encode_batch_packed_host(fmt, records, d, opts)

@@ -170,6 +170,20 @@ class LevelLz77Encoder:
                 "window_size": self._window, "max_length": self._max_length}
 
 
+class CostLz77Encoder(LevelLz77Encoder):
+    """This library's own Lz77Encode (LFX_LZ77_COST): LevelLz77Encoder(level)'s candidates, with the lazy rule
+    replaced by a choice by cost in bits — at every position "literal" or "the level's match", whichever makes the rest of
+    its segment cheaper under the block's own Huffman code, which the same call builds in a first pass (include/lfx.h).  Smaller
+    output than LevelLz77Encoder at the same level for a second parse and a first Huffman pass.  Accepted wherever
+    LevelLz77Encoder is, except Index.encode and the N-GPU encode; like it, it has no encode / flush of its own."""
+
+    def compression_level(self):
+        return CompressionLevel.BEST
+
+    def _opts(self):
+        return dict(super()._opts(), lz77_kind=_ffi.LZ77_COST | (self._level if 0 <= self._level <= 255 else 255) << 8)
+
+
 class NoCompressionLz77Encoder:
     """lib.rs:111-145: every byte a literal (still Huffman coded by the block encoder)."""
 

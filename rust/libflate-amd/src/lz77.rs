@@ -116,6 +116,11 @@ impl<E: Lz77Encode + 'static> GpuLz77 for E {
             o.window_size = c.window_size as u32;
             o.max_length = c.max_length as u32;
             true
+        } else if let Some(c) = any.downcast_ref::<CostLz77Encoder>() {
+            o.lz77_kind = ffi::lfx_lz77_cost_n(c.level);          // (a level outside 1..=9: LFX_E_ARG from the encoder's constructor)
+            o.window_size = c.window_size as u32;
+            o.max_length = c.max_length as u32;
+            true
         } else {
             // only the container header looks at these two (zlib.rs:212-220, gzip.rs:684)
             o.lz77_kind = ffi::LFX_LZ77_DEFAULT;
@@ -289,6 +294,25 @@ impl Lz77Encode for LevelLz77Encoder {
     fn compression_level(&self) -> CompressionLevel {
         match self.level { 0..=3 => CompressionLevel::Fast, 4..=6 => CompressionLevel::Balance, _ => CompressionLevel::Best }
     }
+    fn window_size(&self) -> u16 { self.window_size }
+}
+
+/// This library's own `Lz77Encode` (`LFX_LZ77_COST`, include/lfx.h): `LevelLz77Encoder(level)`'s candidates with
+/// the lazy rule replaced by a choice by cost in bits under the block's own Huffman code, which the same call builds in a first
+/// pass.  Like `LevelLz77Encoder` it only configures the device pipeline; `Lz77Encode::encode` / `flush` panic.
+#[derive(Debug, Clone)]
+pub struct CostLz77Encoder { level: u8, window_size: u16, max_length: u16 }
+impl CostLz77Encoder {
+    /// `level`: 1..=9 (any other is refused when the encoder is made: `LFX_E_ARG`)
+    pub fn new(level: u8) -> Self { CostLz77Encoder { level, window_size: MAX_WINDOW_SIZE, max_length: MAX_LENGTH } }
+    pub fn with_window_size(self, window_size: u16) -> Self { CostLz77Encoder { window_size: std::cmp::min(window_size, MAX_WINDOW_SIZE), ..self } }
+    pub fn with_max_length(self, max_length: u16) -> Self { CostLz77Encoder { max_length: std::cmp::min(max_length, MAX_LENGTH), ..self } }
+    pub fn level(&self) -> u8 { self.level }
+}
+impl Lz77Encode for CostLz77Encoder {
+    fn encode<S: Sink>(&mut self, _buf: &[u8], _sink: S) { panic!("libflate-amd: CostLz77Encoder runs inside the encoders only (EncodeOptions::with_lz77)") }
+    fn flush<S: Sink>(&mut self, _sink: S) { panic!("libflate-amd: CostLz77Encoder runs inside the encoders only (EncodeOptions::with_lz77)") }
+    fn compression_level(&self) -> CompressionLevel { CompressionLevel::Best }
     fn window_size(&self) -> u16 { self.window_size }
 }
 
