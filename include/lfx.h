@@ -861,6 +861,39 @@ int lfx_encode_batch_packed_device(lfx_ctx *c, int format, const lfx_encode_opts
                                    uint32_t align, void *d_out, uint64_t cap,
                                    uint64_t *out_off, uint64_t *out_len, uint64_t *total,
                                    void *d_table /* optional, device: count x {off, len} as uint64 pairs */);
+/* The inverse: a batch decoded back to back, placed by the decoded sizes.  The caller names no place and no
+ * capacity for any stream.  Let size[i], sstat[i], scons[i] be what lfx_decode_batch_size_device reports for stream i — with
+ * `dict`, what the same size walk reports with the dictionary's bytes as history in front of the streams that read it.
+ * Sizes and layout.  §26's, by a device scan over the sizes:
+ *   out_off[0] = 0, out_off[i + 1] = round_up(out_off[i] + size[i], align), *total = out_off[count - 1] + size[count - 1]
+ * (the tail is not rounded).  align: a power of two in 1..4096, else LFX_E_ARG.  count == 0: LFX_OK, *total = 0.
+ * Decode.  Stream i is decoded exactly as lfx_decode_batch_device — with `dict`, lfx_decode_batch_dict_device — decodes it with
+ * out_off[i] as above and out_cap[i] = size[i]: d_out[out_off[i], +out_len[i]), out_len[i] and status[i] are that call's, on
+ * damaged streams too (a stream that fails keeps the bytes it produced before the fault; a checksum mismatch is reported with
+ * all of its bytes in place).  consumed[i] = scons[i].  The return value is LFX_OK with the per-stream verdicts in status[];
+ * lfx_ctx_last_error is the first failed stream's message.  No byte of d_out outside the slots [out_off[i], out_off[i] + size[i])
+ * is written — gap bytes keep their values — and nothing at or behind cap.
+ * Capacity.  *total > cap: LFX_E_NOSPACE; out_off[], *total and d_table hold the layout, out_len[i] = size[i], status[i] =
+ * sstat[i], consumed[i] = scons[i], d_out is untouched and the context is usable for the next call.  d_out == NULL with
+ * cap == 0 is therefore the size query (d_out == NULL with any other cap: LFX_E_ARG); where nothing is to be written
+ * (*total == 0) it answers LFX_OK with the same fields.
+ * Inputs.  The streams are d_in[off, +len): EITHER in_off and in_len (host arrays) with d_in_table NULL, OR d_in_table (device
+ * memory, 8-byte aligned: count pairs {off, len} of uint64_t, what lfx_encode_batch_packed_device writes to its d_table) with
+ * in_off and in_len NULL — the call copies the table itself; both, or neither, or one host array alone: LFX_E_ARG.
+ * dict (NULL: none): only with LFX_ZLIB or LFX_DEFLATE, and a dictionary of this context, else LFX_E_ARG; a zlib stream without
+ * FDICT in the batch is decoded without it, one with another DICTID fails alone ("Dictionary mismatch").  out_off, out_len,
+ * consumed, status and total are HOST memory and may each be NULL; d_table (NULL: none; device memory, 8-byte aligned): count
+ * pairs {out_off, size}.  A NULL context: LFX_E_DEVICE, nothing written.
+ * The container headers are parsed once for both halves, and no scratch grows with the output (rule 6 of the size calls).
+ * Not covered: multi-member gzip, the seek index, the N-GPU calls.  There is no host form: Context.decode_batch_packed_host
+ * (Python) stages the records as encode_batch_packed_host does. */
+int lfx_decode_batch_packed_device(lfx_ctx *c, int format, const lfx_dict *dict /* NULL: none */, uint32_t count,
+                                   const void *d_in,
+                                   const uint64_t *in_off, const uint64_t *in_len,   /* host, or both NULL ...        */
+                                   const void *d_in_table,                            /* ... then device: count x {off, len} */
+                                   uint32_t align, void *d_out, uint64_t cap,
+                                   uint64_t *out_off, uint64_t *out_len, uint64_t *consumed, int32_t *status,
+                                   uint64_t *total, void *d_table /* optional, device */);
 
 /* ---- a chain dictionary: LFX_LZ77_CHAIN and LFX_LZ77_LAZY through a preset dictionary ----
  * lfx_dict_new_chain makes a dictionary that also carries the hash chain of its own tail.  With it lfx_encode_dict_device,

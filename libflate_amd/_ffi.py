@@ -47,7 +47,7 @@ EXPORTS = [
     "lfx_dict_new", "lfx_dict_id", "lfx_dict_free", "lfx_decode_dict_device", "lfx_decode_dict_host",
     "lfx_decode_batch_dict_device", "lfx_decoder_set_dict",
     "lfx_encode_dict_bound", "lfx_encode_dict_device", "lfx_encode_dict_host", "lfx_encode_batch_dict_device",
-    "lfx_dict_new_chain", "lfx_encoder_new_dict", "lfx_encode_batch_packed_device",
+    "lfx_dict_new_chain", "lfx_encoder_new_dict", "lfx_encode_batch_packed_device", "lfx_decode_batch_packed_device",
 ]
 
 
@@ -219,6 +219,7 @@ def lib():
     L.lfx_encode_batch_dict_device.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lfx_encode_batch_packed_device.argtypes = [vp, i32, C.POINTER(EncodeOpts), C.POINTER(Schedule), vp, u32, vp, vp, vp, u32, vp, u64,
                                                  vp, vp, C.POINTER(u64), vp]
+    L.lfx_decode_batch_packed_device.argtypes = [vp, i32, vp, u32, vp, vp, vp, vp, u32, vp, u64, vp, vp, vp, vp, C.POINTER(u64), vp]
     L.lfx_decode_members_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,
                                             C.POINTER(u32)]
     L.lfx_decode_members_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(Member), u32,

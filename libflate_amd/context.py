@@ -465,6 +465,61 @@ class Context:
         out = d_out[:total].cpu().numpy().tobytes()
         return [out[o:o + n] for o, n in layout]
 
+    # ---- a batch decoded back to back (lfx_decode_batch_packed_device) ------------------
+    def decode_batch_packed_device(self, fmt, d_in, in_offs, in_lens, d_out, cap, *, zdict=None, align=1, d_in_table=None,
+                                   d_table=None):
+        """lfx_decode_batch_packed_device: the streams d_in[in_offs[i], +in_lens[i]) decoded back to back into d_out[0, cap),
+        every stream's start a multiple of `align`, placed on the device by their decoded sizes; zdict: one Dictionary for all
+        of them (zlib / raw DEFLATE).  d_in_table: device memory holding the {off, len} pairs instead — what
+        encode_batch_packed_device wrote to its d_table; in_offs then only says how many streams there are (a count, or a list
+        whose length is the count, or None with in_lens a count).  d_table: device memory for count {off, size} pairs, or None
+        → (rc, out_offs, out_lens, consumed, statuses, total); rc is LFX_OK (the verdicts are in statuses) or LFX_E_NOSPACE
+        (total > cap: nothing was decoded, the layout and the sizes say what it needs; d_out = None with cap = 0 is the size
+        query), anything else raises"""
+        if d_in_table is not None:
+            n = in_offs if in_offs is not None else in_lens
+            k = int(n) if isinstance(n, int) else len(n)
+            io = il = None
+        else:
+            k = len(in_offs)
+            a = lambda v: (C.c_uint64 * max(k, 1))(*v)
+            io, il = a(in_offs), a(in_lens)
+        u64s = lambda: (C.c_uint64 * max(k, 1))()
+        oo, ol, used, st, total = u64s(), u64s(), u64s(), (C.c_int32 * max(k, 1))(), C.c_uint64(0)
+        rc = _ffi.lib().lfx_decode_batch_packed_device(self._h, fmt, self._dict_handle(zdict), k, d_in, io, il, d_in_table, align,
+                                                       d_out, cap, oo, ol, used, st, C.byref(total), d_table)
+        if rc and rc != _ffi.E_NOSPACE:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return rc, list(oo[:k]), list(ol[:k]), list(used[:k]), list(st[:k]), total.value
+
+    def decode_batch_packed_host(self, fmt, records, zdict=None):
+        """a list of streams (bytes) → (the list of their decoded bytes, statuses): one upload, the size query (d_out = None,
+        cap = 0) for `total`, one allocation of exactly that, the decode, one download.  A failed stream's entry holds what it
+        produced before the fault, and last_error() is the first failed stream's message."""
+        import torch
+        records = [bytes(r) for r in records]
+        if not records:
+            return [], []
+        offs, at = [], 0
+        for r in records:
+            offs.append(at)
+            at += len(r)
+        lens = [len(r) for r in records]
+        dev = torch.device("cuda", self.device)
+        d_in = torch.frombuffer(bytearray(b"".join(records) or b"\0"), dtype=torch.uint8).to(dev)
+        torch.cuda.current_stream(dev).synchronize()
+        rc, _offs, _lens, _used, st, total = self.decode_batch_packed_device(fmt, d_in.data_ptr(), offs, lens, None, 0, zdict=zdict)
+        if total == 0:
+            return [b""] * len(records), st
+        d_out = torch.empty(total, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        rc, out_offs, out_lens, _used, st, total = self.decode_batch_packed_device(fmt, d_in.data_ptr(), offs, lens, d_out.data_ptr(),
+                                                                                 total, zdict=zdict)
+        if rc:
+            raise _ffi.LfxError(rc, self.last_error())
+        out = d_out.cpu().numpy().tobytes()
+        return [out[o:o + n] for o, n in zip(out_offs, out_lens)], st
+
 
 class Dictionary:
     """A preset dictionary (lfx_dict): what zlib.compressobj(zdict=...) was given.  The last 32 KiB are the

@@ -19,6 +19,7 @@
 #include "lfx_index.h"
 #include "lfx_bgzf.h"
 #include "lfx_dict.h"
+#include "lfx_batch_unpack.h"
 
 static_assert(offsetof(lfx::DecStream, out_off) == 16 && sizeof(lfx::DecStream) % 8 == 0, "checksum_ranges stride");
 static_assert(offsetof(lfx::InflateResult, out_len) == 8 && sizeof(lfx::InflateResult) % 8 == 0, "checksum_ranges stride");
@@ -30,6 +31,9 @@ using namespace lfx;
 namespace {
 
 int size_member(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t off0, MemberResult &mr);
+int batch_size_walk(Ctx *c, int format, uint32_t count, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len,
+                    const std::vector<DecHeader> &hdrs, std::vector<InflateResult> &res, std::vector<uint64_t> &used_out,
+                    const lfx_dict *dict = nullptr);
 
 // the container checksum of the member's output d_out[0, mr.out_len) against the trailer at d_in[tpos, tpos + need)
 int verify_trailer(Ctx *c, int format, const uint8_t *d_in, uint64_t tpos, uint64_t need, const uint8_t *d_out, const MemberResult &mr,
@@ -734,22 +738,21 @@ static int batch_fast(Ctx *c, const uint8_t *d_in, uint64_t n_in, uint8_t *d_out
 }  // namespace lfx
 
 namespace {
-// the body of lfx_decode_batch_device: res[i] = stream i's verdict (trailer included), used[i] = its bytes consumed
-int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uint64_t *in_off, const uint64_t *in_len,
-                 void *d_out, const uint64_t *out_off, const uint64_t *out_cap, std::vector<InflateResult> &res,
-                 std::vector<uint64_t> *used = nullptr, const lfx_dict *dict = nullptr) {
+// behind the headers of a batch decode, in parse_headers' extra room: each stream's checksums and its bytes consumed
+constexpr size_t batch_extra_bytes(uint32_t count) { return 16ull * count + 64; }
+
+// The decode half of a batch: the streams placed (out_off / out_cap, here and in d_streams) and their headers parsed (hdrs, and
+// d_hdrs with batch_extra_bytes of room behind them) → res[i] = stream i's verdict (trailer included), used[i] = its bytes
+// consumed.
+int decode_batch_placed(Ctx *c, int format, uint32_t count, const void *d_in, const uint64_t *in_off, const uint64_t *in_len,
+                        void *d_out, const uint64_t *out_off, const uint64_t *out_cap, const std::vector<DecHeader> &hdrs,
+                        DecStream *d_streams, DecHeader *d_hdrs, std::vector<InflateResult> &res, std::vector<uint64_t> *used,
+                        const lfx_dict *dict) {
     hipStream_t st = c->stream;
-    std::vector<DecStream> streams(count);
-    for (uint32_t i = 0; i < count; i++) streams[i] = DecStream{in_off[i], in_len[i], out_off[i], out_cap[i]};
     int rc;
-    std::vector<DecHeader> hdrs;
-    DecStream *d_streams;
-    DecHeader *d_hdrs;       // (behind the headers: each stream's checksums and its bytes consumed)
-    if ((rc = parse_headers(c, format, (const uint8_t *)d_in, streams, hdrs, 16ull * count + 64, &d_streams, &d_hdrs, dict))) return rc;
     uint32_t *d_crc = (uint32_t *)(d_hdrs + count);
     uint32_t *d_adler = d_crc + count;
     uint64_t *d_consumed = (uint64_t *)(d_adler + count);
-    c->phase("headers");
     std::vector<InflateJob> jobs(count);
     for (uint32_t i = 0; i < count; i++) {
         if (c->idx && (format == LFX_DEFLATE || hdrs[i].status == 0)) {   // (an index build: a member's first block)
@@ -814,6 +817,21 @@ int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uin
     HIP_TRY(hipStreamSynchronize(st));
     c->phase("verify");
     return LFX_OK;
+}
+
+// the body of lfx_decode_batch_device: the headers, then the decode half at the caller's places
+int decode_batch(Ctx *c, int format, uint32_t count, const void *d_in, const uint64_t *in_off, const uint64_t *in_len,
+                 void *d_out, const uint64_t *out_off, const uint64_t *out_cap, std::vector<InflateResult> &res,
+                 std::vector<uint64_t> *used = nullptr, const lfx_dict *dict = nullptr) {
+    std::vector<DecStream> streams(count);
+    for (uint32_t i = 0; i < count; i++) streams[i] = DecStream{in_off[i], in_len[i], out_off[i], out_cap[i]};
+    int rc;
+    std::vector<DecHeader> hdrs;
+    DecStream *d_streams;
+    DecHeader *d_hdrs;
+    if ((rc = parse_headers(c, format, (const uint8_t *)d_in, streams, hdrs, batch_extra_bytes(count), &d_streams, &d_hdrs, dict))) return rc;
+    c->phase("headers");
+    return decode_batch_placed(c, format, count, d_in, in_off, in_len, d_out, out_off, out_cap, hdrs, d_streams, d_hdrs, res, used, dict);
 }
 }  // namespace
 
@@ -1494,7 +1512,7 @@ int huff_consumed(Ctx *c, const uint8_t *d_in, const std::vector<HuffProbe> &pro
         for (uint64_t k = std::max<uint64_t>((before + 7) / 8, (p.r.blk_start_bit + 7) / 8); k < hi; k++) {
             InflateJob j{};
             j.in_off = p.in_off; j.in_len = k; j.start_bit = p.r.blk_start_bit;
-            j.out_cap = ~0ull; j.hist_avail = p.r.blk_out_start; j.flags = JOB_COUNT_ONLY;
+            j.out_cap = ~0ull; j.hist_avail = p.hist + p.r.blk_out_start; j.flags = JOB_COUNT_ONLY;
             jobs.push_back(j);
             owner.push_back(i);
         }
@@ -1651,10 +1669,37 @@ extern "C" int lfx_decode_batch_size_device(lfx_ctx *cc, int format, uint32_t co
     std::vector<DecHeader> hdrs(count, DecHeader{});
     if (format != LFX_DEFLATE && (rc = parse_headers(c, format, d_in, streams, hdrs))) return rc;
     c->phase("headers");
+    std::vector<InflateResult> res;
+    std::vector<uint64_t> used;
+    if ((rc = batch_size_walk(c, format, count, d_in, in_off, in_len, hdrs, res, used))) return rc;
+    int worst = LFX_OK;
+    for (uint32_t i = 0; i < count; i++) {
+        const InflateResult &r = res[i];
+        if (out_len) out_len[i] = r.out_len;
+        if (consumed) consumed[i] = used[i];
+        const int s = map_status(r.status);
+        if (status) status[i] = s;
+        if (s != LFX_OK && worst == LFX_OK) { worst = s; c->set_error(format_error(r.err, r.a0, r.a1)); }
+    }
+    c->phase("trailers");
+    return LFX_OK;   // per-stream results are in status[]
+} LFX_ABI_CATCH
+
+namespace {
+// The size half of a batch behind its headers: res[i] = what the decode of stream i would report with room enough — status,
+// error, out_len — and used[i] = its bytes consumed, the trailer's presence included (verify_trailers_kernel without the
+// checksum comparison).  The walker for every stream of at least 64 bytes whose header stands, the count-only serial kernel
+// for the rest, the probes behind a Huffman verdict.  dict (lfx_decode_batch_packed_device): the streams that read it — raw
+// DEFLATE always, zlib when its header said so (HDR_DICT) — have its usable bytes as history in front of their first byte.
+int batch_size_walk(Ctx *c, int format, uint32_t count, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len,
+                    const std::vector<DecHeader> &hdrs, std::vector<InflateResult> &res, std::vector<uint64_t> &used_out,
+                    const lfx_dict *dict) {
+    int rc;
+    auto hist_of = [&](uint32_t i) -> uint64_t { return dict && (format == LFX_DEFLATE || (hdrs[i].flags & HDR_DICT)) ? dict->usable : 0; };
     uint64_t n_in = 0;
     for (uint32_t i = 0; i < count; i++) n_in = std::max(n_in, in_off[i] + in_len[i]);
     // ---- the walker for every stream of at least 64 bytes whose header stands
-    std::vector<InflateResult> res(count, InflateResult{});
+    res.assign(count, InflateResult{});
     std::vector<uint8_t> settled(count, 0);
     std::vector<WalkJob> wj;
     std::vector<uint32_t> widx;
@@ -1668,7 +1713,7 @@ extern "C" int lfx_decode_batch_size_device(lfx_ctx *cc, int format, uint32_t co
     uint64_t walk_blocks = 0;
     for (size_t q = 0; q < wj.size(); q++) {
         walk_blocks += wr[q].nblocks;
-        if (wr[q].status != WALK_FINAL || !walk_settled(wr[q], 0)) continue;
+        if (wr[q].status != WALK_FINAL || !walk_settled(wr[q], hist_of(widx[q]))) continue;
         InflateResult &o = res[widx[q]];
         o.end_bit = wr[q].end_bit - in_off[widx[q]] * 8;
         o.out_len = o.blk_out_start = wr[q].n_out;
@@ -1687,6 +1732,7 @@ extern "C" int lfx_decode_batch_size_device(lfx_ctx *cc, int format, uint32_t co
         j.in_len = hdrs[i].status != 0 ? 0 : in_len[i];     // (header failed: nothing to decode)
         j.start_bit = hdrs[i].deflate_off * 8;
         j.out_cap = ~0ull;
+        j.hist_avail = hist_of(i);          // (count-only: the reach of a match is judged, no byte of the history is read)
         j.flags = JOB_COUNT_ONLY;
         slow.push_back(j);
         slow_idx.push_back(i);
@@ -1697,7 +1743,10 @@ extern "C" int lfx_decode_batch_size_device(lfx_ctx *cc, int format, uint32_t co
     std::vector<HuffProbe> probes;
     std::vector<uint32_t> probe_idx;
     for (size_t q = 0; q < slow.size(); q++)
-        if (huff_verdict(sres[q])) { probes.push_back(HuffProbe{slow[q].in_off, slow[q].in_len, sres[q]}); probe_idx.push_back(slow_idx[q]); }
+        if (huff_verdict(sres[q])) {
+            probes.push_back(HuffProbe{slow[q].in_off, slow[q].in_len, sres[q], slow[q].hist_avail});
+            probe_idx.push_back(slow_idx[q]);
+        }
     std::vector<uint64_t> probe_used;
     if ((rc = huff_consumed(c, d_in, probes, probe_used))) return rc;
     std::vector<uint64_t> huff_used(count, ~0ull);
@@ -1705,8 +1754,8 @@ extern "C" int lfx_decode_batch_size_device(lfx_ctx *cc, int format, uint32_t co
     c->phase("serial");
     if (c->diag.debug) fprintf(stderr, "[lfx] batch size: %zu streams walked (%llu blocks), %zu through the exact path\n", wj.size(),
                                (unsigned long long)walk_blocks, slow.size());
-    // ---- the trailer's presence and `consumed` (verify_trailers_kernel without the checksum comparison)
-    int worst = LFX_OK;
+    // ---- the trailer's presence and `consumed`
+    used_out.assign(count, 0);
     for (uint32_t i = 0; i < count; i++) {
         InflateResult &r = res[i];
         const DecHeader &h = hdrs[i];
@@ -1722,14 +1771,109 @@ extern "C" int lfx_decode_batch_size_device(lfx_ctx *cc, int format, uint32_t co
                 else used += need;
             }
         }
-        if (out_len) out_len[i] = r.out_len;
-        if (consumed) consumed[i] = used;
-        const int s = map_status(r.status);
-        if (status) status[i] = s;
-        if (s != LFX_OK && worst == LFX_OK) { worst = s; c->set_error(format_error(r.err, r.a0, r.a1)); }
+        used_out[i] = used;
     }
-    c->phase("trailers");
-    return LFX_OK;   // per-stream results are in status[]
+    return LFX_OK;
+}
+}  // namespace
+
+// ---- the batch decoded back to back: the headers once, the size half, the layout from a device scan of the
+// decoded sizes (lfx_batch_unpack.hip), the decode half at those places
+extern "C" int lfx_decode_batch_packed_device(lfx_ctx *cc, int format, const lfx_dict *dict, uint32_t count, const void *d_in_,
+                                              const uint64_t *in_off, const uint64_t *in_len, const void *d_in_table, uint32_t align,
+                                              void *d_out, uint64_t cap, uint64_t *out_off, uint64_t *out_len, uint64_t *consumed,
+                                              int32_t *status, uint64_t *total, void *d_table) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (format < 0 || format > 2) return LFX_E_ARG;
+    if (dict && ((format != LFX_ZLIB && format != LFX_DEFLATE) || dict->c != c)) return LFX_E_ARG;
+    if (!bpack_align_ok(align)) { c->set_error("align: a power of two in 1..4096"); return LFX_E_ARG; }
+    if (!d_out && cap) { c->set_error("d_out: NULL with a capacity (the size query is d_out = NULL, cap = 0)"); return LFX_E_ARG; }
+    if ((((uintptr_t)d_table | (uintptr_t)d_in_table) & 7) != 0) { c->set_error("d_table and d_in_table must be 8-byte aligned"); return LFX_E_ARG; }
+    if (count > BPACK_MAX_COUNT) { c->set_error("count: too many streams for one call"); return LFX_E_ARG; }
+    if ((in_off == nullptr) != (in_len == nullptr) || (in_off && d_in_table) || (count && !in_off && !d_in_table)) {
+        c->set_error("the streams' places: either in_off and in_len (host) or d_in_table (device), not both");
+        return LFX_E_ARG;
+    }
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    c->n_ev = 0;
+    c->phase("start");
+    if (total) *total = 0;
+    if (!count) return LFX_OK;
+    const uint8_t *d_in = (const uint8_t *)d_in_;
+    int rc;
+    // ---- the streams' places in the input: the caller's arrays, or the device table copied here
+    std::vector<uint64_t> io(count), il(count);
+    if (d_in_table) {
+        std::vector<uint64_t> tab(2 * (size_t)count);
+        HIP_TRY(hipMemcpyAsync(tab.data(), d_in_table, 16ull * count, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t i = 0; i < count; i++) { io[i] = tab[2 * (size_t)i]; il[i] = tab[2 * (size_t)i + 1]; }
+    } else {
+        io.assign(in_off, in_off + count);
+        il.assign(in_len, in_len + count);
+    }
+    // ---- container headers, once for both halves; behind them the decode half's words, then the layout's scratch
+    const BunpackScratch w = bunpack_scratch(count);
+    std::vector<DecStream> streams(count);
+    for (uint32_t i = 0; i < count; i++) streams[i] = DecStream{io[i], il[i], 0, 0};
+    std::vector<DecHeader> hdrs;
+    DecStream *d_streams;
+    DecHeader *d_hdrs;
+    if ((rc = parse_headers(c, format, d_in, streams, hdrs, batch_extra_bytes(count) + 8 * w.words, &d_streams, &d_hdrs, dict))) return rc;
+    uint64_t *scratch = (uint64_t *)((uint8_t *)(d_hdrs + count) + batch_extra_bytes(count));
+    c->phase("headers");
+    // ---- the size half
+    std::vector<InflateResult> sres;
+    std::vector<uint64_t> sused;
+    if ((rc = batch_size_walk(c, format, count, d_in, io.data(), il.data(), hdrs, sres, sused, dict))) return rc;
+    std::vector<uint64_t> size(count);
+    for (uint32_t i = 0; i < count; i++) size[i] = sres[i].out_len;
+    uint64_t fits = 0;
+    if (!bpack_bound_sum(size.data(), count, align, &fits)) { c->set_error("the streams' decoded sizes exceed 64 bits"); return LFX_E_ARG; }
+    c->phase("sizes");
+    // ---- the layout: sizes up, three kernels, the pairs and the total back in one transfer
+    HIP_TRY(hipMemcpyAsync(scratch + w.size, size.data(), 8ull * count, hipMemcpyHostToDevice, st));
+    LAUNCH_TRY(launch_batch_unpack_layout(st, d_streams, count, align, scratch, (uint64_t *)d_table));
+    std::vector<uint64_t> back(bunpack_back_words(count));
+    HIP_TRY(hipMemcpyAsync(back.data(), scratch + w.pairs, 8ull * back.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->phase("layout");
+    std::vector<uint64_t> off(count);
+    for (uint32_t i = 0; i < count; i++) off[i] = back[2 * (size_t)i];
+    const uint64_t need = back[2 * (size_t)count];
+    if (out_off) std::copy(off.begin(), off.end(), out_off);
+    if (total) *total = need;
+    if (need > cap || !d_out) {
+        // nothing is decoded: the size half's verdicts (d_out == NULL with nothing to write is the size query's answer too)
+        int worst = LFX_OK;
+        for (uint32_t i = 0; i < count; i++) {
+            if (out_len) out_len[i] = size[i];
+            if (consumed) consumed[i] = sused[i];
+            const int s = map_status(sres[i].status);
+            if (status) status[i] = s;
+            if (s != LFX_OK && worst == LFX_OK) { worst = s; c->set_error(format_error(sres[i].err, sres[i].a0, sres[i].a1)); }
+        }
+        if (need <= cap) return LFX_OK;
+        c->set_error("output capacity too small (*total says what the streams need): no stream was decoded");
+        return LFX_E_NOSPACE;
+    }
+    // ---- the decode half at those places, out_cap = the size
+    std::vector<InflateResult> res;
+    if ((rc = decode_batch_placed(c, format, count, d_in, io.data(), il.data(), d_out, off.data(), size.data(), hdrs, d_streams, d_hdrs, res,
+                                  nullptr, dict)))
+        return rc;
+    int worst = LFX_OK;
+    for (uint32_t i = 0; i < count; i++) {
+        if (out_len) out_len[i] = res[i].out_len;
+        if (consumed) consumed[i] = sused[i];
+        const int s = map_status(res[i].status);
+        if (status) status[i] = s;
+        if (s != LFX_OK && worst == LFX_OK) { worst = s; c->set_error(format_error(res[i].err, res[i].a0, res[i].a1)); }
+    }
+    return LFX_OK;  // per-stream results are in status[]
 } LFX_ABI_CATCH
 
 extern "C" int lfx_decode_members_size_device(lfx_ctx *cc, const void *d_in, uint64_t n, uint64_t *out_len, uint64_t *consumed,

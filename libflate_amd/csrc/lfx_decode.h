@@ -150,4 +150,9 @@ int launch_member_emit(hipStream_t st, const uint8_t *in, uint64_t n, const uint
 int launch_verify_trailers(hipStream_t st, int format, uint32_t count, const uint8_t *in,
                            const DecStream *streams, const DecHeader *hdrs, InflateResult *results,
                            const uint32_t *crc, const uint32_t *adler, uint64_t *consumed);
+// lfx_decode_batch_packed_device (lfx_batch_unpack.hip): the device-wide scan of bpack_term(size, s, count, align)
+// over the decoded sizes at scratch[bunpack_scratch(count).size ..], then per stream streams[].out_off / out_cap = its offset
+// and size, the pairs {off, len} and behind them the total at scratch[.pairs ..] (and the pairs in `table`, device memory, when
+// it is not null).  scratch: bunpack_scratch(count).words 64-bit words (lfx_batch_unpack.h).
+int launch_batch_unpack_layout(hipStream_t st, DecStream *streams, uint32_t count, uint32_t align, uint64_t *scratch, uint64_t *table);
 }  // namespace lfx

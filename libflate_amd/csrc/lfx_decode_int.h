@@ -52,7 +52,7 @@ int run_jobs(Ctx *c, const uint8_t *d_in, uint8_t *d_out, const std::vector<Infl
 
 // `consumed` behind an "Invalid huffman coded stream" verdict of the exact kernel (lfx_decode.cpp): the decode, the size call and
 // the batch decode all report what the reference's reader has pulled from its input at that point
-struct HuffProbe { uint64_t in_off, in_len; InflateResult r; };
+struct HuffProbe { uint64_t in_off, in_len; InflateResult r; uint64_t hist = 0; /* bytes of history in front of the stream (a preset dictionary) */ };
 inline bool huff_verdict(const InflateResult &r) { return r.status == 1 && r.err == ERR_HUFF; }
 int huff_consumed(Ctx *c, const uint8_t *d_in, const std::vector<HuffProbe> &probes, std::vector<uint64_t> &used);
 

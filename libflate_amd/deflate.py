@@ -129,6 +129,60 @@ def _compress_batch(fmt, records, zdict, options, context, lz77=None, level=None
             d.close()
 
 
+def _decompress(fmt, data, zdict, context):
+    """the one-shot inverse of _compress: the size call in front for the capacity (lfx_decode_size_host), then decode_host;
+    with a dictionary decode_dict_host, whose capacity grows (the size calls take no dictionary)"""
+    from .context import Dictionary, default_context
+    ctx = context if context is not None else default_context()
+    data = bytes(data)
+    if zdict is None:
+        _rc, size, _used, _msg = ctx.decode_size_host(fmt, data)
+        rc, out, _used, msg = ctx.decode_host(fmt, data, cap=max(size, 1))
+    else:
+        own = not hasattr(zdict, "handle")
+        d = Dictionary(zdict, ctx) if own else zdict
+        try:
+            rc, out, _used, msg = ctx.decode_dict_host(fmt, d, data)
+        finally:
+            if own:
+                d.close()
+    if rc != _ffi.OK:
+        raise StreamError(rc, msg)
+    return out
+
+
+def _decompress_batch(fmt, records, zdict, context):
+    """the inverse of _compress_batch: Context.decode_batch_packed_host; the first failed record raises StreamError with its
+    index in front of the library's message"""
+    from .context import Dictionary, default_context
+    ctx = context if context is not None else default_context()
+    own = zdict is not None and not hasattr(zdict, "handle")
+    d = Dictionary(zdict, ctx) if own else zdict
+    try:
+        outs, statuses = ctx.decode_batch_packed_host(fmt, records, d)
+        msg = ctx.last_error()
+    finally:
+        if own:
+            d.close()
+    for i, st in enumerate(statuses):
+        if st != _ffi.OK:
+            raise StreamError(st, "record %d: %s" % (i, msg))
+    return outs
+
+
+def decompress(data, zdict=None, context=None):
+    """compress's inverse: one raw DEFLATE stream → its bytes.  zdict: the preset dictionary the stream was made with, bytes or
+    a libflate_amd.Dictionary (what zlib.decompressobj(wbits=-15, zdict=...) takes).  Raises StreamError where the stream fails."""
+    return _decompress(_ffi.DEFLATE, data, zdict, context)
+
+
+def decompress_batch(records, zdict=None, context=None):
+    """compress_batch's inverse: a list of raw DEFLATE streams (bytes) → the list of their bytes, in one upload, one decode of
+    all records placed back to back by their decoded sizes (lfx_decode_batch_packed_device) and one download.
+    One zdict serves every record.  A failed record raises StreamError; the message names its index."""
+    return _decompress_batch(_ffi.DEFLATE, records, zdict, context)
+
+
 def compress_batch(records, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False):
     """[compress(r, ...) for r in records] — a list of bytes to the list of their raw DEFLATE streams — in one upload, one
     encode of all records (lfx_encode_batch_packed_device) and one download of the streams packed back to

@@ -166,6 +166,19 @@ def compress_batch(records, options=None, context=None, lz77=None, level=None, m
     return _deflate._compress_batch(_ffi.GZIP, records, None, options, context, lz77, level, merge_blocks)
 
 
+def decompress(data, context=None):
+    """compress's inverse: one gzip member → its bytes, CRC-32 checked (bytes behind the member are left unread, as by
+    Decoder; concatenated members: decode_members).  Raises StreamError where the member fails."""
+    return _deflate._decompress(_ffi.GZIP, data, None, context)
+
+
+def decompress_batch(records, context=None):
+    """compress_batch's inverse: a list of gzip members (bytes) → the list of their bytes, in one upload, one decode of all
+    records placed back to back by their decoded sizes (lfx_decode_batch_packed_device) and one download.  A
+    failed record raises StreamError; the message names its index."""
+    return _deflate._decompress_batch(_ffi.GZIP, records, None, context)
+
+
 def encode_members(data, member_size=1 << 20, bgzf=False, options=None, context=None, lz77=None):
     """`data` as gzip members of member_size input bytes each, lying back to back: what decode_members, zcat and Python's gzip
     read, and with bgzf=True (member_size at most 65505; bgzip's own is _ffi.BGZF_MEMBER_SIZE = 65280) a BGZF file with its

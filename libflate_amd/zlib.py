@@ -54,6 +54,20 @@ def compress_batch(records, zdict=None, options=None, context=None, lz77=None, l
     return _deflate._compress_batch(_ffi.ZLIB, records, zdict, options, context, lz77, level, merge_blocks)
 
 
+def decompress(data, zdict=None, context=None):
+    """compress's inverse: one zlib stream → its bytes, Adler-32 checked.  zdict: the preset dictionary, bytes or a
+    libflate_amd.Dictionary (what zlib.decompressobj(zdict=...) takes); a stream without FDICT is decoded without it.  Raises
+    StreamError where the stream fails."""
+    return _deflate._decompress(_ffi.ZLIB, data, zdict, context)
+
+
+def decompress_batch(records, zdict=None, context=None):
+    """compress_batch's inverse: a list of zlib streams (bytes) → the list of their bytes, in one upload, one decode of all
+    records placed back to back by their decoded sizes (lfx_decode_batch_packed_device) and one download.  One
+    zdict serves every record.  A failed record raises StreamError; the message names its index."""
+    return _deflate._decompress_batch(_ffi.ZLIB, records, zdict, context)
+
+
 class Decoder(_DecoderBase):
     """zlib::Decoder (zlib.rs:284-410)."""
     FORMAT = _ffi.ZLIB

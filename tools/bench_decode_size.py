@@ -83,7 +83,8 @@ def main():
         yh = Y.lfx_ctx_new(0, C.byref(st))
         assert yh and st.value == 0
     else:
-        Y, yh = L, libflate_amd.Context(0).handle
+        yctx = libflate_amd.Context(0)      # (kept: a temporary's handle would be freed with it before the first call)
+        Y, yh = L, yctx.handle
     h = ctx.handle
     results = []
 
