@@ -956,6 +956,39 @@ lfx_dict *lfx_dict_new_chain(lfx_ctx *c, const void *bytes, uint64_t len, int on
 lfx_encoder *lfx_encoder_new_dict(lfx_ctx *c, int format, const lfx_encode_opts *o, const lfx_dict *dict,
                                   lfx_write_cb w, lfx_flush_cb f, void *user, int *status);
 
+/* ---- training a preset dictionary from sample records ----
+ * zlib has no trainer; this one is a simplified FASTCOVER, defined here and in tests/dict_train_model.py (numpy), which the
+ * device result equals byte for byte.  The result is what lfx_dict_new / lfx_dict_new_chain take.
+ *
+ *  Inputs.  `count` records in one buffer, record i at [off[i], off[i] + len[i]); off and len are HOST arrays.  The records must
+ *  not overlap and must come in ascending order of off (off[i] >= off[i - 1] + len[i - 1]), else LFX_E_ARG; gaps between them
+ *  are never read.  dict_size: the target size, 64..32768.  segment: the segment length k, 16..dict_size; 0 selects 128.  Fixed:
+ *  d = 8 (the d-mer), f = 20 (2^20 counters).  The records' positions in record order, concatenated, are the position space
+ *  [0, N); N > 2^31 is LFX_E_ARG.  Any other out-of-domain argument: LFX_E_ARG.  cap < dict_size: LFX_E_NOSPACE.  count == 0 or
+ *  N == 0: LFX_OK and *dict_len = 0.  A NULL context: LFX_E_DEVICE, nothing written.
+ *  Hash.  h(p) = (le64(bytes at p) * 0x9E3779B185EBCA87 mod 2^64) >> (64 - f), defined only where p + d does not pass the end of
+ *  p's record.  Nothing is read across a record's end or outside the records.
+ *  Counts.  freq[x] = the number of defined positions with h(p) == x, in 32 bits.
+ *  Epochs.  E = dict_size / k, rounded down; epoch e owns the positions [e * N / E, (e + 1) * N / E) (integer division).  A
+ *  position is a candidate when p + k stays inside its record.
+ *  Score.  The score of a candidate is the sum of freq[h(q)] over q in [p, p + k - d], read from the counters as they stand when
+ *  its epoch is decided, held in 32 bits: a sum above 2^32 - 1 counts as 2^32 - 1.  A non-candidate scores 0.  A d-mer that
+ *  occurs twice in one segment counts twice.
+ *  Selection.  Epochs are decided in order.  The pick of an epoch is the highest score, among equal scores the lowest position;
+ *  an epoch whose best score is 0 picks nothing.  After a pick freq[h(q)] = 0 for every q of the picked segment — what keeps the
+ *  same content from being picked twice.
+ *  Assembly.  The picks sorted by score ascending — the best segment last, at the shortest distances — among equal scores the
+ *  earlier epoch later.  The dictionary is the picked segments in that order, k bytes each: *dict_len is a multiple of k and may
+ *  be less than dict_size.  Only d_dict[0, *dict_len) is written.
+ *  The kernels run on the context's stream with no host wait between the epochs; the call returns when the dictionary is there.
+ *  The scratch (4 MiB of counters, 12 bytes per record, 4 bytes per 256 positions, the epoch step's prefix words: at most
+ *  512 x (4096 + k) x 8 bytes) is the context's and grows only. */
+int lfx_dict_train_device(lfx_ctx *c, const void *d_samples, uint32_t count, const uint64_t *off, const uint64_t *len,
+                          uint32_t dict_size, uint32_t segment, void *d_dict, uint64_t cap, uint64_t *dict_len);
+/* same, host buffers: the bytes from the first record's start to the last record's end are staged like lfx_encode_host's input */
+int lfx_dict_train_host(lfx_ctx *c, const void *samples, uint32_t count, const uint64_t *off, const uint64_t *len,
+                        uint32_t dict_size, uint32_t segment, void *dict, uint64_t cap, uint64_t *dict_len);
+
 /* ---- plug-in: libflate_lz77::Lz77Encode (libflate_lz77/src/lib.rs:83-107) -----------------
  * Codes are delivered in batches: word = (val << 16) | dist; dist == 0 → Code::Literal(val),
  * else Code::Pointer{length: val, backward_distance: dist} (lib.rs:27-42). */

@@ -48,6 +48,7 @@ EXPORTS = [
     "lfx_decode_batch_dict_device", "lfx_decoder_set_dict",
     "lfx_encode_dict_bound", "lfx_encode_dict_device", "lfx_encode_dict_host", "lfx_encode_batch_dict_device",
     "lfx_dict_new_chain", "lfx_encoder_new_dict", "lfx_encode_batch_packed_device", "lfx_decode_batch_packed_device",
+    "lfx_dict_train_device", "lfx_dict_train_host",
 ]
 
 
@@ -211,6 +212,8 @@ def lib():
     L.lfx_decode_dict_device.argtypes = [vp, i32, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.lfx_decode_dict_host.argtypes = [vp, i32, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.lfx_decode_batch_dict_device.argtypes = [vp, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    for f in (L.lfx_dict_train_device, L.lfx_dict_train_host):
+        f.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, u64, C.POINTER(u64)]
     L.lfx_decoder_set_dict.argtypes = [vp, vp]
     L.lfx_encode_dict_bound.restype = u64
     L.lfx_encode_dict_bound.argtypes = [u64, C.POINTER(EncodeOpts), C.POINTER(Schedule)]

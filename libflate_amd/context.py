@@ -373,6 +373,28 @@ class Context:
             raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
         return [(st[i], out_len[i]) for i in range(k)]
 
+    # ---- training a preset dictionary (lfx_dict_train_*) --------------------------------
+    def _dict_train(self, fn, src, offs, lens, size, segment, dst, cap):
+        k = len(offs)
+        a = lambda v: (C.c_uint64 * max(k, 1))(*v)
+        got = C.c_uint64(0)
+        rc = fn(self._h, src, k, a(offs), a(lens), size, segment, dst, cap, C.byref(got))
+        if rc:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+        return got.value
+
+    def dict_train_device(self, d_samples, offs, lens, size, segment, d_dict, cap):
+        """lfx_dict_train_device: a dictionary of at most `size` bytes trained from the records d_samples[offs[i], +lens[i]) into
+        d_dict[0, cap), cap >= size; the offsets and lengths are host-side lists, ascending and not overlapping → its length"""
+        return self._dict_train(_ffi.lib().lfx_dict_train_device, d_samples, offs, lens, size, segment, d_dict, cap)
+
+    def dict_train_host(self, data, offs, lens, size, segment=128):
+        """lfx_dict_train_host: the records data[offs[i], +lens[i]) of host bytes → the dictionary"""
+        data = bytes(data)
+        out = C.create_string_buffer(max(size, 1))
+        n = self._dict_train(_ffi.lib().lfx_dict_train_host, data, offs, lens, size, segment, out, size)
+        return out.raw[:n]
+
     # ---- encoding with a preset dictionary (lfx_encode_dict_*, DESIGN.md §18) ---------------------------
     def encode_dict_device(self, fmt, zdict, d_in, n, d_out, cap, opts=None, schedule=None):
         """lfx_encode_dict_device: zlib (FDICT + DICTID) / raw DEFLATE whose first chunk is primed by a Dictionary (None: exactly
@@ -548,6 +570,30 @@ class Dictionary:
         self._ctx._retain()
         self.id = int(_ffi.lib().lfx_dict_id(self._h))
 
+    @classmethod
+    def train(cls, records, size=32768, segment=128, context=None, chain=False):
+        """A dictionary of at most `size` bytes trained on the device from sample records (lfx_dict_train_*):
+        segments of `segment` bytes whose 8-byte substrings are the most frequent across the records, the best one last.
+        records: a list of bytes, or (tensor, offsets, lengths) — a contiguous CUDA uint8 tensor and host-side lists naming the
+        records inside it, ascending and not overlapping; the dictionary then never leaves the device.  `trained` holds its
+        length; chain as in Dictionary()."""
+        ctx = context if context is not None else default_context()
+        if isinstance(records, tuple) and len(records) == 3 and hasattr(records[0], "data_ptr"):
+            import torch
+            t, offs, lens = records
+            if not t.is_cuda or t.dtype.itemsize != 1 or not t.is_contiguous():
+                raise TypeError("Dictionary.train: a tensor must be a contiguous CUDA uint8 tensor")
+            d_dict = torch.empty(size, dtype=torch.uint8, device=t.device)
+            torch.cuda.current_stream(t.device).synchronize()
+            n = ctx.dict_train_device(t.data_ptr(), list(offs), list(lens), size, segment, d_dict.data_ptr(), size)
+            data = d_dict[:n]
+        else:
+            data = train_dictionary(records, size, segment, context=ctx)
+            n = len(data)
+        d = cls(data, ctx, chain)
+        d.trained = n
+        return d
+
     @property
     def handle(self):
         return self._h
@@ -563,6 +609,18 @@ class Dictionary:
             self.close()
         except Exception:
             pass
+
+
+def train_dictionary(records, size=32768, segment=128, context=None):
+    """a list of bytes → the bytes of a dictionary of at most `size` bytes trained from them on the device
+    (lfx_dict_train_host) — what zlib.compressobj(zdict=...), compress(zdict=...) and Dictionary() take"""
+    ctx = context if context is not None else default_context()
+    records = [bytes(r) for r in records]
+    offs, at = [], 0
+    for r in records:
+        offs.append(at)
+        at += len(r)
+    return ctx.dict_train_host(b"".join(records), offs, [len(r) for r in records], size, segment)
 
 
 _default = {}

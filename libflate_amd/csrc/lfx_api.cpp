@@ -18,6 +18,7 @@
 #include "lfx_batch_pack.h"
 #include "lfx_ctx.h"
 #include "lfx_device.h"
+#include "lfx_dict_train.h"
 #include "lfx_enc_frame.h"
 #include "lfx_encode_int.h"
 #include "lfx_huff.h"
@@ -473,6 +474,76 @@ extern "C" int lfx_encode_dict_host(lfx_ctx *cc, int format, const lfx_encode_op
     return encode_staged(c, in, n, bound, out, cap, out_len, [&](uint64_t &len) {
         return lfx_encode_dict_device(cc, format, o, s, dict, c->d_io_in.p, n, c->d_io_out.p, bound & ~3ull, &len);
     });
+} LFX_ABI_CATCH
+
+// ---- training a preset dictionary from sample records: the checks and the record table are
+// lfx_dict_train.h's, the kernels lfx_dict_train.hip's; one host wait, for the dictionary's length
+static int dict_train_impl(Ctx *c, const DtrainPlan &pl, const uint8_t *d_samples, uint8_t *d_dict, uint64_t *dict_len) {
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    const DtrainScratch w = dtrain_scratch(pl.n, pl.nrec(), pl.epochs, pl.k);
+    if (int rc = c->d_dict_train.reserve(w.bytes)) { c->set_error("out of device memory for the trainer's scratch"); return rc; }
+    uint8_t *d = (uint8_t *)c->d_dict_train.p;
+    // the counters, the slots and the length word in one fill each; the record table (pl outlives the copies: the call
+    // synchronises before it returns)
+    if (hipMemsetAsync(d + w.freq, 0, 4ull << DTRAIN_F, c->stream) != hipSuccess ||
+        hipMemsetAsync(d + w.slots, 0, 8ull * pl.epochs + 8, c->stream) != hipSuccess ||
+        hipMemcpyAsync(d + w.pos, pl.pos.data(), 4ull * pl.pos.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(d + w.off, pl.off.data(), 8ull * pl.off.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        c->set_error("the trainer's uploads failed");
+        return LFX_E_DEVICE;
+    }
+    int rc = launch_dict_train(c->stream, pl, w, d, d_samples, d_dict);
+    c->phase("dict_train");
+    uint64_t len = 0;
+    if (!rc && hipMemcpyAsync(&len, d + w.out_len, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
+    if (hipStreamSynchronize(c->stream) != hipSuccess || rc) { c->set_error("the trainer's kernels failed"); return LFX_E_DEVICE; }
+    *dict_len = len;
+    return LFX_OK;
+}
+
+extern "C" int lfx_dict_train_device(lfx_ctx *cc, const void *d_samples, uint32_t count, const uint64_t *off, const uint64_t *len,
+                                     uint32_t dict_size, uint32_t segment, void *d_dict, uint64_t cap, uint64_t *dict_len) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    DtrainPlan pl;
+    const char *why;
+    if (int rc = dtrain_check(count, off, len, dict_size, segment, d_dict, cap, &pl, &why)) { c->set_error(why); return rc; }
+    if (pl.n && !d_samples) { c->set_error("the samples buffer is NULL"); return LFX_E_ARG; }
+    uint64_t got = 0;
+    if (pl.n)
+        if (int rc = dict_train_impl(c, pl, (const uint8_t *)d_samples, (uint8_t *)d_dict, &got)) return rc;
+    if (dict_len) *dict_len = got;
+    return LFX_OK;
+} LFX_ABI_CATCH
+
+extern "C" int lfx_dict_train_host(lfx_ctx *cc, const void *samples, uint32_t count, const uint64_t *off, const uint64_t *len,
+                                   uint32_t dict_size, uint32_t segment, void *dict, uint64_t cap, uint64_t *dict_len) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    DtrainPlan pl;
+    const char *why;
+    if (int rc = dtrain_check(count, off, len, dict_size, segment, dict, cap, &pl, &why)) { c->set_error(why); return rc; }
+    if (pl.n && !samples) { c->set_error("the samples buffer is NULL"); return LFX_E_ARG; }
+    uint64_t got = 0;
+    if (pl.n) {
+        (void)hipSetDevice(c->device);
+        // the bytes from the first record's start to the last one's end go up (gaps between records with them); the table's
+        // offsets move with them
+        int rc;
+        if ((rc = c->d_io_out.reserve(dict_size))) return rc;
+        if ((rc = stage_in(c, (const uint8_t *)samples + pl.extent_lo, pl.extent_hi - pl.extent_lo))) return rc;
+        for (uint64_t &o : pl.off) o -= pl.extent_lo;
+        // (a page-locked `samples` was only queued for DMA: no return before the stream has passed the copy, on any path)
+        if ((rc = dict_train_impl(c, pl, (const uint8_t *)c->d_io_in.p, (uint8_t *)c->d_io_out.p, &got))) { (void)hipStreamSynchronize(c->stream); return rc; }
+        if ((rc = device_to_host(c, dict, c->d_io_out.p, got, c->stream))) { c->set_error("device to host copy failed"); return rc; }
+    }
+    if (dict_len) *dict_len = got;
+    return LFX_OK;
 } LFX_ABI_CATCH
 
 // ---- members encode: one buffer as back-to-back gzip members / BGZF, packed at their final offsets ----------
