@@ -107,9 +107,6 @@ void Diag::read() {
     auto on = [](const char *k) { return getenv(k) != nullptr; };
     debug = on("LFX_DEBUG");
     match_v1 = on("LFX_MATCH_V1");
-    match_v5 = on("LFX_MATCH_V5");
-    if (const char *mp = getenv("LFX_MATCH_PARTS")) match_parts = atoi(mp);
-    if (const char *rc7 = getenv("LFX_R7_CAP")) r7_cap = atoi(rc7);
     no_serial = on("LFX_NO_SERIAL");
     batch_serial = on("LFX_BATCH_SERIAL");
     no_pieces = on("LFX_NO_PIECES");
@@ -118,10 +115,10 @@ void Diag::read() {
     two_pass = on("LFX_TWO_PASS");
     hist_separate = on("LFX_HIST_SEPARATE");
     if (const char *pc = getenv("LFX_PACK_BY_CHUNK")) pack_by_chunk = atoi(pc) ? 1 : 0;
-    find2_exp = getenv("LFX_FIND2_EXP") ? atoi(getenv("LFX_FIND2_EXP")) : 0;
     no_pin_slots = on("LFX_NO_PIN_SLOTS");
     no_small_scan = on("LFX_NO_SMALL_SCAN");
     store_tight = on("LFX_STORE_TIGHT");
+    if (const char *ds = getenv("LFX_DUMP_SEG")) dump_seg = atoi(ds);
 }
 
 void Ctx::phase(const char *name) {
@@ -167,12 +164,7 @@ extern "C" lfx_ctx *lfx_ctx_new(int device, int *status) try {
     if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_zero, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_res, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_part[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_part[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_part[2], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_part[3], hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&c->ev_zero, hipEventDisableTiming) != hipSuccess) {
         (void)hipStreamDestroy(c->own_stream);
         delete c;
         if (status) *status = LFX_E_DEVICE;
@@ -202,8 +194,6 @@ extern "C" void lfx_ctx_free(lfx_ctx *cc) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_zero) (void)hipEventDestroy(c->ev_zero);
-    if (c->ev_res) (void)hipEventDestroy(c->ev_res);
-    for (hipEvent_t e : c->ev_part) if (e) (void)hipEventDestroy(e);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

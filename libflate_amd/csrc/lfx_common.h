@@ -98,7 +98,7 @@ struct SegDesc {
     uint32_t chunk;
     uint32_t start;
     uint32_t len;
-    uint32_t lnk_base;   // lfx_match7 / lfx_match5: first entry of the segment's private link region, in units of 64 entries (128 bytes)
+    uint32_t lnk_base;   // lfx_match7: first entry of the segment's private link region, in units of 64 entries (128 bytes)
 };
 constexpr uint32_t SEG_POSITIONS = 256 * 1024;
 

@@ -31,9 +31,6 @@ struct DevBuf {
 struct Diag {
     bool debug = false;          // LFX_DEBUG: per-stage counters and cycle stamps on stderr
     bool match_v1 = false;       // LFX_MATCH_V1: first-generation match kernel (+ md → cd)
-    bool match_v5 = false;       // LFX_MATCH_V5: lfx_match5.hip (round 4: hash heads, window ring, link ring)
-    int r7_cap = 0;              // LFX_R7_CAP: lfx_match7's resolver ends every walk after so many hops (WRONG answers: timing experiments only)
-    int match_parts = 1;         // LFX_MATCH_PARTS: lfx_match7 in up to four launches, each part's resolver on the side stream
     bool no_serial = false;      // LFX_NO_SERIAL: the serial fallback of the single-stream decoder is an error
     bool batch_serial = false;   // LFX_BATCH_SERIAL: every stream of a batch through the serial kernel
     bool no_pieces = false;      // LFX_NO_PIECES
@@ -41,11 +38,11 @@ struct Diag {
     bool no_small_scan = false;  // LFX_NO_SMALL_SCAN: 1024 slices a block also for small blocks (round 5's geometry)
     bool two_pass = false;       // LFX_TWO_PASS: every block through blk_emit_kernel (no storing scan)
     bool no_pin_slots = false;   // LFX_NO_PIN_SLOTS: the decode's small transfers as plain pageable copies (the path of a full arena)
-    int find2_exp = 0;           // LFX_FIND2_EXP=1..4: a cut-down finder stage 2 runs in front of the real one (phase "find2x"): timing only
     bool hist_separate = false;  // LFX_HIST_SEPARATE: the blocks' symbol counts by histogram_kernel (round 5) instead of inside parse_emit
     int pack_by_chunk = -1;      // LFX_PACK_BY_CHUNK: 0 the tile-parallel pack kernels always, 1 pack_chunk_kernel wherever it is legal (unset: by the geometry)
     bool store_tight = false;    // LFX_STORE_TIGHT: the storing scan's regions sized for 16 bits a code (tests: lanes overflow, blocks fall back)
     int enc_batch_mb = 0;        // LFX_ENC_BATCH_MB: the stream encoder encodes closed blocks once so many MiB wait (0: the default, 8)
+    int dump_seg = -1;           // LFX_DUMP_SEG=<n> (with LFX_DEBUG): the parse state of segment n on stderr (-1: none)
     void read();
 };
 
@@ -71,7 +68,6 @@ struct Ctx {
     // main stream: fork / join through these two events
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_zero = nullptr;
-    hipEvent_t ev_part[4] = {}, ev_res = nullptr;   // lfx_match7: the resolver of one part of the segments runs beside the next part's kernel
     // The pack kernels OR into a zero-filled output: the fill runs on the side stream, beside the match kernel, instead of
     // between the Huffman and the pack kernels (every entry point is synchronous, so nothing else is using the buffer).  While
     // `ptr` is set a fill may still be running on the caller's buffer: no entry point returns before join() or settle().

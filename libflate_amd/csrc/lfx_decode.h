@@ -122,8 +122,8 @@ int launch_inflate_dict(hipStream_t st, const uint8_t *in, uint8_t *out, const I
 constexpr uint32_t FIND_SHARDS = 256;
 constexpr uint32_t FIND_HDR_WORDS = 1024, FIND_HDR_FINAL = 320, FIND_HDR_DBG = 360, FIND_HDR_READ = 512 /* words the host reads back */;
 // stage 2's batch counters: FIND2_GROUPS of them, 128 bytes apart.  ONE counter for all batches was the kernel's floor: eight
-// thousand device-scope atomics on one address at ~20 ns each are 0.19 ms whatever the batches cost (measured with batches
-// that do nothing, LFX_FIND2_EXP=3) — the wavefronts of group k deal the batches k, k + GROUPS, ... among themselves.
+// thousand device-scope atomics on one address at ~20 ns each are 0.19 ms whatever the batches cost (measured in round 6
+// with batches that did nothing) — the wavefronts of group k deal the batches k, k + GROUPS, ... among themselves.
 constexpr uint32_t FIND2_GROUPS = 16, FIND_HDR_WORK = 512, FIND_HDR_WORK_STRIDE = 32;
 inline uint32_t find_shard_cap(uint64_t comp_bytes) {      // survivors are ~0.4 % of the bytes: room for 16 x a list's expected share
     const uint64_t want = comp_bytes / 4000;
@@ -137,8 +137,7 @@ int launch_find_stage2(hipStream_t st, const uint8_t *in, uint64_t nbytes, const
                        uint32_t shard_cap, const uint32_t *count /* device: stage 1's FIND_SHARDS + 1 words */,
                        uint32_t *work /* device, zero: the batch counter of the persistent grid */,
                        uint32_t *final_count, uint64_t *final_list, uint32_t final_cap, uint32_t n_cu,
-                       uint64_t *dbg = nullptr /* device, zero: seven counters (LFX_DEBUG) */,
-                       int exp = 0 /* timing experiments: a cut-down kernel that finds nothing (LFX_FIND2_EXP) */);
+                       uint64_t *dbg = nullptr /* device, zero: seven counters (LFX_DEBUG) */);
 // multi-member decode (lfx_members.hip): gzip member candidates (1f 8b 08, reserved FLG bits clear) per tile of MEMBER_TILE
 // input bytes — counted, then written in input order to the positions the host gives each tile (MEMBER_SKIP: none)
 constexpr uint64_t MEMBER_TILE = 16384;

@@ -79,29 +79,18 @@ struct EncCall {
 };
 
 // ---- LFX_DEBUG dumps (each behind a synchronous copy, where the stage that calls it stands in the stream)
-void dbg_match(Ctx *c, const EncCall &k) {
+void dbg_match(const EncCall &k) {
     uint64_t hv[256];
     (void)hipMemcpy(hv, k.v.mdbg, sizeof hv, hipMemcpyDeviceToHost);
-    const bool match_v1 = k.match_v1, v5 = !match_v1 && c->diag.match_v5, v7 = !match_v1 && !c->diag.match_v5;
-    if (v7) {
+    if (!k.match_v1) {
         // lfx_match7: wave 0 = exchange on head, wave 1 = exchange on second, waves 2..15 = helpers
         for (int w = 0; w < 16; w++)
             fprintf(stderr, "[lfx] match7 wave%d: work=%llu barrier-wait=%llu tiles=%llu\n", w, (unsigned long long)hv[w * 8],
                     (unsigned long long)hv[w * 8 + 1], (unsigned long long)hv[w * 8 + 5]);
     } else {
         for (int w = 0; w < 16; w++)
-            fprintf(stderr, "[lfx] match%s wave%d: %s=%llu %s=%llu wait=%llu tiles=%llu\n", match_v1 ? "1" : "5", w,
-                    match_v1 ? "load" : "phaseA", (unsigned long long)hv[w * 8], match_v1 ? "work" : "phaseB",
+            fprintf(stderr, "[lfx] match1 wave%d: load=%llu work=%llu wait=%llu tiles=%llu\n", w, (unsigned long long)hv[w * 8],
                     (unsigned long long)hv[w * 8 + 1], (unsigned long long)hv[w * 8 + 2], (unsigned long long)hv[w * 8 + 5]);
-    }
-    if (v5) {
-        uint64_t handed = 0;
-        for (int w = 1; w < 16; w++) handed += hv[128 + w * 8 + 5];
-        fprintf(stderr, "[lfx] match5 workgroup 0: %llu walks handed over to wave 0 of %llu positions; wave 0 waited %llu cycles for their loads\n",
-                (unsigned long long)handed, (unsigned long long)hv[5] * 960ull, (unsigned long long)hv[6]);
-        for (int w = 1; w < 16; w++)
-            fprintf(stderr, "[lfx] match5 wave%d loop trips: sum=%u max=%u tiles>4=%u tiles>8=%u\n", w, (unsigned)hv[w * 8 + 3],
-                    (unsigned)(hv[w * 8 + 3] >> 32), (unsigned)hv[w * 8 + 4], (unsigned)(hv[w * 8 + 4] >> 32));
     }
 }
 // the parse's two launchers over a call's views: the persistent walk, and the chaining kernels behind it (counted: with the
@@ -124,7 +113,7 @@ int parse_chain(Ctx *c, const EncCall &k, bool counted, bool fixseg_only = false
 int dbg_dump_seg(Ctx *c, const EncCall &k) {
     const EncView &v = k.v;
     hipStream_t st = c->stream;
-    const uint32_t sg = (uint32_t)atoi(getenv("LFX_DUMP_SEG"));
+    const uint32_t sg = (uint32_t)c->diag.dump_seg;
     for (int stage_no = 1; stage_no <= 3 && sg < k.plan.n_segs; stage_no++) {
         if (int rc = parse_walk(c, k, nullptr, nullptr)) return rc;
         if (stage_no != 1)
@@ -175,7 +164,7 @@ int reserve_scratch(Ctx *c, EncCall &k) {
     if (!hc && (rc = c->d_cd.reserve(2 * n + 64))) return rc;                   // candidate distances, 16 bits per position
     if (!hc && k.chain_depth && (rc = c->d_cd2.reserve(2 * n + 64))) return rc;  // ... and the chain stage's, which the parse then reads
     if (!hc && k.chain_depth && (k.lazy || k.tuned) && (rc = c->d_len.reserve(n + 64))) return rc;   // ... and LazyLz77Encoder's length byte per position (the tuned instances write it at every level)
-    if (!hc && !match_v1 && (rc = c->d_glnk.reserve(264 * std::max<uint64_t>(lnk_units, 1)))) return rc;   // lfx_match7: link records (4 bytes) + ballot words (8 bytes per 64); lfx_match5: links (2 bytes)
+    if (!hc && !match_v1 && (rc = c->d_glnk.reserve(264 * std::max<uint64_t>(lnk_units, 1)))) return rc;   // lfx_match7: link records (4 bytes) + ballot words (8 bytes per 64)
     if (!hc && !match_v1 && (rc = c->d_ucount.reserve(4 * std::max<size_t>(nsegs, 1)))) return rc;   // lfx_match7: unresolved positions per segment
     if (!hc && match_v1 && (rc = c->d_md.reserve(4 * std::max<uint64_t>(n, 1)))) return rc;   // first-generation kernel: (length, distance) words
     if ((rc = c->d_codes.reserve(4 * std::max<uint64_t>(plan.n_codes_cap, 1)))) return rc;
@@ -236,7 +225,7 @@ int upload_tables(Ctx *c, const EncCall &k) {
 // tile → chunk and segment → chunk.  The call's first kernel also clears the blocks' symbol counters, the result record and the
 // match stage's per-segment counts (three fill operations in front of the match kernel before: 22 us of a 4.6 ms step)
 int chunk_maps(Ctx *c, const EncCall &k) {
-    const bool ucount_here = !k.hc && !k.match_v1 && !c->diag.match_v5;
+    const bool ucount_here = !k.hc && !k.match_v1;
     const ZeroSpan z_hist{k.v.hist, (uint32_t)(320 * (k.pack_by_chunk ? (size_t)c->cur_nchunks : std::max<size_t>(c->cur_nblocks, 1)))}, z_res{(uint32_t *)c->d_res.p, 64u},
         z_ucount{ucount_here ? (uint32_t *)c->d_ucount.p : nullptr, ucount_here ? (uint32_t)std::max<size_t>(k.g.segs.size(), 1) : 0u};
     c->cur_tile_map = k.v.tile_map;
@@ -260,40 +249,25 @@ int upload_codes(Ctx *c, const EncCall &k) {
 }
 
 // lfx_match7: the candidate kernel, then the positions it leaves open (0.5 % of a text): ballot words → lists → walks.
-// (Measured, round 5: the segments in four parts, the resolver of a part on the side stream beside the next part's
-//  kernel — `LFX_MATCH_PARTS=4` — 1.10 ms against 1.15 in one piece at 256 MiB: a part of 256 workgroups ends with
-//  its slowest segment, and the compaction waits for slots behind the kernel.  The resolver with four walks in
-//  flight per lane made the overlap pointless.)
+// Both on the main stream, one launch each.  (Measured, round 5: the segments in four parts, the resolver of a part on the
+// side stream beside the next part's kernel, 1.10 ms against 1.15 in one piece at 256 MiB: a part of 256 workgroups ends
+// with its slowest segment, and the compaction waits for slots behind the kernel.  The resolver with four walks in flight
+// per lane made the overlap pointless.)
 int match7(Ctx *c, const EncCall &k) {
     const EncView &v = k.v;
     hipStream_t st = c->stream;
     const uint32_t ns = (uint32_t)k.g.segs.size();
-    const uint32_t parts = match7_parts(ns, (uint32_t)std::max(c->n_cu, 1), c->diag.match_parts);
     uint32_t *d_glnk = (uint32_t *)c->d_glnk.p;
     uint64_t *d_umask = (uint64_t *)((uint8_t *)c->d_glnk.p + 256 * std::max<uint64_t>(k.g.lnk_units, 1));
     uint32_t *d_ucount = (uint32_t *)c->d_ucount.p;     // (cleared by the call's first kernel, launch_chunk_maps)
-    for (uint32_t q = 0; q < parts; q++) {
-        const uint32_t s0 = (uint32_t)((uint64_t)ns * q / parts), s1 = (uint32_t)((uint64_t)ns * (q + 1) / parts);
-        LAUNCH_TRY(launch_match7(st, k.d_in, k.n, v.chunks, v.segs + s0, s1 - s0, k.po.window_size, v.cd, d_glnk, d_umask,
-                                 v.d_match_flags, q == 0 ? v.mdbg : nullptr));
-        if (parts == 1 && c->timing_fine()) c->phase("lz77_cand");
-        hipStream_t rs = parts > 1 ? c->side_stream : st;
-        if (parts > 1) {
-            HIP_TRY(hipEventRecord(c->ev_part[q], st));
-            HIP_TRY(hipStreamWaitEvent(rs, c->ev_part[q], 0));
-        }
-        LAUNCH_TRY(launch_resolve7(rs, v.chunks, v.segs + s0, s1 - s0, k.po.window_size, v.cd, d_glnk, d_umask, v.stage, d_ucount + s0,
-                                   (uint32_t)std::max(c->diag.r7_cap, 0)));
-    }
-    if (parts > 1) {
-        HIP_TRY(hipEventRecord(c->ev_res, c->side_stream));
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_res, 0));
-    }
+    LAUNCH_TRY(launch_match7(st, k.d_in, k.n, v.chunks, v.segs, ns, k.po.window_size, v.cd, d_glnk, d_umask, v.d_match_flags, v.mdbg));
+    if (c->timing_fine()) c->phase("lz77_cand");
+    LAUNCH_TRY(launch_resolve7(st, v.chunks, v.segs, ns, k.po.window_size, v.cd, d_glnk, d_umask, v.stage, d_ucount));
     return LFX_OK;
 }
 
 // candidate distances for every position: lfx_match7 unless the context fell back to (or LFX_MATCH_V1 asks for) the
-// first-generation kernel, or LFX_MATCH_V5 asks for lfx_match5
+// first-generation kernel
 int stage_match(Ctx *c, const EncCall &k) {
     const EncView &v = k.v;
     hipStream_t st = c->stream;
@@ -301,13 +275,10 @@ int stage_match(Ctx *c, const EncCall &k) {
     if (k.match_v1) {
         LAUNCH_TRY(launch_match(st, k.d_in, k.n, v.chunks, v.segs, ns, k.po.window_size, k.po.max_length, (uint32_t *)c->d_md.p, v.mdbg));
         LAUNCH_TRY(launch_md_to_cd(st, (const uint32_t *)c->d_md.p, k.n, v.cd));
-    } else if (!c->diag.match_v5) {
-        if (int rc = match7(c, k)) return rc;
     } else {
-        LAUNCH_TRY(launch_match5(st, k.d_in, k.n, v.chunks, v.segs, ns, k.po.window_size, v.cd, (uint16_t *)c->d_glnk.p, v.d_match_flags,
-                                 v.mdbg));
+        if (int rc = match7(c, k)) return rc;
     }
-    if (v.mdbg) dbg_match(c, k);
+    if (v.mdbg) dbg_match(k);
     c->phase(c->timing_fine() ? "lz77_resolve" : "lz77_match");
     return LFX_OK;
 }
@@ -396,7 +367,7 @@ int stage_parse(Ctx *c, EncCall &k) {
     const EncView &v = k.v;
     hipStream_t st = c->stream;
     const bool want_checksum = k.ck_mode != 0;
-    if (c->diag.debug && getenv("LFX_DUMP_SEG"))
+    if (c->diag.debug && c->diag.dump_seg >= 0)
         if (int rc = dbg_dump_seg(c, k)) return rc;
     if (int rc = parse_walk(c, k, v.d_match_flags, v.mdbg ? v.mdbg + 256 : nullptr)) return rc;
     // The side stream's fork point: behind the walk kernel, in front of the chaining kernels.  Recorded HERE, whatever the walk

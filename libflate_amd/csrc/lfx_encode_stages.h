@@ -60,7 +60,7 @@ inline EncodeGeom encode_geometry(const Plan &plan, bool host_codes, uint32_t n_
         for (uint64_t s = 0; s + 3 < ch.len; s += seg_len)
             g.segs.push_back(SegDesc{ci, (uint32_t)s, (uint32_t)std::min<uint64_t>(seg_len, ch.len - s), 0});
     }
-    // lfx_match5: every segment keeps the final links of its positions — its warm-up included — in a region of its own
+    // lfx_match7: every segment keeps the final links of its positions — its warm-up included — in a region of its own
     for (SegDesc &sg : g.segs) {
         if (g.lnk_units > 0xFFFFFFFFull) { g.err = GEOM_E_LINK_SCRATCH; return g; }
         sg.lnk_base = (uint32_t)g.lnk_units;
@@ -113,12 +113,6 @@ inline EncodeGeom encode_geometry(const Plan &plan, bool host_codes, uint32_t n_
     g.pack_by_chunk = legal && pack_switch != PACK_BY_CHUNK_OFF &&
                       (pack_switch == PACK_BY_CHUNK_ON || (nchunks >= std::max<uint32_t>(n_cu, 1) && max_tiles <= PACK_CHUNK_MAX_TILES));
     return g;
-}
-
-// lfx_match7 in parts (LFX_MATCH_PARTS, at most four): only when every part still has a segment per CU
-inline uint32_t match7_parts(uint32_t n_segs, uint32_t n_cu, int want) {
-    const uint32_t want_parts = (uint32_t)std::max(want, 1);
-    return n_segs >= 2 * n_cu ? std::min<uint32_t>(std::min<uint32_t>(4, want_parts), n_segs / n_cu) : 1;
 }
 
 }  // namespace lfx

@@ -2376,13 +2376,11 @@ __device__ __forceinline__ void clen_table_build(uint8_t *tab, uint32_t lane, ui
 // the stream's last bit fails at the end (the bits a walk reads behind the end are the last dword's, over and over: whatever
 // it makes of them is discarded).  Until then a wavefront that held a candidate within 6000 bits of the stream's end took a
 // second, byte-wise walk with every step bounds-checked: three or four wavefronts per stream, ~100 us each — two thirds of
-// the kernel's time whenever one of them started late (found with batches that do nothing, LFX_FIND2_EXP=4: 102 us).
+// the kernel's time whenever one of them started late (found in round 6 with a cut-down kernel whose batches did nothing: 102 us).
 #ifndef LFX_FIND2_HB
 #define LFX_FIND2_HB 16
 #endif
 constexpr uint32_t FIND2_HB = LFX_FIND2_HB;   // dwords of the stream a lane stages at a time (stage2_check_staged)
-template <int EXP>      // EXP: timing experiments (LFX_FIND2_EXP: a cut-down kernel runs in front of the real one): 1 = no walk (every candidate
-                        // fails), 2 = no table either, 3 = no staging either, 4 = no batch counter either (batches by stride)
 __device__ __forceinline__ bool stage2_check_staged(const uint8_t *__restrict__ in, uint64_t nbytes, uint64_t cand_bit, bool valid,
                                                     uint8_t *cl_tab, uint32_t *hbuf, uint64_t *dbg, uint32_t *work, uint32_t &next_raw) {
     const uint32_t lane = threadIdx.x;
@@ -2401,7 +2399,7 @@ __device__ __forceinline__ bool stage2_check_staged(const uint8_t *__restrict__ 
         for (uint32_t k = 0; k < FIND2_HB; ++k)
             if (need) hbuf[k * 64 + lane] = v[k];
     };
-    stage(valid && EXP < 3);
+    stage(valid);
     const uint32_t e0 = hbuf[lane], e1 = hbuf[64 + lane], e2 = hbuf[128 + lane], e3 = hbuf[192 + lane];
     const uint32_t x0 = __builtin_amdgcn_alignbit(e1, e0, off), x1 = __builtin_amdgcn_alignbit(e2, e1, off),
                    x2 = __builtin_amdgcn_alignbit(e3, e2, off);
@@ -2414,7 +2412,7 @@ __device__ __forceinline__ bool stage2_check_staged(const uint8_t *__restrict__ 
         clw |= (uint64_t)(k < nc ? fw & 7u : 0u) << (3 * f_clen_order_c(k));
     }
     const uint64_t t1 = dbg ? clock64() : 0;
-    if (EXP < 2) clen_table_build(cl_tab, lane, clw);
+    clen_table_build(cl_tab, lane, clw);
     // the wavefront's next batch is reserved HERE — behind the staging loads and the table, in front of the walk, which only
     // touches LDS: the counter's answer (a device-scope atomic, thousands on one address) arrives while the wavefront walks.
     // (In front of the staging loads — rounds 3-5 — the loads' wait was the atomic's wait too: memory operations return in order.)
@@ -2423,7 +2421,7 @@ __device__ __forceinline__ bool stage2_check_staged(const uint8_t *__restrict__ 
     {
         uint32_t zero;
         asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
-        if (lane == 0 && EXP < 4) next_raw = atomicAdd(work + zero, 1u);
+        if (lane == 0) next_raw = atomicAdd(work + zero, 1u);
     }
     const uint64_t t2 = dbg ? clock64() : 0;
     uint32_t steps = 0, restaged = 0;
@@ -2448,7 +2446,6 @@ __device__ __forceinline__ bool stage2_check_staged(const uint8_t *__restrict__ 
     {
         uint32_t acc = 0;
         last = 31u;
-        if (EXP >= 1) good = false;
         bool runA = good;
         uint32_t badv = 0;                 // (the only verdict carried through the loop besides runA: `good` is settled behind it)
         // (the re-staging stands OUTSIDE the step loop: with the branch inside it the compiler merged the two paths with a copy of
@@ -2566,7 +2563,6 @@ __device__ __forceinline__ bool stage2_check_staged(const uint8_t *__restrict__ 
 // workgroups fetch batches of 64 survivors from a device counter until the lists are exhausted — stage 1 and stage 2 run
 // back to back without the host reading the counts in between (it reads them, the overflow marker and the result list
 // in ONE round trip afterwards).
-template <int EXP>
 __global__ __launch_bounds__(64) void find_blocks_stage2(const uint8_t *__restrict__ in, uint64_t nbytes,
                                                          const uint64_t *__restrict__ cand, uint32_t shard_cap,
                                                          const uint32_t *__restrict__ count, uint32_t *__restrict__ work,
@@ -2611,14 +2607,13 @@ __global__ __launch_bounds__(64) void find_blocks_stage2(const uint8_t *__restri
         for (uint32_t step = FIND_SHARDS / 2; step; step >>= 1) shard += s_pre[shard + step] <= gi ? step : 0u;
         const uint64_t i = (uint64_t)shard * shard_cap + (gi - s_pre[shard]);
         const uint64_t cand_bit = valid ? cand[i] : 0;
-        const bool good = stage2_check_staged<EXP>(in, nbytes, cand_bit, valid, cl_tab, hbuf, dbg, my_work, next_raw);
+        const bool good = stage2_check_staged(in, nbytes, cand_bit, valid, cl_tab, hbuf, dbg, my_work, next_raw);
         if (good) {
             const uint32_t slot = atomicAdd(final_count, 1u);   // a few hundred per stream
             if (slot < final_cap) final_list[slot] = cand_bit;
         }
         __syncthreads();      // (the per-lane tables are reused)
-        if (EXP == 4) base += gridDim.x * 64u;                    // (timing: a fixed deal by stride, no counter)
-        else base = (grp + FIND2_GROUPS * (members + (uint32_t)__builtin_amdgcn_readfirstlane((int)next_raw))) * 64u;
+        base = (grp + FIND2_GROUPS * (members + (uint32_t)__builtin_amdgcn_readfirstlane((int)next_raw))) * 64u;
     }
     if (dbg && threadIdx.x == 0) atomicAdd((unsigned long long *)&dbg[6], (unsigned long long)(clock64() - tk0));   // a wavefront's life
 }
@@ -2864,7 +2859,7 @@ int launch_sym_substitute(hipStream_t st, const uint16_t *sym, const SymUnit *un
 }
 int launch_find_stage2(hipStream_t st, const uint8_t *in, uint64_t nbytes, const uint64_t *cand,
                        uint32_t shard_cap, const uint32_t *count, uint32_t *work, uint32_t *final_count, uint64_t *final_list,
-                       uint32_t final_cap, uint32_t n_cu, uint64_t *dbg, int exp) {
+                       uint32_t final_cap, uint32_t n_cu, uint64_t *dbg) {
     // One-wavefront workgroups, 8 KB + 256 bytes per staged dword + the lists' prefix of LDS each: EXACTLY as many as are
     // resident at once, by the runtime's own count.  (Rounds 3-5 divided 160 KB by the arrays' bytes: 13 — but the allocation
     // is rounded up and twelve fit; the thirteenth workgroup of every CU started when the first ones LEFT, at the end, and the
@@ -2875,18 +2870,14 @@ int launch_find_stage2(hipStream_t st, const uint8_t *in, uint64_t nbytes, const
     int &per_cu = per_cu_dev[dev_ & 63];
     if (per_cu == 0) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)find_blocks_stage2<0>, 64, 0) != hipSuccess || nb < 1) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)find_blocks_stage2, 64, 0) != hipSuccess || nb < 1) {
             (void)hipGetLastError();
             nb = 8;
         }
         per_cu = nb;
     }
     const dim3 grid((uint32_t)per_cu * (n_cu ? n_cu : 256u));
-    if (exp == 1) hipLaunchKernelGGL(find_blocks_stage2<1>, grid, dim3(64), 0, st, in, nbytes, cand, shard_cap, count, work, final_count, final_list, final_cap, dbg);
-    else if (exp == 2) hipLaunchKernelGGL(find_blocks_stage2<2>, grid, dim3(64), 0, st, in, nbytes, cand, shard_cap, count, work, final_count, final_list, final_cap, dbg);
-    else if (exp == 3) hipLaunchKernelGGL(find_blocks_stage2<3>, grid, dim3(64), 0, st, in, nbytes, cand, shard_cap, count, work, final_count, final_list, final_cap, dbg);
-    else if (exp == 4) hipLaunchKernelGGL(find_blocks_stage2<4>, grid, dim3(64), 0, st, in, nbytes, cand, shard_cap, count, work, final_count, final_list, final_cap, dbg);
-    else hipLaunchKernelGGL(find_blocks_stage2<0>, grid, dim3(64), 0, st, in, nbytes, cand, shard_cap, count, work, final_count, final_list, final_cap, dbg);
+    hipLaunchKernelGGL(find_blocks_stage2, grid, dim3(64), 0, st, in, nbytes, cand, shard_cap, count, work, final_count, final_list, final_cap, dbg);
     LFX_LAUNCH_CHECK();
     return 0;
 }

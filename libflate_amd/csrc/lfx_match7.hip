@@ -3,8 +3,8 @@
 // Replaces, bit for bit, the table probe of DefaultLz77Encoder::flush (libflate_lz77/src/default.rs:76-87,146-182): per
 // position the distance to the most recent earlier occurrence of its 3-byte prefix inside the window (0 = none) → cd[].
 //
-// What the earlier generations (lfx_match5.hip) paid for: a 14-bit hash table answers "most recent position with this
-// HASH"; exactness came from a 38 KB window ring (3-byte compares), a 75 KB link ring (duplicate-collapsed chains), pointer
+// What the earlier generations (lfx_match5.hip, which has left the build: HISTORY.md §3.1a) paid for: a 14-bit hash table
+// answers "most recent position with this HASH"; exactness came from a 38 KB window ring (3-byte compares), a 75 KB link ring (duplicate-collapsed chains), pointer
 // jumping and chain walks between two workgroup barriers per 960 positions — 385 wave-instructions per 64 positions.
 //
 // This formulation keeps no bytes and no links in LDS.  The 24-bit prefix is mapped by a BIJECTION (multiplication by an odd
@@ -579,11 +579,10 @@ __global__ __launch_bounds__(r7::SLAB_WORDS) void lz77_compact7_kernel(
 // round trip for every walk — the entry's position, or its answer-so-far and its tag, or a hop (the record of the position
 // reached: its tag and its link) — so that a long walk holds nobody up, and the kernel's time is the round trips of its longest
 // lane, not their sum over the entries.  (What it costs is its scattered sectors from HBM: ending every walk after one hop —
-// LFX_R7_CAP=1, wrong answers — saves 0.07 of 0.24 ms.)
+// wrong answers, measured once in round 5 — saved 0.07 of 0.24 ms.)
 __global__ __launch_bounds__(r7::THREADS) void lz77_resolve7_kernel(
     const ChunkDesc *__restrict__ chunks, const SegDesc *__restrict__ segs, uint32_t window, uint16_t *__restrict__ cd,
-    const uint32_t *__restrict__ glnk, const uint32_t *__restrict__ ulist, const uint32_t *__restrict__ ucount,
-    uint32_t hop_cap /* diagnostics: 0 = none */) {
+    const uint32_t *__restrict__ glnk, const uint32_t *__restrict__ ulist, const uint32_t *__restrict__ ucount) {
     using namespace r7;
     const uint32_t seg = blockIdx.x / WGS, part = blockIdx.x % WGS;
     const uint32_t total = ucount[seg];
@@ -598,13 +597,13 @@ __global__ __launch_bounds__(r7::THREADS) void lz77_resolve7_kernel(
     const uint32_t *ulist_s = ulist + ch.in_off + sg.start;
     constexpr uint32_t STRIDE = WGS * THREADS;             // walks j of all lanes: entries j * STRIDE + lane, + NS * STRIDE, ...
     // walk state: 0 fetch the entry, 1 fetch its tag and where its walk starts, 2 hop, 3 no more entries
-    uint32_t state[NS], i[NS], p[NS], tag[NS], r[NS], dist[NS], hops[NS];
+    uint32_t state[NS], i[NS], p[NS], tag[NS], r[NS], dist[NS];
     bool first[NS];
 #pragma unroll
     for (uint32_t j = 0; j < NS; ++j) {
         i[j] = part * THREADS + threadIdx.x + j * STRIDE;
         state[j] = i[j] < total ? 0u : 3u;
-        p[j] = tag[j] = r[j] = dist[j] = hops[j] = 0;
+        p[j] = tag[j] = r[j] = dist[j] = 0;
         first[j] = false;
     }
     for (;;) {
@@ -636,7 +635,6 @@ __global__ __launch_bounds__(r7::THREADS) void lz77_resolve7_kernel(
                 dist[j] = c[j] - m7::UNRES + 1;              // d2: the position of `second`, known to carry another prefix
                 r[j] = p[j] - dist[j];
                 first[j] = true;
-                hops[j] = 0;
                 state[j] = 2;
             } else if (state[j] == 2) {
                 bool done = false;
@@ -648,7 +646,6 @@ __global__ __launch_bounds__(r7::THREADS) void lz77_resolve7_kernel(
                     dist[j] += l;
                     if (l == 0 || dist[j] > window) done = true;       // default.rs:81 (inclusive window)
                     else r[j] -= l;
-                    if (hop_cap && ++hops[j] >= hop_cap) done = true;   // (LFX_R7_CAP: wrong answers, timing only)
                 }
                 first[j] = false;
                 if (done) {
@@ -678,14 +675,14 @@ int launch_match7(hipStream_t st, const uint8_t *in, uint64_t in_bytes, const Ch
 // ... and what it left open: ballot words → lists → walks.  ucount (one counter per segment, at the first of these segments)
 // must be zero.
 int launch_resolve7(hipStream_t st, const ChunkDesc *chunks, const SegDesc *segs, uint32_t nsegs, uint32_t window, uint16_t *cd,
-                    const uint32_t *glnk, const uint64_t *umask, uint32_t *ulist, uint32_t *ucount, uint32_t hop_cap) {
+                    const uint32_t *glnk, const uint64_t *umask, uint32_t *ulist, uint32_t *ucount) {
     if (nsegs == 0) return 0;
     hipLaunchKernelGGL(lz77_compact7_kernel, dim3(nsegs * (r7::SLABS + 1)), dim3(r7::SLAB_WORDS), 0, st, chunks, segs, umask, ulist,
                        ucount);
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) return (int)e_;
     hipLaunchKernelGGL(lz77_resolve7_kernel, dim3(nsegs * r7::WGS), dim3(r7::THREADS), 0, st, chunks, segs, window, cd, glnk, ulist,
-                       ucount, hop_cap);
+                       ucount);
     e_ = hipGetLastError();
     return e_ != hipSuccess ? (int)e_ : 0;
 }

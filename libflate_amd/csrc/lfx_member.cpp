@@ -59,14 +59,6 @@ int find_collect(Ctx *c, const uint8_t *d_in, uint64_t n, const FindBufs &fb, Fo
     const uint32_t n_cu = (uint32_t)std::max(c->n_cu, 1);
     // stage 2 takes the survivor counts from the device (persistent grid): no host round trip between the stages; the
     // counts, the overflow marker, the number of results and the first results come back in ONE round trip
-    const int find2_exp = c->diag.find2_exp >= 1 && c->diag.find2_exp <= 4 ? c->diag.find2_exp : 0;
-    if (find2_exp) {       // timing experiment: a cut-down stage 2 first (phase "find2x"), then the real one
-        LAUNCH_TRY(launch_find_stage2(st, d_in, n, fb.d_cand, fb.shard_cap, d_count, d_count + FIND_HDR_WORK, d_final_count, fb.d_final,
-                                      fb.final_cap, n_cu, nullptr, find2_exp));
-        HIP_TRY(hipMemsetAsync(d_count + FIND_HDR_FINAL, 0, 4, st));
-        HIP_TRY(hipMemsetAsync(d_count + FIND_HDR_WORK, 0, 4 * (FIND_HDR_WORDS - FIND_HDR_WORK), st));
-        c->phase("find2x");
-    }
     LAUNCH_TRY(launch_find_stage2(st, d_in, n, fb.d_cand, fb.shard_cap, d_count, d_count + FIND_HDR_WORK, d_final_count, fb.d_final,
                                   fb.final_cap, n_cu, c->diag.debug ? (uint64_t *)(d_count + FIND_HDR_DBG) : nullptr));
     constexpr uint32_t HEAD_N = 1024;      // (results that come back with the counts; a stream has a few hundred)

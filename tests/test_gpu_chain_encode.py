@@ -366,5 +366,3 @@ def test_first_generation_match_kernel(lfx, ffi, torch, oracle):
     c = context_with(lfx, LFX_MATCH_V1="1")
     check(c, ffi, torch, oracle, TEXT, 8, fmts=(0,))
     check(c, ffi, torch, oracle, _edge_data(TILE, TILE + 700), 8, fmts=(0,))
-    c5 = context_with(lfx, LFX_MATCH_V5="1")
-    check(c5, ffi, torch, oracle, TEXT, 8, fmts=(0,))

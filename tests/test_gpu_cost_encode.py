@@ -262,8 +262,7 @@ def test_stale_state_in_both_orders(lfx, ctx, ffi, torch, oracle):
 
 def test_older_match_generations(lfx, ffi, torch, oracle):
     data = MIXED[:6000]
-    for env in ({"LFX_MATCH_V1": "1"}, {"LFX_MATCH_V5": "1"}):
-        check(context_with(lfx, **env), ffi, torch, oracle, data, 6, fmts=(1,))
+    check(context_with(lfx, LFX_MATCH_V1="1"), ffi, torch, oracle, data, 6, fmts=(1,))
 
 
 # ---------------------------------------------------------------------------------------------- refusals

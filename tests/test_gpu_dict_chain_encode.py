@@ -289,10 +289,8 @@ def test_host_call_and_module_helpers(lfx, ctx, ffi, oracle, dicts):
         assert mod.compress(data, zdict=D32, context=ctx) == dm.expected_stream(oracle, name, D32, data)
 
 
-@pytest.mark.parametrize("env", ["LFX_MATCH_V1", "LFX_MATCH_V5"])
+@pytest.mark.parametrize("env", ["LFX_MATCH_V1"])
 def test_match_generations(lfx, ffi, torch, oracle, dicts, env):
     c = context_with(lfx, **{env: "1"})
     check(c, ffi, torch, oracle, dicts, D32, D32[-700:] + TEXT[42000:44000] + D32[30000:31500] + b"a" * 300)
     check(c, ffi, torch, oracle, dicts, b"a" * 100, b"a" * 600, depths=(3,))
-    if env == "LFX_MATCH_V5":
-        assert c.match_fallbacks() == 0

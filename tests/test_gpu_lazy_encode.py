@@ -323,11 +323,8 @@ def test_refusals(lfx, ctx, ffi, torch):
 
 # ---------------------------------------------------------------------------------------------- match generations
 def test_other_match_generations(lfx, ffi, torch, oracle):
-    """the chain stage and the demotion run behind the match stage whichever generation ran (LFX_MATCH_V1 / LFX_MATCH_V5 are
-    read when a context is made)"""
+    """the chain stage and the demotion run behind the match stage whichever generation ran (LFX_MATCH_V1 is read when a
+    context is made)"""
     c = context_with(lfx, LFX_MATCH_V1="1")
     check(c, ffi, torch, oracle, MIXED, 8, fmts=(0,))
     check(c, ffi, torch, oracle, place(40 * KIB, TILE - 1), 8, fmts=(0,))
-    c5 = context_with(lfx, LFX_MATCH_V5="1")
-    check(c5, ffi, torch, oracle, MIXED, 8, fmts=(0,))
-    check(c5, ffi, torch, oracle, place(40 * KIB, TILE - 1), 8, fmts=(0,))

@@ -8,7 +8,6 @@ timeout 300 python tools/exp/m5_stress.py ${STRESS:-120} 2>&1 | tail -5
 timeout 300 python tools/exp/enc_timing.py 67108864 8192 1 2>&1 | grep -E "equal|rror"
 timeout 300 python tools/exp/enc_timing.py 67108864 0 1 2>&1 | grep -E "equal|rror"
 timeout 300 python tools/exp/enc_timing.py 268435456 8192 4 2>&1 | grep -E "rep 3|rror" | cut -c1-400
-LFX_MATCH_V5=1 timeout 300 python tools/exp/enc_timing.py 268435456 8192 3 2>&1 | grep -E "rep 2|rror" | cut -c1-200
 LFX_DEBUG=1 timeout 300 python tools/exp/enc_timing.py 268435456 8192 1 2>&1 | grep -E "match7 wave" | head -16
 # per-kernel durations of the same loop
 cd /tmp && export TMPDIR=/tmp
