@@ -989,6 +989,40 @@ int lfx_dict_train_device(lfx_ctx *c, const void *d_samples, uint32_t count, con
 int lfx_dict_train_host(lfx_ctx *c, const void *samples, uint32_t count, const uint64_t *off, const uint64_t *len,
                         uint32_t dict_size, uint32_t segment, void *dict, uint64_t cap, uint64_t *dict_len);
 
+/* ---- the byte-shuffle filter for numeric records ----
+ * HDF5's H5Z_FILTER_SHUFFLE, which is numcodecs' Shuffle: the pre-filter in front of DEFLATE that HDF5 (shuffle=True,
+ * compression="gzip"), Zarr (Shuffle + Zlib / GZip), Blosc and TIFF ship.  Defined here and in tests/shuffle_model.py (numpy),
+ * which the device result equals byte for byte.
+ *
+ *  Definition.  For a record of n bytes and an element size s >= 1 let k = n / s (integer division) and r = n % s.
+ *    LFX_SHUFFLE:    out[j * k + i] = in[i * s + j] for 0 <= i < k, 0 <= j < s; the r trailing bytes are copied,
+ *                    out[k * s + t] = in[k * s + t].
+ *    LFX_UNSHUFFLE:  the inverse permutation.
+ *  s == 1, k <= 1 and n == 0 follow from the formula: the identity, or nothing to do.  Records are independent: nothing is read
+ *  or written outside a record, and no byte outside [out_off[i], out_off[i] + len[i]) changes — records may lie back to back at
+ *  any byte offset.
+ *  Arguments.  elem_size: 1..256, dir: LFX_SHUFFLE or LFX_UNSHUFFLE, else LFX_E_ARG.  count == 0 and n == 0: LFX_OK, nothing
+ *  written.  A NULL context: LFX_E_DEVICE, nothing written.
+ *  Records (the batch call).  Record i is d_in[off, +len) and is written to d_out[out_off[i], +len).  EITHER in_off and len (host
+ *  arrays) with d_table NULL, OR d_table (device memory, 8-byte aligned: count pairs {off, len} of uint64_t — what
+ *  lfx_encode_batch_packed_device and lfx_decode_batch_packed_device write to their d_table) with in_off and len NULL; the call
+ *  copies the table itself.  Both, neither, or one host array alone: LFX_E_ARG.  out_off (host) NULL: the output takes the input
+ *  offsets, in d_out.  With d_table out_off must be NULL (LFX_E_ARG).
+ *  Overlap.  There is no in-place form: a record's input bytes [d_in + off, +len) that meet any record's output bytes, or two
+ *  output ranges that meet, are LFX_E_ARG, and nothing is written.  An offset plus its length beyond 64 bits: LFX_E_ARG.
+ *  The device calls run one launch on the context's stream and return when the bytes are there; lfx_shuffle_host stages its
+ *  buffers as lfx_encode_host does.  The scratch (24 bytes per record, 16 bytes per tile of about 16 KiB) is the context's and
+ *  grows only.
+ *  Not covered: bitshuffle, delta and predictor filters, the stream encoders and decoders, members / BGZF, the seek index, the
+ *  N-GPU calls. */
+enum { LFX_SHUFFLE = 0, LFX_UNSHUFFLE = 1 };
+int lfx_shuffle_device(lfx_ctx *c, int dir, uint32_t elem_size, const void *d_in, uint64_t n, void *d_out);
+int lfx_shuffle_batch_device(lfx_ctx *c, int dir, uint32_t elem_size, uint32_t count,
+                             const void *d_in, const uint64_t *in_off, const uint64_t *len,   /* host, or both NULL ...        */
+                             const void *d_table,                                             /* ... then device: count x {off, len} */
+                             void *d_out, const uint64_t *out_off /* host; NULL: the input offsets */);
+int lfx_shuffle_host(lfx_ctx *c, int dir, uint32_t elem_size, const void *in, uint64_t n, void *out);
+
 /* ---- plug-in: libflate_lz77::Lz77Encode (libflate_lz77/src/lib.rs:83-107) -----------------
  * Codes are delivered in batches: word = (val << 16) | dist; dist == 0 → Code::Literal(val),
  * else Code::Pointer{length: val, backward_distance: dist} (lib.rs:27-42). */

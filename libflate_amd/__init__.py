@@ -6,7 +6,7 @@ CPU fallback.
 """
 from . import _ffi  # noqa: F401
 from .context import Context, Dictionary, default_context, train_dictionary  # noqa: F401
-from . import bgzf, deflate, gzip, lz77, non_blocking, zlib  # noqa: F401
+from . import bgzf, deflate, filters, gzip, lz77, non_blocking, zlib  # noqa: F401
 from .index import Index  # noqa: F401
 from ._stream import StreamError  # noqa: F401
 
@@ -30,4 +30,4 @@ def decoded_size(data, format="gzip", multi=False, context=None):
         raise StreamError(rc, msg)
     return out_len
 
-__all__ = ["Context", "Dictionary", "default_context", "train_dictionary", "Index", "decoded_size", "StreamError", "bgzf", "deflate", "zlib", "gzip", "lz77", "non_blocking"]
+__all__ = ["Context", "Dictionary", "default_context", "train_dictionary", "Index", "decoded_size", "StreamError", "bgzf", "deflate", "zlib", "gzip", "lz77", "non_blocking", "filters"]

@@ -22,6 +22,7 @@ DEC_MULTI = 1
 DEC_NONBLOCKING = 2
 DEC_LAZY_HEADER = 4     # a blocking decoder that leaves the container header to the first header() / read() (set_dict first)
 MEMBERS_BGZF = 1
+SHUFFLE, UNSHUFFLE = 0, 1     # lfx_shuffle_*: the direction
 BGZF_MEMBER_SIZE = 65280      # bgzip's own slice; 65505 is the most a BGZF member holds
 VOFF_NONE = 2**64 - 1         # lfx_bgzf_read.end_voff: no such bound
 
@@ -48,7 +49,7 @@ EXPORTS = [
     "lfx_decode_batch_dict_device", "lfx_decoder_set_dict",
     "lfx_encode_dict_bound", "lfx_encode_dict_device", "lfx_encode_dict_host", "lfx_encode_batch_dict_device",
     "lfx_dict_new_chain", "lfx_encoder_new_dict", "lfx_encode_batch_packed_device", "lfx_decode_batch_packed_device",
-    "lfx_dict_train_device", "lfx_dict_train_host",
+    "lfx_dict_train_device", "lfx_dict_train_host", "lfx_shuffle_device", "lfx_shuffle_batch_device", "lfx_shuffle_host",
 ]
 
 
@@ -214,6 +215,9 @@ def lib():
     L.lfx_decode_batch_dict_device.argtypes = [vp, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     for f in (L.lfx_dict_train_device, L.lfx_dict_train_host):
         f.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp, u64, C.POINTER(u64)]
+    for f in (L.lfx_shuffle_device, L.lfx_shuffle_host):
+        f.argtypes = [vp, i32, u32, vp, u64, vp]
+    L.lfx_shuffle_batch_device.argtypes = [vp, i32, u32, u32, vp, vp, vp, vp, vp, vp]
     L.lfx_decoder_set_dict.argtypes = [vp, vp]
     L.lfx_encode_dict_bound.restype = u64
     L.lfx_encode_dict_bound.argtypes = [u64, C.POINTER(EncodeOpts), C.POINTER(Schedule)]

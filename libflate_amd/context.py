@@ -395,6 +395,38 @@ class Context:
         n = self._dict_train(_ffi.lib().lfx_dict_train_host, data, offs, lens, size, segment, out, size)
         return out.raw[:n]
 
+    # ---- the byte-shuffle filter for numeric records (lfx_shuffle_*) --------------------
+    def _shuffle_rc(self, rc):
+        if rc:
+            raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
+
+    def shuffle_device(self, d_in, n, d_out, elem_size, inverse=False):
+        """lfx_shuffle_device: d_in[0, n) byte-shuffled with elements of elem_size bytes (HDF5's shuffle filter) into d_out[0, n);
+        inverse=True: unshuffled.  The two ranges must not meet."""
+        self._shuffle_rc(_ffi.lib().lfx_shuffle_device(self._h, _ffi.UNSHUFFLE if inverse else _ffi.SHUFFLE, elem_size, d_in, n, d_out))
+
+    def shuffle_batch_device(self, d_in, in_offs, lens, d_out, elem_size, *, inverse=False, out_offs=None, d_table=None):
+        """lfx_shuffle_batch_device: the records d_in[in_offs[i], +lens[i]) shuffled (inverse=True: unshuffled), each on its own,
+        into d_out[out_offs[i], +lens[i]) in one launch; out_offs=None: at the input offsets.  d_table: device memory holding the
+        {off, len} pairs instead — what encode_batch_packed_device / decode_batch_packed_device wrote to their d_table; in_offs
+        then only says how many records there are (a count, or a list whose length is the count), lens and out_offs are None."""
+        if d_table is not None:
+            k = int(in_offs) if isinstance(in_offs, int) else len(in_offs)
+            io = il = None
+        else:
+            k = len(in_offs)
+            io, il = (C.c_uint64 * max(k, 1))(*in_offs), (C.c_uint64 * max(k, 1))(*lens)
+        oo = (C.c_uint64 * max(k, 1))(*out_offs) if out_offs is not None else None
+        self._shuffle_rc(_ffi.lib().lfx_shuffle_batch_device(self._h, _ffi.UNSHUFFLE if inverse else _ffi.SHUFFLE, elem_size, k, d_in, io, il,
+                                                             d_table, d_out, oo))
+
+    def shuffle_host(self, data, elem_size, inverse=False):
+        """lfx_shuffle_host on host bytes → the shuffled (inverse=True: unshuffled) bytes"""
+        data = bytes(data)
+        out = C.create_string_buffer(max(len(data), 1))
+        self._shuffle_rc(_ffi.lib().lfx_shuffle_host(self._h, _ffi.UNSHUFFLE if inverse else _ffi.SHUFFLE, elem_size, data, len(data), out))
+        return out.raw[:len(data)]
+
     # ---- encoding with a preset dictionary (lfx_encode_dict_*, DESIGN.md §18) ---------------------------
     def encode_dict_device(self, fmt, zdict, d_in, n, d_out, cap, opts=None, schedule=None):
         """lfx_encode_dict_device: zlib (FDICT + DICTID) / raw DEFLATE whose first chunk is primed by a Dictionary (None: exactly
@@ -458,9 +490,10 @@ class Context:
             raise (_ffi.DeviceError if rc == _ffi.E_DEVICE else _ffi.LfxError)(rc, self.last_error())
         return rc, total.value, [(oo[i], ol[i]) for i in range(k)]
 
-    def encode_batch_packed_host(self, fmt, records, zdict=None, opts=None, schedule=None):
+    def encode_batch_packed_host(self, fmt, records, zdict=None, opts=None, schedule=None, shuffle=None):
         """a list of bytes → the list of their streams: one upload, one lfx_encode_batch_packed_device call with cap = the sum
-        of the bounds, one download of `total` bytes"""
+        of the bounds, one download of `total` bytes.  shuffle: an element size — every record is byte-shuffled on the device in
+        front of the encode (lfx_shuffle_batch_device); None: no such call is made"""
         import torch
         records = [bytes(r) for r in records]
         if not records:
@@ -480,6 +513,10 @@ class Context:
         d_in = torch.frombuffer(bytearray(b"".join(records) or b"\0"), dtype=torch.uint8).to(dev)
         d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
         torch.cuda.current_stream(dev).synchronize()
+        if shuffle is not None:
+            d_plain, d_in = d_in, torch.empty_like(d_in)
+            torch.cuda.current_stream(dev).synchronize()
+            self.shuffle_batch_device(d_plain.data_ptr(), offs, [len(r) for r in records], d_in.data_ptr(), shuffle)
         rc, total, layout = self.encode_batch_packed_device(fmt, d_in.data_ptr(), offs, [len(r) for r in records], d_out.data_ptr(), cap,
                                                             zdict=zdict, opts=opts, schedule=schedule)
         if rc:
@@ -518,6 +555,15 @@ class Context:
         """a list of streams (bytes) → (the list of their decoded bytes, statuses): one upload, the size query (d_out = None,
         cap = 0) for `total`, one allocation of exactly that, the decode, one download.  A failed stream's entry holds what it
         produced before the fault, and last_error() is the first failed stream's message."""
+        return self._decode_batch_packed_host(fmt, records, zdict, None)
+
+    def decode_batch_unshuffle_host(self, fmt, records, elem_size, zdict=None):
+        """decode_batch_packed_host with every record unshuffled on the device behind the decode (elements of elem_size bytes),
+        fed from the decode's device table without the layout passing through the caller (lfx_shuffle_batch_device, DESIGN.md
+        §30) → (the list of their bytes, statuses)"""
+        return self._decode_batch_packed_host(fmt, records, zdict, elem_size)
+
+    def _decode_batch_packed_host(self, fmt, records, zdict, shuffle):
         import torch
         records = [bytes(r) for r in records]
         if not records:
@@ -534,11 +580,18 @@ class Context:
         if total == 0:
             return [b""] * len(records), st
         d_out = torch.empty(total, dtype=torch.uint8, device=dev)
+        d_table = torch.empty(2 * len(records), dtype=torch.int64, device=dev) if shuffle is not None else None
         torch.cuda.current_stream(dev).synchronize()
         rc, out_offs, out_lens, _used, st, total = self.decode_batch_packed_device(fmt, d_in.data_ptr(), offs, lens, d_out.data_ptr(),
-                                                                                 total, zdict=zdict)
+                                                                                 total, zdict=zdict,
+                                                                                 d_table=d_table.data_ptr() if shuffle is not None else None)
         if rc:
             raise _ffi.LfxError(rc, self.last_error())
+        if shuffle is not None:                 # (a successful call leaves last_error() as the decode left it)
+            d_plain = torch.empty_like(d_out)
+            torch.cuda.current_stream(dev).synchronize()
+            self.shuffle_batch_device(d_out.data_ptr(), len(records), None, d_plain.data_ptr(), shuffle, inverse=True, d_table=d_table.data_ptr())
+            d_out = d_plain
         out = d_out.cpu().numpy().tobytes()
         return [out[o:o + n] for o, n in zip(out_offs, out_lens)], st
 

@@ -24,6 +24,7 @@
 #include "lfx_huff.h"
 #include "lfx_index.h"
 #include "lfx_plan.h"
+#include "lfx_shuffle.h"
 #include "lfx_abi_guard.h"
 
 using namespace lfx;
@@ -533,6 +534,99 @@ extern "C" int lfx_dict_train_host(lfx_ctx *cc, const void *samples, uint32_t co
         if ((rc = device_to_host(c, dict, c->d_io_out.p, got, c->stream))) { c->set_error("device to host copy failed"); return rc; }
     }
     if (dict_len) *dict_len = got;
+    return LFX_OK;
+} LFX_ABI_CATCH
+
+// ---- the byte-shuffle filter: the tile list and the range check are lfx_shuffle.h's, the kernels
+// lfx_shuffle.hip's; the record table and the tile list go up, one launch, one host wait
+static int shuffle_impl(Ctx *c, int dir, uint32_t s, const std::vector<ShufRec> &recs, const void *d_in, void *d_out) {
+    bool any = false;
+    for (const ShufRec &r : recs) {
+        if (r.in_off + r.len < r.len || r.out_off + r.len < r.len) { c->set_error("a record's offset plus its length exceeds 64 bits"); return LFX_E_ARG; }
+        any = any || r.len;
+    }
+    if (!any) return LFX_OK;
+    if (!d_in || !d_out) { c->set_error("a buffer is NULL"); return LFX_E_ARG; }
+    if (!shuf_ranges_ok((uint32_t)recs.size(), recs.data(), (uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out)) {
+        c->set_error("a record's input meets an output range, or two output ranges meet: there is no in-place form");
+        return LFX_E_ARG;
+    }
+    std::vector<ShufItem> items;
+    if (!shuf_build_items((uint32_t)recs.size(), recs.data(), s, items)) { c->set_error("too many tiles for one call"); return LFX_E_ARG; }
+    (void)hipSetDevice(c->device);
+    c->n_ev = 0;
+    c->phase("start");
+    const size_t rec_bytes = sizeof(ShufRec) * recs.size(), item_bytes = sizeof(ShufItem) * items.size();
+    if (int rc = c->d_shuffle.reserve(rec_bytes + item_bytes)) { c->set_error("out of device memory for the tile list"); return rc; }
+    uint8_t *d = (uint8_t *)c->d_shuffle.p;
+    // (recs and items outlive the copies: the call synchronises before it returns)
+    if (hipMemcpyAsync(d, recs.data(), rec_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(d + rec_bytes, items.data(), item_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        c->set_error("the tile list's upload failed");
+        return LFX_E_DEVICE;
+    }
+    const int rc = launch_shuffle(c->stream, dir, s, (const uint8_t *)d_in, (uint8_t *)d_out, (const ShufRec *)d, (const ShufItem *)(d + rec_bytes),
+                                  (uint32_t)items.size());
+    c->phase("shuffle");
+    if (hipStreamSynchronize(c->stream) != hipSuccess || rc) { c->set_error("the shuffle kernel failed"); return LFX_E_DEVICE; }
+    return LFX_OK;
+}
+
+static int shuffle_args(Ctx *c, int dir, uint32_t elem_size) {
+    if (dir != LFX_SHUFFLE && dir != LFX_UNSHUFFLE) { c->set_error("dir: LFX_SHUFFLE or LFX_UNSHUFFLE"); return LFX_E_ARG; }
+    if (elem_size < 1 || elem_size > SHUF_MAX_ELEM) { c->set_error("elem_size: 1..256"); return LFX_E_ARG; }
+    return LFX_OK;
+}
+
+extern "C" int lfx_shuffle_device(lfx_ctx *cc, int dir, uint32_t elem_size, const void *d_in, uint64_t n, void *d_out) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (int rc = shuffle_args(c, dir, elem_size)) return rc;
+    return shuffle_impl(c, dir, elem_size, {ShufRec{0, 0, n}}, d_in, d_out);
+} LFX_ABI_CATCH
+
+extern "C" int lfx_shuffle_batch_device(lfx_ctx *cc, int dir, uint32_t elem_size, uint32_t count, const void *d_in, const uint64_t *in_off,
+                                        const uint64_t *len, const void *d_table, void *d_out, const uint64_t *out_off) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (int rc = shuffle_args(c, dir, elem_size)) return rc;
+    if ((in_off == nullptr) != (len == nullptr) || (in_off && d_table) || (count && !in_off && !d_table)) {
+        c->set_error("the records' places: either in_off and len (host) or d_table (device), not both");
+        return LFX_E_ARG;
+    }
+    if (d_table && out_off) { c->set_error("out_off: NULL with d_table (the output takes the input offsets)"); return LFX_E_ARG; }
+    if (((uintptr_t)d_table & 7) != 0) { c->set_error("d_table must be 8-byte aligned"); return LFX_E_ARG; }
+    if (!count) return LFX_OK;
+    std::vector<ShufRec> recs(count);
+    if (d_table) {
+        (void)hipSetDevice(c->device);
+        std::vector<uint64_t> tab(2 * (size_t)count);
+        if (hipMemcpyAsync(tab.data(), d_table, 16ull * count, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) { c->set_error("the table's download failed"); return LFX_E_DEVICE; }
+        for (uint32_t i = 0; i < count; i++) recs[i] = ShufRec{tab[2 * (size_t)i], tab[2 * (size_t)i], tab[2 * (size_t)i + 1]};
+    } else {
+        for (uint32_t i = 0; i < count; i++) recs[i] = ShufRec{in_off[i], out_off ? out_off[i] : in_off[i], len[i]};
+    }
+    return shuffle_impl(c, dir, elem_size, recs, d_in, d_out);
+} LFX_ABI_CATCH
+
+extern "C" int lfx_shuffle_host(lfx_ctx *cc, int dir, uint32_t elem_size, const void *in, uint64_t n, void *out) try {
+    if (!cc) return LFX_E_DEVICE;
+    Ctx *c = reinterpret_cast<Ctx *>(cc);
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    if (int rc = shuffle_args(c, dir, elem_size)) return rc;
+    if (!n) return LFX_OK;
+    if (!in || !out) { c->set_error("a buffer is NULL"); return LFX_E_ARG; }
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = c->d_io_out.reserve(n))) return rc;
+    if ((rc = stage_in(c, in, n))) return rc;
+    // (a page-locked `in` was only queued for DMA: no return before the stream has passed the copy, on any path)
+    if ((rc = shuffle_impl(c, dir, elem_size, {ShufRec{0, 0, n}}, c->d_io_in.p, c->d_io_out.p))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if ((rc = device_to_host(c, out, c->d_io_out.p, n, c->stream))) { c->set_error("device to host copy failed"); return rc; }
     return LFX_OK;
 } LFX_ABI_CATCH
 

@@ -107,6 +107,9 @@ struct Ctx {
     // lfx_dict_train_device: the counters, the picks, the record table and index, the step's prefix words
     // (lfx_dict_train.h: dtrain_scratch).  Sized only by calls of that kind.
     DevBuf d_dict_train;
+    // lfx_shuffle_* (DESIGN.md §30): the record table and the tile list of one call (lfx_shuffle.h).  Sized only by calls of
+    // that kind.
+    DevBuf d_shuffle;
     // an encode with LFX_HUFFMAN_AUTO: the type every block left block_choose_kernel with, one byte per block.
     // Sized only by calls of that kind; n_choices: its entries of the last prepare (0: that call was not one) — read by the
     // test hook lfx_debug_block_choices alone, no encode path looks at either.
@@ -146,7 +149,7 @@ struct Ctx {
                 &d_dec_streams, &d_dec_state, &d_dec_tmp, &d_dec_cand, &d_dec_blocks, &d_dec_tabs, &d_dec_sym, &d_dec_win, &d_dec_maps,
                 &d_dec_temp, &d_dec_lanesx, &d_idx_tasks, &d_idx_probe, &d_idx_stage, &d_idx_enc,
                 &d_bgzf_meta, &d_bgzf_tasks, &d_bgzf_scratch, &d_bgzf_pack, &d_dict_items, &d_cd2, &d_chain_items, &d_len, &d_choice, &d_hist_chunk, &d_chunk_bits,
-                &d_merge_regions, &d_merge, &d_cost_items, &d_dict_train};
+                &d_merge_regions, &d_merge, &d_cost_items, &d_dict_train, &d_shuffle};
     }
     void *h_res = nullptr;  // pinned, 4 KiB (+ the arena below)
     // Small transfers of the decode paths (job lists up, scan results and counters down) go through page-locked memory: a

@@ -91,7 +91,9 @@ def _with_lz77(options, lz77, cls, level=None):
     return (options if options is not None else cls()).with_lz77(lz77)
 
 
-def _compress(fmt, data, zdict, options, context, lz77=None, level=None, merge_blocks=False):
+def _compress(fmt, data, zdict, options, context, lz77=None, level=None, merge_blocks=False, shuffle=None):
+    if shuffle is not None:     # (the batch of one record: the same stream, with the shuffle in front of it on the device)
+        return _compress_batch(fmt, [data], zdict, options, context, lz77, level, merge_blocks, shuffle)[0]
     from .context import Dictionary, default_context
     ctx = context if context is not None else default_context()
     options = _with_lz77(options, lz77, EncodeOptions, level)
@@ -112,7 +114,7 @@ def _compress(fmt, data, zdict, options, context, lz77=None, level=None, merge_b
             d.close()
 
 
-def _compress_batch(fmt, records, zdict, options, context, lz77=None, level=None, merge_blocks=False):
+def _compress_batch(fmt, records, zdict, options, context, lz77=None, level=None, merge_blocks=False, shuffle=None):
     from .context import Dictionary, default_context
     ctx = context if context is not None else default_context()
     options = _with_lz77(options, lz77, EncodeOptions, level)
@@ -123,15 +125,20 @@ def _compress_batch(fmt, records, zdict, options, context, lz77=None, level=None
     chained = opts is not None and (opts.lz77_kind & 0xFF) in (_ffi.LZ77_CHAIN, _ffi.LZ77_LAZY, _ffi.LZ77_LEVEL, _ffi.LZ77_COST)
     d = Dictionary(zdict, ctx, chain=chained) if own else zdict     # (as in _compress)
     try:
+        if shuffle is not None:
+            return ctx.encode_batch_packed_host(fmt, records, d, opts, shuffle=shuffle)
         return ctx.encode_batch_packed_host(fmt, records, d, opts)
     finally:
         if own:
             d.close()
 
 
-def _decompress(fmt, data, zdict, context):
+def _decompress(fmt, data, zdict, context, shuffle=None):
     """the one-shot inverse of _compress: the size call in front for the capacity (lfx_decode_size_host), then decode_host;
-    with a dictionary decode_dict_host, whose capacity grows (the size calls take no dictionary)"""
+    with a dictionary decode_dict_host, whose capacity grows (the size calls take no dictionary).  shuffle: the batch of one
+    record, which unshuffles on the device"""
+    if shuffle is not None:
+        return _decompress_batch(fmt, [data], zdict, context, shuffle)[0]
     from .context import Dictionary, default_context
     ctx = context if context is not None else default_context()
     data = bytes(data)
@@ -151,7 +158,7 @@ def _decompress(fmt, data, zdict, context):
     return out
 
 
-def _decompress_batch(fmt, records, zdict, context):
+def _decompress_batch(fmt, records, zdict, context, shuffle=None):
     """the inverse of _compress_batch: Context.decode_batch_packed_host; the first failed record raises StreamError with its
     index in front of the library's message"""
     from .context import Dictionary, default_context
@@ -159,7 +166,10 @@ def _decompress_batch(fmt, records, zdict, context):
     own = zdict is not None and not hasattr(zdict, "handle")
     d = Dictionary(zdict, ctx) if own else zdict
     try:
-        outs, statuses = ctx.decode_batch_packed_host(fmt, records, d)
+        if shuffle is not None:
+            outs, statuses = ctx.decode_batch_unshuffle_host(fmt, records, shuffle, d)
+        else:
+            outs, statuses = ctx.decode_batch_packed_host(fmt, records, d)
         msg = ctx.last_error()
     finally:
         if own:
@@ -170,33 +180,41 @@ def _decompress_batch(fmt, records, zdict, context):
     return outs
 
 
-def decompress(data, zdict=None, context=None):
+def decompress(data, zdict=None, context=None, shuffle=None):
     """compress's inverse: one raw DEFLATE stream → its bytes.  zdict: the preset dictionary the stream was made with, bytes or
-    a libflate_amd.Dictionary (what zlib.decompressobj(wbits=-15, zdict=...) takes).  Raises StreamError where the stream fails."""
-    return _decompress(_ffi.DEFLATE, data, zdict, context)
+    a libflate_amd.Dictionary (what zlib.decompressobj(wbits=-15, zdict=...) takes).  Raises StreamError where the stream fails.
+    shuffle: the element size the decoded bytes were shuffled with — they are unshuffled on the device behind the decode
+    (libflate_amd.filters.unshuffle); None: no such step."""
+    return _decompress(_ffi.DEFLATE, data, zdict, context, shuffle)
 
 
-def decompress_batch(records, zdict=None, context=None):
+def decompress_batch(records, zdict=None, context=None, shuffle=None):
     """compress_batch's inverse: a list of raw DEFLATE streams (bytes) → the list of their bytes, in one upload, one decode of
     all records placed back to back by their decoded sizes (lfx_decode_batch_packed_device) and one download.
-    One zdict serves every record.  A failed record raises StreamError; the message names its index."""
-    return _decompress_batch(_ffi.DEFLATE, records, zdict, context)
+    One zdict serves every record.  A failed record raises StreamError; the message names its index.
+    shuffle: the element size the decoded bytes were shuffled with — they are unshuffled on the device behind the decode
+    (libflate_amd.filters.unshuffle); None: no such step."""
+    return _decompress_batch(_ffi.DEFLATE, records, zdict, context, shuffle)
 
 
-def compress_batch(records, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False):
+def compress_batch(records, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False, shuffle=None):
     """[compress(r, ...) for r in records] — a list of bytes to the list of their raw DEFLATE streams — in one upload, one
     encode of all records (lfx_encode_batch_packed_device) and one download of the streams packed back to
-    back.  The keywords are compress's; one zdict serves every record."""
-    return _compress_batch(_ffi.DEFLATE, records, zdict, options, context, lz77, level, merge_blocks)
+    back.  The keywords are compress's; one zdict serves every record.
+    shuffle: an element size, 1..256 — the input is byte-shuffled on the device in front of the encode (HDF5's shuffle filter,
+    libflate_amd.filters.shuffle); None: no such step."""
+    return _compress_batch(_ffi.DEFLATE, records, zdict, options, context, lz77, level, merge_blocks, shuffle)
 
 
-def compress(data, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False):
+def compress(data, zdict=None, options=None, context=None, lz77=None, level=None, merge_blocks=False, shuffle=None):
     """`data` as one raw DEFLATE stream, encoded in one call (one write_all + finish).  zdict: a preset dictionary, bytes or a
     libflate_amd.Dictionary — the stream then starts with the dictionary as history, what
     zlib.decompressobj(wbits=-15, zdict=...) reads (lfx_encode_dict_host).  lz77: an Lz77Encode of this package
     for the options, e.g. lz77.ChainLz77Encoder(8).  level: 1..9, shorthand for lz77=lz77.LevelLz77Encoder(level)
-    (DESIGN.md §23), exclusive with lz77.  merge_blocks=True: the options with merge_blocks()."""
-    return _compress(_ffi.DEFLATE, data, zdict, options, context, lz77, level, merge_blocks)
+    (DESIGN.md §23), exclusive with lz77.  merge_blocks=True: the options with merge_blocks().
+    shuffle: an element size, 1..256 — the input is byte-shuffled on the device in front of the encode (HDF5's shuffle filter,
+    libflate_amd.filters.shuffle); None: no such step."""
+    return _compress(_ffi.DEFLATE, data, zdict, options, context, lz77, level, merge_blocks, shuffle)
 
 
 class Decoder(_DecoderBase):

@@ -147,36 +147,44 @@ def list_members(data, context=None):
     return members
 
 
-def compress(data, options=None, context=None, lz77=None, level=None, merge_blocks=False):
+def compress(data, options=None, context=None, lz77=None, level=None, merge_blocks=False, shuffle=None):
     """`data` as one gzip member, encoded in one call (one write_all + finish; modification time 0 unless the options say
     otherwise).  lz77: an Lz77Encode of this package for the options, e.g. lz77.ChainLz77Encoder(8).  level:
     1..9, shorthand for lz77=lz77.LevelLz77Encoder(level), exclusive with lz77.  merge_blocks=True: the options
-    with merge_blocks()."""
+    with merge_blocks().
+    shuffle: an element size, 1..256 — the input is byte-shuffled on the device in front of the encode (HDF5's shuffle filter,
+    libflate_amd.filters.shuffle); None: no such step."""
     if options is None:
         options = EncodeOptions()
-    return _deflate._compress(_ffi.GZIP, data, None, options, context, lz77, level, merge_blocks)
+    return _deflate._compress(_ffi.GZIP, data, None, options, context, lz77, level, merge_blocks, shuffle)
 
 
-def compress_batch(records, options=None, context=None, lz77=None, level=None, merge_blocks=False):
+def compress_batch(records, options=None, context=None, lz77=None, level=None, merge_blocks=False, shuffle=None):
     """[compress(r, ...) for r in records] — a list of bytes to the list of their gzip members — in one upload, one encode of
     all records (lfx_encode_batch_packed_device) and one download of the members packed back to back.  The
-    keywords are compress's."""
+    keywords are compress's.
+    shuffle: an element size, 1..256 — the input is byte-shuffled on the device in front of the encode (HDF5's shuffle filter,
+    libflate_amd.filters.shuffle); None: no such step."""
     if options is None:
         options = EncodeOptions()
-    return _deflate._compress_batch(_ffi.GZIP, records, None, options, context, lz77, level, merge_blocks)
+    return _deflate._compress_batch(_ffi.GZIP, records, None, options, context, lz77, level, merge_blocks, shuffle)
 
 
-def decompress(data, context=None):
+def decompress(data, context=None, shuffle=None):
     """compress's inverse: one gzip member → its bytes, CRC-32 checked (bytes behind the member are left unread, as by
-    Decoder; concatenated members: decode_members).  Raises StreamError where the member fails."""
-    return _deflate._decompress(_ffi.GZIP, data, None, context)
+    Decoder; concatenated members: decode_members).  Raises StreamError where the member fails.
+    shuffle: the element size the decoded bytes were shuffled with — they are unshuffled on the device behind the decode
+    (libflate_amd.filters.unshuffle); None: no such step."""
+    return _deflate._decompress(_ffi.GZIP, data, None, context, shuffle)
 
 
-def decompress_batch(records, context=None):
+def decompress_batch(records, context=None, shuffle=None):
     """compress_batch's inverse: a list of gzip members (bytes) → the list of their bytes, in one upload, one decode of all
     records placed back to back by their decoded sizes (lfx_decode_batch_packed_device) and one download.  A
-    failed record raises StreamError; the message names its index."""
-    return _deflate._decompress_batch(_ffi.GZIP, records, None, context)
+    failed record raises StreamError; the message names its index.
+    shuffle: the element size the decoded bytes were shuffled with — they are unshuffled on the device behind the decode
+    (libflate_amd.filters.unshuffle); None: no such step."""
+    return _deflate._decompress_batch(_ffi.GZIP, records, None, context, shuffle)
 
 
 def encode_members(data, member_size=1 << 20, bgzf=False, options=None, context=None, lz77=None):

@@ -12,6 +12,7 @@
 mod ffi;
 pub mod deflate;
 pub mod dict;
+pub mod filters;
 pub mod gzip;
 pub mod lz77;
 pub mod non_blocking;
